@@ -16,8 +16,11 @@ N > 1: the corpus is sharded by video range (strong scaling: total work fixed), 
 (tvretrieval_amd/dist.py).
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (K6) against the dense bf16 MFMA peak using
-its algorithmic flops 2*Nq*Nv_local*L*H per launch and HIP-event durations measured inside the timed region;
-`cpu_baseline` is the oracle (reference formulation, torch CPU) on a bounded sample, rank 0 / N=1 only.
+its algorithmic flops 2*Nq*Nv_local*L*H per launch and HIP-event durations measured inside the timed region.
+A plain run sets up, warms up, times the steps and prints the line.  --full adds everything else: the per-stage breakdown
+(one extra untimed step), `cpu_baseline` (the oracle, reference formulation, torch CPU, on a bounded sample, rank 0 / N=1
+only), and the `extras` legs (other configurations and modes; N > 1: the other rerank scheme and exact-rank mode).
+--dump-outputs DIR writes the lists the last timed step returned as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -51,6 +54,8 @@ RAGGED = {"c3r", "tinyr", "tvr_val"}
 PEAK_TFLOPS = {"bf16": 2500.0, "f32": 157.3}     # dense MFMA peaks, MI355X_MICROARCH.md
 CHUNK = int(os.environ.get("XML_BENCH_CHUNK", "2048"))  # videos per synthetic / encode batch (>= 3072 GEMM tiles: persistent kernel)
 SHARD_ALIGN = 64                                  # shard boundaries: one K6 round of an XCD set = 8 XCDs x 4 tiles x 2 videos
+DUMP_Q2C_ROWS = 128                               # --dump-outputs: rows of the (Nq, Nv) q2c matrix kept (fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
 
 
 def model_config(hidden, dv, ds, dq, ctx_mode, max_ctx_l):
@@ -285,6 +290,7 @@ def run_extras(args, headline_qps):
         import copy
         a = copy.copy(args)
         a.workload, a.steps, a.warmup, a.no_cpu_baseline, a.no_extras = workload, steps, warmup, True, True
+        a.full, a.dump_outputs = True, None          # (--full: the stage breakdown below)
         r = run(a, emit=False)
         keep = {"value": r["value"], "unit": r["unit"], "ms_per_step": r["ms_per_step"], "dtype": r["dtype"],
                 "steps": steps, "workload": r["config"]["workload"], "k6_tflops": r["roofline"]["achieved"],
@@ -449,12 +455,30 @@ def summary_of(res):
             "c2_qps": g(ex, "c2", "value")}
 
 
+def dump_outputs(out, dirname):
+    """--dump-outputs: what vcmr_search handed its caller in the last timed step, one DIR/<name>.npy per array -- scores
+    float32, indices float64 (exact for every int32).  q2c (Nq, Nv) is larger than the budget: q2c_sample keeps a fixed,
+    seeded set of DUMP_Q2C_ROWS of its rows, in ascending query order (absent in exact-rank mode, which never forms q2c)."""
+    arrays = {name: out[name].cpu().numpy().astype(np.float64 if name.endswith("indices") else np.float32)
+              for name in ("top_scores", "top_indices", "flat_scores", "flat_indices")}
+    q2c = out.get("q2c")
+    if q2c is not None:
+        nq = q2c.shape[0]
+        rows = np.sort(np.random.default_rng(2018).choice(nq, min(DUMP_Q2C_ROWS, nq), replace=False))
+        arrays["q2c_sample"] = q2c[torch.from_numpy(rows).to(q2c.device)].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def extras_in_child(args, headline_qps, timeout_s=420):
     """run_extras in a CHILD process: whatever happens there (a device fault in an experimental leg, a timeout) cannot cost
     the headline measurement, which the parent already holds.  The child prints one JSON object."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--extras-only", repr(float(headline_qps)), "--steps", str(args.steps),
-           "--warmup", str(args.warmup)]
+           "--warmup", str(args.warmup), "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     t0 = time.perf_counter()
     try:
@@ -538,7 +562,7 @@ def run(args, backend_factory=None, emit=True):
     enc_dev_s = enc_ev[0].elapsed_time(enc_ev[1]) * 1e-3
     del storage
     enc_bf16_s = None
-    if world == 1 and not multi and be.name == "hip" and args.workload == "c3" and not args.no_extras \
+    if args.full and world == 1 and not multi and be.name == "hip" and args.workload == "c3" and not args.no_extras \
             and dtype == torch.bfloat16 and not exact:
         # the same corpus with the RAW features resident as bf16 (the C ABI takes f32 or the compute dtype, x_dt of
         # xml_linear_ln_relu_pos): the input LayerNorm then reads half the bytes -- 3.2 GB less per 2 048 videos
@@ -641,12 +665,16 @@ def run(args, backend_factory=None, emit=True):
     be.sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = None             # (a step's outputs are released before the next step starts)
+        last = step()
     be.sync()
     if multi:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     inf.K6_TIMER = None
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs)
+    del last
     exact_info = None
     if exact and exact_flags:
         timed_flags = exact_flags[-args.steps:]
@@ -669,7 +697,7 @@ def run(args, backend_factory=None, emit=True):
 
     # ---- N > 1: the OTHER rerank scheme, same index, same steps (the headline keeps the scheme the flags chose) --------
     alt_scheme = None
-    if multi and not args.no_extras:
+    if multi and args.full and not args.no_extras:
         alt_owner = bool(args.sharded_rerank)          # headline = sharded rerank -> alternative = owner rerank, and v.v.
         if alt_owner and index.feat2_all is None:
             xdist.replicate_rerank_features(index)
@@ -697,7 +725,7 @@ def run(args, backend_factory=None, emit=True):
     # ---- N > 1: the same sharded pass in exact-rank mode (ops.F16S model with the same weights; every shard hands its
     #      exact local top-k to the merge), so that one line carries bf16 and identical-lists throughput at this N ----------
     exact_sharded = None
-    if multi and not args.no_extras and be.name == "hip" and not exact and dtname == "bf16":
+    if multi and args.full and not args.no_extras and be.name == "hip" and not exact and dtname == "bf16":
         xi = m16 = None
         build_err = None
         try:        # local part first; the ranks then AGREE to run the leg (a rank failing alone must not leave the others
@@ -713,7 +741,8 @@ def run(args, backend_factory=None, emit=True):
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         if int(flag.item()) == 0:
             exact_sharded = {"error": build_err or "another rank could not build its exact-rank shard"}
-    if exact_sharded is None and multi and not args.no_extras and be.name == "hip" and not exact and dtname == "bf16":
+    if exact_sharded is None and multi and args.full and not args.no_extras and be.name == "hip" and not exact \
+            and dtname == "bf16":
         try:
             with torch.no_grad():
                 if not args.sharded_rerank:
@@ -760,9 +789,9 @@ def run(args, backend_factory=None, emit=True):
                       / (k6_avg_ms * 1e-3) / 1e12)
     achieved = flops_per_launch / (k6_avg_ms * 1e-3) / 1e12
 
-    # ---- stage breakdown, one extra untimed step --------------------------------------------------------
+    # ---- --full: stage breakdown, one extra untimed step ------------------------------------------------
     breakdown = {}
-    if not multi:
+    if args.full and not multi:
         def timed(name, fn):
             s, e = be.event(), be.event()
             s.record(); r = fn(); e.record(); be.sync()
@@ -786,7 +815,7 @@ def run(args, backend_factory=None, emit=True):
                 st, ed = timed("convse_k7", lambda: inf.stage_span_probs(model, index, qvec, ti, ops,
                                                                          **(dict(vid_len=vl) if vl is not None else {})))
                 timed("moment_k9", lambda: ops.moment_topk(st, ed, tw, index.l_ref, 2, 16, 200, **rk))
-    else:       # rank 0's view of one sharded pass, collectives (and the waiting for slower ranks in them) included
+    elif args.full:     # rank 0's view of one sharded pass, collectives (and the waiting for slower ranks in them) included
         marks = []
 
         def mark(name):
@@ -855,7 +884,7 @@ def run(args, backend_factory=None, emit=True):
             res["ragged_corpus"] = ragged
             res["roofline"]["note"] = "ragged corpus: `achieved` prices the VALID clip rows (algorithmic work); " \
                                       "executed_tflops in ragged_corpus prices the padded rows the MFMA pipe actually ran"
-        if world == 1 and not args.no_cpu_baseline and be.name == "hip" and not exact:
+        if args.full and world == 1 and not args.no_cpu_baseline and be.name == "hip" and not exact:
             def search(nq_s, nv_s):       # the baseline's slice through the HIP path, for the agreement figures
                 with torch.no_grad():
                     sub = inf.build_corpus_index(model, context_batches(0, nv_s, l, dv, ds, model.use_video,
@@ -875,7 +904,8 @@ def run(args, backend_factory=None, emit=True):
             res["cpu_baseline"] = cpu_baseline(model, cfg, index, qf, qm, nv, dtname, search, search_exact)
         else:
             res["cpu_baseline"] = None
-        if world == 1 and not multi and be.name == "hip" and args.workload == "c3" and not args.no_extras and not exact:
+        if args.full and world == 1 and not multi and be.name == "hip" and args.workload == "c3" and not args.no_extras \
+                and not exact:
             enc_flops = 2.0 * l * hidden * (dv + ds) + 44.0 * l * hidden ** 2 + 24.0 * l ** 2 * hidden
             enc_tf = res["encode_videos_per_s"] * enc_flops / 1e12
             extras = {"encode": {"videos_per_s": res["encode_videos_per_s"],
@@ -933,11 +963,22 @@ def main(argv=None, backend_factory=None, script=None):
     ap.add_argument("--exact-rank", action="store_true",
                     help="run the pass in exact-rank mode (f32 model, bf16 K6 as a filter + f32 re-score + certificate): the "
                          "f32 path's lists; any N (every shard hands its exact local top-k to the merge)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure the stage breakdown, the CPU baseline and the extra legs "
+                         "(a plain run sets up, warms up, times --steps steps and prints the line)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1, c3: skip the extra legs (exact-rank mode, c2, c3r, training step) after the headline run")
+                    help="with --full, N = 1, c3: skip the extra legs (exact-rank mode, c2, c3r, training step) after the "
+                         "headline run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the lists the last timed step returned (and a fixed sample of its q2c rows) as DIR/<name>.npy; "
+                         "single process only")
     ap.add_argument("--extras-only", default=None, metavar="HEADLINE_QPS",
-                    help="(internal) run only the extra legs of the default run and print them as one JSON object")
+                    help="(internal) run only the extra legs of the --full run and print them as one JSON object")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_sharded):
+        ap.error("--dump-outputs needs a single-process run (--gpus 1 without --force-sharded)")
     if args.extras_only is not None:
         torch.cuda.set_device(0)
         print(json.dumps(run_extras(args, float(args.extras_only))), flush=True)

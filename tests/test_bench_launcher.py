@@ -21,7 +21,7 @@ def _run(argv, timeout=900, script="bench.py", **extra_env):
 
 
 def test_bench_self_spawns_two_gloo_ranks():
-    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "tiny", "--no-cpu-baseline"],
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "tiny", "--no-cpu-baseline", "--full"],
              script="bench_cpu_entry.py")
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -42,7 +42,7 @@ def test_bench_self_spawns_two_gloo_ranks():
 def test_bench_self_spawns_eight_gloo_ranks():
     """The driver's 8-GPU command line, rehearsed on CPU: `bench.py --gpus 8` through its own launcher, 8 gloo ranks, the
     300-video test corpus cut into 8 shards, both rerank schemes timed, one JSON line."""
-    r = _run(["--gpus", "8", "--steps", "1", "--warmup", "0", "--workload", "tiny", "--no-cpu-baseline"],
+    r = _run(["--gpus", "8", "--steps", "1", "--warmup", "0", "--workload", "tiny", "--no-cpu-baseline", "--full"],
              script="bench_cpu_entry.py", timeout=1500)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -64,7 +64,7 @@ def test_bench_rank_failure_propagates():
 def test_bench_tiny_forced_sharded_on_gpu():
     """Same entry on the GPU box: the N > 1 code path through a real 1-rank RCCL group."""
     r = _run(["--gpus", "1", "--force-sharded", "--workload", "tiny", "--steps", "2", "--warmup", "1",
-              "--no-cpu-baseline"])
+              "--no-cpu-baseline", "--full"])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["config"]["backend"] == "hip" and res["config"]["ranks_in_process_group"] == 1
@@ -85,3 +85,53 @@ def test_bench_refuses_to_measure_fallback_collectives():
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["config"]["collectives_fallback"] == 1 and res["config"]["collectives"].startswith("torch.distributed")
+
+
+def _dump_run(tmp_path, name, steps, warmup, script):
+    import numpy as np
+    out = tmp_path / name
+    r = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--workload", "tiny", "--dump-outputs", str(out)],
+             script=script)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert lines[-1].startswith("{") and sum(ln.startswith("{") for ln in lines) == 1, lines
+    res = json.loads(lines[-1])
+    arrays = {p.stem: np.load(p) for p in sorted(out.glob("*.npy"))}
+    return res, arrays
+
+
+def _check_plain_run_and_dump(tmp_path, script):
+    """A plain run times exactly --steps steps and measures nothing beside the headline (no stage breakdown, CPU baseline or
+    extra legs); --dump-outputs writes the last timed step's lists, and the same arguments give the same arrays."""
+    import numpy as np
+    res1, a1 = _dump_run(tmp_path, "a", 1, 0, script)
+    res2, a2 = _dump_run(tmp_path, "b", 2, 1, script)
+    for res, steps in ((res1, 1), (res2, 2)):
+        assert res["steps"] == steps and res["roofline"]["launches_timed"] == steps
+        assert res["ms_per_step"] > 0 and abs(res["value"] - 64 * 1e3 / res["ms_per_step"]) < 1e-6 * res["value"]
+        assert res["breakdown_ms"] == {} and res["cpu_baseline"] is None and "extras" not in res
+    assert set(a1) == {"top_scores", "top_indices", "flat_scores", "flat_indices", "q2c_sample"}, sorted(a1)
+    assert a1["top_scores"].shape == a1["top_indices"].shape == (64, 100)
+    assert a1["flat_scores"].shape == a1["flat_indices"].shape == (64, 200)
+    assert a1["q2c_sample"].shape == (64, 300)
+    assert sum(a.nbytes for a in a1.values()) <= 64 << 20
+    for name, a in a1.items():
+        assert a.dtype == (np.float64 if name.endswith("indices") else np.float32), (name, a.dtype)
+        assert np.array_equal(a, a2[name]), name
+    assert (a1["top_indices"] >= 0).all() and (a1["top_indices"] < 300).all()
+    assert (np.diff(a1["top_scores"], axis=1) <= 0).all()
+
+
+def test_plain_run_and_dump_outputs(tmp_path):
+    _check_plain_run_and_dump(tmp_path, "bench_cpu_entry.py")
+
+
+def test_dump_outputs_refuses_several_ranks():
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "tiny", "--dump-outputs", "unused"],
+             script="bench_cpu_entry.py", timeout=120)
+    assert r.returncode != 0 and "--dump-outputs needs a single-process run" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_and_dump_outputs_on_gpu(tmp_path):
+    _check_plain_run_and_dump(tmp_path, "bench.py")

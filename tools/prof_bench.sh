@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 RAW=/tmp/prof_bench; OUT=$R/gpurun_out; mkdir -p $RAW $OUT
-CMD="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+CMD="python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/stats -o bench -- $CMD > $RAW/stats.log 2>&1
 echo "stats rc=$?"; tail -1 $RAW/stats.log | cut -c1-400
 f=$(find $RAW/stats -name "*kernel_stats.csv" | head -1)
@@ -15,7 +15,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python - <<PY > $OUT/bench_pmc_traffic.txt
 import csv, glob, collections
-print("# rocprofv3 --pmc <counter> --kernel-trace -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline  (one pass per counter)")
+print("# rocprofv3 --pmc <counter> --kernel-trace -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline  (one pass per counter)")
 print("# per-launch averages; FETCH_SIZE/WRITE_SIZE are in KiB as reported (uncorrected)")
 for f in sorted(glob.glob("$RAW/*/**/*counter_collection.csv", recursive=True)):
     agg = collections.defaultdict(lambda: [0.0, 0])
