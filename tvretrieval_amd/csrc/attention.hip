@@ -648,7 +648,7 @@ extern "C" int xml_attention_block(const void* x, const float* key_mask, const v
     return XML_OK;
   rc = xmli_gemm(att, wo, bo, x, pre, rows, hidden, hidden, 0, /*residual*/ 2, 1, /*out_f32*/ 1, dt, st, sws);
   if (rc) return rc;
-  return xmli_add_layernorm(pre, XML_F32, nullptr, ln_g, ln_b, y, rows, hidden, hidden, adt, st);
+  return xmli_gemm_ln_tail((const float*)pre, ln_g, ln_b, y, rows, hidden, dt, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -720,7 +720,7 @@ extern "C" int xml_attention_block_varlen(const void* x, const int32_t* cu_seqle
     return XML_OK;
   rc = xmli_gemm(att, wo, bo, x, pre, rows, hidden, hidden, 0, /*residual*/ 2, 1, /*out_f32*/ 1, dt, st, sws);
   if (rc) return rc;
-  return xmli_add_layernorm(pre, XML_F32, nullptr, ln_g, ln_b, y, rows, hidden, hidden, adt, st);
+  return xmli_gemm_ln_tail((const float*)pre, ln_g, ln_b, y, rows, hidden, dt, st);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -739,12 +739,13 @@ static int launch_gemm256p(const void* A, const void* W, const float* bias, cons
 }
 
 // ---- GEMM with the LayerNorm in its epilogue --------------------------------------------------------------------
-// Taken for a SHAPE CLASS, never for a batch size above some tile count: rows that span 1-3 whole 256-column tiles
-// (N = 256 / 512 / 768), K a whole number of 128-byte steps, and at least LN_FUSED_MIN_ROWS rows.  Whether a projection
-// runs fused therefore does not depend on how many videos a context batch holds (any batch of >= 16 videos of 128 clips
-// qualifies): the encoder's bits are the same for context batches of 2 048, 200 or 37 videos
-// (tests/test_gpu_model.py::test_index_bits_do_not_depend_on_the_context_batch).  Below the row threshold (a 50-query batch's
-// 1 500 tokens) the callers run GEMM (f32 out) + LayerNorm: small tiles fill the chip there, six row blocks would not.
+// Taken for a SHAPE CLASS: rows that span 1-3 whole 256-column tiles (N = 256 / 512 / 768), K a whole number of 128-byte
+// steps, and at least LN_FUSED_MIN_ROWS rows.  Below the row threshold (a 50-query batch's 1 500 tokens, the 10-video tail
+// of a corpus) the callers run GEMM (f32 out) + xmli_gemm_ln_tail: small tiles fill the chip there, six row blocks would
+// not.  That LayerNorm has this epilogue's statistics, operation for operation, and the GEMM forms are bitwise alike, so a
+// row's bits do not depend on which side of the threshold its launch falls: the encoder's bits are the same for context
+// batches of 2 048, 200, 37 or 2 090 + 10 videos, and a 50-query batch gives its rows of a whole pass
+// (tests/test_gpu_row_invariance.py, tests/test_gpu_model.py::test_index_bits_do_not_depend_on_the_context_batch).
 // The fused kernel waits for nothing outside its workgroup, so it has no residency requirement and no failure path.
 static constexpr int64_t LN_FUSED_MIN_ROWS = 2048;
 
@@ -767,6 +768,124 @@ int xmli_gemm_ln(const void* A, const void* W, const float* bias, const void* ad
                                                       ln_b, ln_ws);
   return launch_gemm256p<bf16_t, bf16_t, bf16_t, true>(A, W, bias, addend, y, M, N, K, relu, add_mode, seq_len, st, ln_g,
                                                         ln_b, ln_ws);
+}
+
+// ---- the LayerNorm of the three-launch path (GEMM with f32 out + LayerNorm), in the LNE epilogue's arithmetic -------------
+// Below LN_FUSED_MIN_ROWS (or when the fused launch is refused) the callers write the pre-LayerNorm rows in f32 and normalise
+// them here.  For the shape class of the LNE kernel (N = 256 / 512 / 768, f32 / bf16) the row statistics are those of the
+// epilogue above, operation for operation, so that a row's output bits do not depend on which side of the row threshold its
+// launch falls:
+//   * per row and 128-column segment (tile t, half wn), four lanes fg = 0..3 each sum their NGRP groups of GC consecutive
+//     columns (columns t 256 + wn 128 + q 4 GC + fg GC + e, q-major, e inner) -- the DIRECT accumulator layout, GC = 8 for
+//     2-byte outputs (PAIRED), 4 for f32;
+//   * the same butterfly (fg ^ 1, then fg ^ 2), the same centred sum of squares around the segment mean;
+//   * the same Chan combine over the 2 tn segments in the order (tile 0 left, tile 0 right, tile 1 left, ...), the same
+//     normalise expression.
+// Lane sub of a row's LPR lanes holds segment sub >> 2 as lane fg = sub & 3 (lanes 8 tn .. LPR - 1 of a row idle).  N and
+// eps arrive at run time as they do in the fused kernel: the divisions are lowered the same way.
+template <typename OutT, int TN>
+__global__ __launch_bounds__(64) void ln_lne_order_kernel(const float* __restrict__ pre, const float* __restrict__ ln_g,
+                                                           const float* __restrict__ ln_b, OutT* __restrict__ y,
+                                                           int64_t rows, int N, float ln_eps) {
+  // Every rounding as hipcc emits it for the epilogue (-ffp-contract=fast there): contraction is off here and each fused
+  // multiply-add is spelled out, so that the compiler's choices in this smaller kernel cannot differ from the big one.
+  // (Products with 128 or 1 / 128 are exact: for those, fused or not gives the same value.)
+#pragma clang fp contract(off)
+  constexpr int GC = sizeof(OutT) == 2 ? 8 : 4;
+  constexpr int NGRP = 128 / (4 * GC);
+  constexpr int LPR = TN == 1 ? 8 : TN == 2 ? 16 : 32;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (LPR - 1);
+  const int base = lane - sub;
+  const int64_t row = ((int64_t)blockIdx.x * 64 + threadIdx.x) / LPR;
+  if (row >= rows || sub >= 8 * TN) return;        // (no lane reads a shuffle from a lane that left: rows are whole)
+  const int seg = sub >> 2, fg = sub & 3;
+  const int c0 = (seg >> 1) * 256 + (seg & 1) * 128 + fg * GC;
+  const float* pr = pre + row * N;
+  // gamma / beta are read together with the row: one memory round trip (left to itself, hipcc sinks these loads to their
+  // use behind the statistics and waits for each pair in turn; the empty asm pins the values here)
+  float v[NGRP][GC], gv[NGRP][GC], bv[NGRP][GC];
+#pragma unroll
+  for (int q = 0; q < NGRP; ++q)
+#pragma unroll
+    for (int e = 0; e < GC; e += 4) {
+      const float4 f = *reinterpret_cast<const float4*>(pr + c0 + q * (4 * GC) + e);
+      const float4 g4 = *reinterpret_cast<const float4*>(ln_g + c0 + q * (4 * GC) + e);
+      const float4 b4 = *reinterpret_cast<const float4*>(ln_b + c0 + q * (4 * GC) + e);
+      v[q][e] = f.x; v[q][e + 1] = f.y; v[q][e + 2] = f.z; v[q][e + 3] = f.w;
+      gv[q][e] = g4.x; gv[q][e + 1] = g4.y; gv[q][e + 2] = g4.z; gv[q][e + 3] = g4.w;
+      bv[q][e] = b4.x; bv[q][e + 1] = b4.y; bv[q][e + 2] = b4.z; bv[q][e + 3] = b4.w;
+    }
+#pragma unroll
+  for (int q = 0; q < NGRP; ++q)
+#pragma unroll
+    for (int e = 0; e < GC; ++e) asm volatile("" : "+v"(v[q][e]), "+v"(gv[q][e]), "+v"(bv[q][e]));
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < NGRP; ++q)
+#pragma unroll
+    for (int e = 0; e < GC; ++e) s += v[q][e];
+  s += __shfl_xor(s, 1, 64);                        // fg ^ 1, then fg ^ 2: the epilogue's shfl_xor 16 / 32
+  s += __shfl_xor(s, 2, 64);
+  // centred squares around the segment mean: c2 = fma(c0, c0, c1 * c1), then c2 = fma(c, c, c2) in order
+  const float* vf = &v[0][0];
+  const float cs0 = __builtin_fmaf(s, -1.0f / 128.0f, vf[0]), cs1 = __builtin_fmaf(s, -1.0f / 128.0f, vf[1]);
+  float c2 = __builtin_fmaf(cs0, cs0, cs1 * cs1);
+#pragma unroll
+  for (int k = 2; k < NGRP * GC; ++k) {
+    const float c = __builtin_fmaf(s, -1.0f / 128.0f, vf[k]);
+    c2 = __builtin_fmaf(c, c, c2);
+  }
+  c2 += __shfl_xor(c2, 1, 64);
+  c2 += __shfl_xor(c2, 2, 64);
+  // Chan's combine over the segments (tile 0 left, tile 0 right, tile 1 left, ...)
+  typedef float xml_f4 __attribute__((ext_vector_type(4)));
+  xml_f4 pv[3];
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+    pv[t] = t < TN ? xml_f4{__shfl(s, base + t * 8, 64), __shfl(c2, base + t * 8, 64), __shfl(s, base + t * 8 + 4, 64),
+                            __shfl(c2, base + t * 8 + 4, 64)}
+                   : xml_f4{0.f, 0.f, 0.f, 0.f};
+  float tot = 0.f;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) tot += pv[t].x + pv[t].z;
+  const float mean = tot / (float)N;
+  float m2 = 0.f;
+#pragma unroll
+  for (int t = 0; t < TN; ++t) {
+    const float d0 = __builtin_fmaf(pv[t].x, 1.0f / 128.0f, -mean), d1 = __builtin_fmaf(pv[t].z, 1.0f / 128.0f, -mean);
+    float u = __builtin_fmaf(d0, 128.0f * d0, pv[t].y);
+    u = pv[t].w + u;
+    u = __builtin_fmaf(d1, 128.0f * d1, u);
+    m2 = u + m2;
+  }
+  const float rstd = 1.0f / sqrtf(m2 / (float)N + ln_eps);
+#pragma unroll
+  for (int q = 0; q < NGRP; ++q) {
+    float o[GC];
+#pragma unroll
+    for (int e = 0; e < GC; ++e) o[e] = __builtin_fmaf((v[q][e] - mean) * rstd, gv[q][e], bv[q][e]);
+    st_global16(y + row * N + c0 + q * (4 * GC), pack16<OutT>(o));
+  }
+}
+
+int xmli_gemm_ln_tail(const float* pre, const float* ln_g, const float* ln_b, void* y, int64_t M, int N, int dt,
+                      hipStream_t st) {
+  const int tn = N / 256;
+  if ((dt != XML_F32 && dt != XML_BF16) || N % 256 || tn < 1 || tn > 3 || M <= 0)     // (split-f16 models: plain LayerNorm)
+    return xmli_add_layernorm(pre, XML_F32, nullptr, ln_g, ln_b, y, M, N, N, xmli_act_dt(dt), st);
+  const int lpr = tn == 1 ? 8 : tn == 2 ? 16 : 32;
+  const dim3 grid((unsigned)cdiv(M * lpr, (int64_t)64)), blk(64);      // one wave per workgroup: 1 500 rows -> 188 / 750 of them
+#define XML_LNT(OT, TN)                                                                                                 \
+  hipLaunchKernelGGL((ln_lne_order_kernel<OT, TN>), grid, blk, 0, st, pre, ln_g, ln_b, (OT*)y, M, N, 1e-5f)
+  if (dt == XML_F32) {
+    if (tn == 1) XML_LNT(float, 1); else if (tn == 2) XML_LNT(float, 2); else XML_LNT(float, 3);
+  } else {
+    if (tn == 1) XML_LNT(bf16_t, 1); else if (tn == 2) XML_LNT(bf16_t, 2); else XML_LNT(bf16_t, 3);
+  }
+#undef XML_LNT
+  XML_CHECK_LAUNCH();
+  return XML_OK;
 }
 
 // worth it when every workgroup gets several tiles; below that the one-tile-per-workgroup kernel is as good

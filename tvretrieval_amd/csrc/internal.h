@@ -17,6 +17,10 @@ size_t xmli_gemm_ln_workspace_bytes(int64_t M, int N);
 int xmli_gemm_ln(const void* A, const void* W, const float* bias, const void* addend, const float* ln_g, const float* ln_b,
                  void* y, int64_t M, int N, int K, int relu, int add_mode, int seq_len, int dt, void* ln_ws,
                  hipStream_t st);
+// the LayerNorm behind a GEMM with f32 out (the callers' path when xmli_gemm_ln is not taken): y = LN(pre) * g + b in act_dt(dt);
+// for xmli_gemm_ln's shape class (N = 256 / 512 / 768, f32 / bf16) with that epilogue's statistics, bit for bit
+int xmli_gemm_ln_tail(const float* pre, const float* ln_g, const float* ln_b, void* y, int64_t M, int N, int dt,
+                      hipStream_t st);
 // y = LN(a + b) ; a may be f32 while b / y are dt ; rows of y have stride ld_out (>= d, tail zero-filled)
 int xmli_add_layernorm(const void* a, int a_dt, const void* b, const float* g, const float* beta, void* y,
                        int64_t rows, int d, int ld_out, int dt, hipStream_t st);

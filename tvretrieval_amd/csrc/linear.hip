@@ -72,7 +72,8 @@ static int launch_gemm(const void* A, const void* W, const float* bias, const vo
   // Few rows (the pooled-query linears of a 128-pair training batch, a 50-query batch's encoder): 128 x 128 tiles leave most
   // of the chip idle behind a serial K loop (128 x 768 x 768: 6 workgroups, 32 us).  Smaller tiles of the SAME mainloop -- every
   // output element sees the same MFMA sequence over K, the results are bit-identical -- until a few hundred workgroups exist
-  // (the small tiles also take the deep-prefetch K loop, gemm_mainloop_deep).
+  // (the small tiles also take the deep-prefetch K loop, gemm_mainloop_deep).  Every form here, gemm256 and gemm256p give
+  // the same bits for a row whatever M is: tests/test_gpu_row_invariance.py crosses each edge by one row.
   const int64_t wg128 = (int64_t)cdiv(N, 128) * cdiv(M, 128);
   const int bmn = wg128 >= 512 ? 128 : wg128 * 4 >= 192 ? 64 : 32;
   dim3 grid(cdiv(N, bmn), cdiv(M, bmn));
@@ -548,7 +549,7 @@ extern "C" int xml_linear_ln_relu_pos(const void* x, int x_dt, const float* ln_i
     return XML_OK;                                         // (a refused launch falls through to the 3-launch path)
   rc = xmli_gemm(xn, w, b, pos, pre, rows, hidden, d_pad, /*relu*/ 1, /*add_mode*/ 1, seq_len, /*out_f32*/ 1, dt, st, sws);
   if (rc) return rc;
-  return xmli_add_layernorm(pre, XML_F32, nullptr, ln_pos_g, ln_pos_b, y, rows, hidden, hidden, adt, st);
+  return xmli_gemm_ln_tail((const float*)pre, ln_pos_g, ln_pos_b, y, rows, hidden, dt, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -667,5 +668,5 @@ extern "C" int xml_linear_ln_relu_pos_packed(const void* x, int x_dt, const int3
     return XML_OK;
   rc = xmli_gemm(xn, w, b, pg, pre, rows, hidden, d_in, /*relu*/ 1, /*add_mode*/ 1, (int)rows, /*out_f32*/ 1, dt, st, sws);
   if (rc) return rc;
-  return xmli_add_layernorm(pre, XML_F32, nullptr, ln_pos_g, ln_pos_b, y, rows, hidden, hidden, adt, st);
+  return xmli_gemm_ln_tail((const float*)pre, ln_pos_g, ln_pos_b, y, rows, hidden, dt, st);
 }
