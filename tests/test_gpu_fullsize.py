@@ -227,7 +227,11 @@ def test_c3_exact_rank_mode_gives_the_fp32_lists(mode):
     print(res)
     v = res["vs_plain_f32"]
     assert v["video_positions_really_different"] == 0 and v["moment_positions_really_different"] == 0, v
-    assert v["top1_video_same"] == 1.0 and v["top1_moment_same"] >= 0.998, v      # (a differing top-1 is inside a tie: line above)
+    # a differing top-1 moment is inside an f32 tie: moment_positions_really_different comes from
+    # tools/bench_exact.py::tie_aware_diff, which walks EVERY differing position of the first 192, position 0 included, and
+    # counts it as "really different" unless the entry sits in the other list with a score within the tie tolerance -- so
+    # the line above already is the per-query tie check for the (at most 0.2 %) differing top-1s
+    assert v["top1_video_same"] == 1.0 and v["top1_moment_same"] >= 0.998, v
     if mode == "f32":      # same kernels behind the filter as the plain path: almost nothing may move
         assert v["video_positions_swapped_in_f32_ties"] <= 50 and v["moment_positions_swapped_in_f32_ties"] <= 100, v
         assert v["queries_with_identical_top100_order"] >= 990, v

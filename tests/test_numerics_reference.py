@@ -1,0 +1,224 @@
+"""CPU side of tests/test_gpu_numerics.py: the float64 oracle, the operand regimes and the assertion helpers, checked
+without a GPU.
+* the float64 forms equal the float32 oracle to float32 accuracy on the benign operands of test_gpu_kernels.py;
+* each generator achieves the figure it promises;
+* the float32 reference is finite in every regime and passes the new checks itself (as f32, and rounded to bf16 by torch),
+  the 1 % cap on rounding-boundary elements included;
+* sensitivity: deliberately wrong stand-ins are rejected by the check meant for them while the existing `close(...)`
+  limits of test_gpu_kernels.py accept them on that suite's operands."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import numerics_regimes as NR
+from oracle import f64
+from oracle import xml_oracle as O
+from test_gpu_kernels import _att_weights, _ragged_mask, close, rnd
+
+BF16, F32 = torch.bfloat16, torch.float32
+LN_REGIMES = sorted(NR.ROW_REGIMES)
+
+
+def test_float64_forms_equal_the_float32_oracle_on_benign_operands():
+    n, l, d_in, h, nh = 3, 24, 96, 128, 4
+    x = rnd(n, l, d_in, seed=10)
+    sd = {"LayerNorm.weight": 1 + 0.1 * rnd(d_in, seed=11), "LayerNorm.bias": 0.1 * rnd(d_in, seed=12),
+          "net.1.weight": rnd(h, d_in, seed=13, scale=d_in ** -0.5), "net.1.bias": 0.1 * rnd(h, seed=14)}
+    pe = {"position_embeddings.weight": rnd(l + 3, h, seed=15, scale=0.5), "LayerNorm.weight": 1 + 0.1 * rnd(h, seed=16),
+          "LayerNorm.bias": 0.1 * rnd(h, seed=17)}
+    want = O.trainable_pos_enc(O.linear_layer(x, O.Weights(sd)), O.Weights(pe))
+    got = f64.linear_ln_relu_pos(x, f64.Weights64(sd), f64.Weights64(pe))
+    assert got.dtype == torch.float64
+    close("K1+K2", got, want, 5e-6)
+    close("linear_layer", f64.linear_layer(x, f64.Weights64(sd)), O.linear_layer(x, O.Weights(sd)), 5e-6)
+    y = want
+    mask = _ragged_mask(n, l, 31)
+    sa = _att_weights(h, 40)
+    close("bert_attention", f64.bert_attention(y, mask.unsqueeze(1), f64.Weights64(sa), nh),
+          O.bert_attention(y, mask.unsqueeze(1), O.Weights(sa), nh), 1e-5)
+    att = O.Weights(sa).sub("self")
+    close("bert_self_attention", f64.bert_self_attention(y, y, y, mask.unsqueeze(1), f64.Weights64(sa).sub("self"), nh),
+          O.bert_self_attention(y, y, y, mask.unsqueeze(1), att, nh), 5e-6)
+    close("bert_self_output", f64.bert_self_output(y, x.new_ones(y.shape), f64.Weights64(sa).sub("output")),
+          O.bert_self_output(y, x.new_ones(y.shape), O.Weights(sa).sub("output")), 1e-5)
+    wm = rnd(2, h, seed=72, scale=h ** -0.5)
+    sc = torch.softmax(O.mask_logits(y @ wm.t(), mask.unsqueeze(2)), dim=1)
+    close("modular_pool", f64.modular_pool(y, mask, wm)[0], torch.einsum("blm,bld->mbd", sc, y), 5e-6)
+    q, c = F.normalize(rnd(7, h, seed=1), dim=-1), F.normalize(rnd(n, l, h, seed=2), dim=-1)
+    s = torch.max(O.mask_logits(torch.einsum("md,nld->mln", q, c), mask.t().unsqueeze(0)), dim=1)[0]
+    close("q2c", f64.q2c_scores(q, c, mask)[0], s, 1e-6)
+    # the staged form differs from the exact one by bf16 roundings, not by more
+    st = f64.bert_attention(y, mask.unsqueeze(1), f64.Weights64(sa), nh, f64.bf16_round, True)
+    err = float((st - f64.bert_attention(y, mask.unsqueeze(1), f64.Weights64(sa), nh)).abs().max())
+    assert 1e-4 < err < 8e-2, err
+
+
+def test_generators_achieve_their_figures():
+    x = NR.outlier_channels(64, 768)
+    big = (x.abs().mean(0) > 4).sum()
+    assert int(big) == 4 and 20 < float(x.abs().mean(0).max()) < 30
+    for d in (3072, 768):
+        x = NR.post_relu_unit(64, d)
+        assert bool((x >= 0).all()) and float((x.norm(dim=-1) - 1).abs().max()) < 1e-6
+        assert 0.5 < float((x.mean(-1) / x.std(-1)).mean()) < 1.5          # mean comparable to the standard deviation
+        assert abs(float(x.mean()) - 0.3989 / math.sqrt(d / 2)) < 0.1 * float(x.mean())
+    for mean, nm in ((10.0, "offset10"), (1e3, "offset1e3")):
+        x = NR.ROW_REGIMES[nm](64, 768)
+        assert abs(float(x.mean()) / mean - 1) < 0.01 and abs(float(x.var(-1).mean()) - 1) < 0.1
+    assert float(NR.tiny(64, 768).var(-1).max()) < 2e-8
+    c = NR.constant(64, 768)
+    assert bool((c == c[:, :1]).all()) and float(c.double().var(-1).max()) == 0.0 and c.unique().numel() > 16
+    oh = NR.one_hot(64, 768)
+    assert bool((oh.sum(-1) == 1).all()) and bool(((oh == 0) | (oh == 1)).all())
+    w = NR.layernorm_case("one_hot", 16, 768, F32)["W"]
+    assert float(w.abs().max()) > 0.7 * math.sqrt(768)
+    m = NR.mixed(64, 768)
+    norms = m.norm(dim=-1)
+    assert float(norms.max() / norms.min()) > 1e6                           # neighbouring rows 7 decades apart
+    for target, lo, hi in ((2.0, 0.05, 0.45), (6.0, 0.4, 0.95), (12.0, 0.8, 1.0)):
+        case = NR.attention_case(target, 4, 64, 128, 4, F32, holes=False, pre_ln=False)
+        print("peaked(%g): logit sd %.2f mean max prob %.3f" % (target, case["logit_std"], case["mean_max_prob"]))
+        assert 0.7 * target < case["logit_std"] < 1.4 * target
+        assert lo < case["mean_max_prob"] < hi
+        pc = NR.pool_case(target, 6, 30, 128, 2, F32, holes=True)
+        assert lo < pc["mean_max_prob"] <= 1.0
+    q, c = NR.near_duplicate_clips(8, 9, 32, 256)
+    cos = torch.einsum("vld,vd->vl", c.double(), q[torch.arange(9) % 8].double())
+    assert float(cos.min()) > 0.88 and float(cos.max()) > 1 - 1e-7
+    assert torch.equal(c[-1], c[0]) and bool(torch.signbit(c[:, ::4, 0]).all()) and bool((c[:, ::4, 0] == 0).all())
+    assert NR.is_prefix(NR.prefix_masks(9, 30)) and not NR.is_prefix(NR.hole_masks(9, 30))
+    pm, hm = NR.prefix_masks(9, 30), NR.hole_masks(9, 30)
+    assert pm[0].sum() == 30 and pm[1].sum() == 1 and hm[0].sum() == 30 and hm[1].sum() == 1 and bool((hm[:, 0] == 1).all())
+
+
+@pytest.mark.parametrize("regime", LN_REGIMES)
+def test_reference_passes_the_layernorm_and_l2norm_checks(regime):
+    """G := the float32 reference (c = 1 holds trivially) and G := torch's bf16 rounding of it: finite, half an ulp,
+    unbiased, under the boundary cap -- the generators are usable for the kernel checks."""
+    for dtype in (F32, BF16):
+        case = NR.layernorm_case(regime, 64, 768, dtype)
+        assert bool(torch.isfinite(case["R"]).all()) and bool(torch.isfinite(case["W"]).all())
+        if regime == "constant":
+            assert torch.equal(case["W"], case["beta"].double().expand_as(case["W"]))
+        NR.check_f32("ref layernorm", regime, case["R"], case["W"], case["R"], 1)
+        NR.check_bf16_rounding("ref layernorm", regime, case["R"].to(BF16), case["W"], case["R"], 2,
+                               strict=regime in NR.BF16_STRICT["layernorm"])
+        case = NR.l2norm_case(regime, 64, 768, dtype)
+        NR.check_f32("ref l2norm", regime, case["R"], case["W"], case["R"], 1)
+        NR.check_bf16_rounding("ref l2norm", regime, case["R"].to(BF16), case["W"], case["R"], 2,
+                               strict=regime in NR.BF16_STRICT["l2norm"])
+
+
+@pytest.mark.parametrize("regime", NR.BF16_STRICT["linear"])
+def test_reference_passes_the_linear_checks(regime):
+    for relu, addend in ((False, False), (True, False), (False, True)):
+        case = NR.linear_case(regime, 96, 256, 768, BF16, relu, addend)
+        assert bool(torch.isfinite(case["R"]).all())
+        NR.check_f32("ref linear", regime, case["R"], case["W"], case["R"], 1, case["scale"])
+        NR.check_bf16_rounding("ref linear", regime, case["R"].to(BF16), case["W"], case["R"], 2, case["scale"])
+
+
+def test_reference_is_finite_in_the_chain_regimes():
+    for regime in ("post_relu_unit", "outlier_channels", "offset1e3", "mixed"):
+        case = NR.k1k2_case(regime, 2, 16, 768, 256, BF16, pre_ln=True)
+        assert all(bool(torch.isfinite(case[k]).all()) for k in "WRS")
+        NR.check_bf16_chain("ref K1+K2", regime, case["S"], case["W"], case["S"], 1)
+    for std in (2.0, 6.0, 12.0):
+        for holes in (False, True):
+            case = NR.attention_case(std, 3, 32, 128, 4, BF16, holes, pre_ln=True)
+            assert all(bool(torch.isfinite(case[k]).all()) for k in "WRS")
+            NR.check_f32("ref attention", "peaked%g" % std, case["R"], case["W"], case["R"], 1)
+    case = NR.q2c_case(8, 9, 32, 256, F32, holes=True)
+    NR.check_f32("ref q2c", "near_duplicate", case["R"], case["W"], case["R"], 1)
+    assert bool((case["W"][:, -1] == case["W"][:, 0]).all())
+
+
+def test_reference_passes_the_pooling_ingest_and_convse_checks():
+    for std in (2.0, 6.0, 12.0):
+        for holes in (False, True):
+            for n, l, h, seed in ((33, 30, 256, 0), (40, 30, 256, 3), (80, 30, 768, 3)):
+                c = NR.pool_case(std, n, l, h, 2, BF16, holes, seed=seed)
+                NR.check_bf16_rounding("ref modular_pool", "peaked%g" % std, c["R"].to(BF16), c["W"], c["R"], 2,
+                                       strict=std == 2.0, cap=False)
+    c = NR.ingest_case(7, 32, 768)
+    NR.check_bf16_rounding("ref ingest_rows", "store_f16", c["R"].to(BF16), c["W"], c["R"], 2)
+    for n_mod, merged in ((2, True), (2, False), (1, False)):
+        c = NR.convse_case(12, 9, 48, 128, n_mod, merged, BF16, True)
+        assert float((c["W"][0].max(-1)[0] > 0.9).double().mean()) > 0.9            # the span softmax is peaked
+        assert bool((c["R"][0][~c["valid"]] == 0).all()) and bool(torch.isfinite(c["R"][0]).all())
+        NR.check_prob_rows("ref convse", "peaked", c["R"][0], c["W"][0], 1e-6)
+    c = NR.core_case(12.0, 3, 48, 256, 4, F32, True, True)
+    NR.check_prob_rows("ref attention_core P", "peaked12", c["Pr"], c["Pw"], 1e-5)
+    assert torch.equal(c["W"].view(3, 48, 4, 64)[..., :48].permute(0, 2, 1, 3), c["Pw"])    # V = identity: context == P
+    c = NR.cross_case(12.0, 4, 33, 20, 128, 4, BF16)
+    assert all(bool(torch.isfinite(c[k]).all()) for k in "WRS") and 0.2 < float(c["f64_rows"].float().mean()) < 0.8
+
+
+# ---- sensitivity: wrong stand-ins -------------------------------------------------------------------------------------
+def _truncate_bf16(x):
+    """f32 -> bf16 by dropping the low 16 bits (round toward zero) instead of rounding to nearest."""
+    return (x.contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+def test_truncated_bf16_store_is_rejected_by_the_bias_check_and_accepted_by_the_old_limits():
+    m, n, k = 300, 136, 96
+    x, w, b = rnd(m, k, seed=1), rnd(n, k, seed=2, scale=k ** -0.5), rnd(n, seed=3)
+    want = F.linear(x, w, b)
+    bad = _truncate_bf16(want)
+    close("linear (test_linear's bf16 limits)", bad, want, 2e-2, 1e-2)                 # the existing suite accepts it
+    scale = x.double().norm(dim=1, keepdim=True) * w.double().norm(dim=1)[None] + b.double().abs()[None]
+    W = f64.linear(x, w, b)
+    NR.check_bf16_rounding("linear", "gaussian", want.to(BF16), W, want, 2, scale)       # a correct store passes
+    with pytest.raises(AssertionError, match="not a correct rounding"):
+        NR.check_bf16_rounding("linear truncated", "gaussian", bad, W, want, 2, scale)
+    # the bias check alone catches it too (the maximum of a truncation error is one ulp: the boundary rule could hide it)
+    err = (bad.double() - W) * torch.sign(W) / NR.bf16_ulp(W)
+    assert float(err.mean()) < -0.4 and abs(float(err.mean())) > 50 * 4 * NR.BIAS_SIGMA / math.sqrt(err.numel())
+
+
+def _softmax_exp2_no_max(s):
+    """float32 softmax WITHOUT max subtraction, exp as exp2(x log2 e).  As accurate as the shifted form while nothing
+    overflows (the normalisation cancels the dominant term's relative error); what it lacks is range."""
+    e = torch.exp2(s * 1.4426950408889634)
+    return e / e.sum(-1, keepdim=True)
+
+
+def test_softmax_without_max_subtraction_overflows_at_spread_12_on_an_offset_and_is_rejected_as_non_finite():
+    g = torch.Generator().manual_seed(5)
+    v = rnd(64, 32, seed=9)
+
+    def pooled(spread, softmax):
+        s = shift + torch.randn(200, 64, generator=g) * spread
+        W = torch.softmax(s.double(), -1) @ v.double()
+        return softmax(s) @ v, torch.softmax(s, -1) @ v, W
+    shift = 0.0
+    bad, ref, W = pooled(1.0, _softmax_exp2_no_max)
+    close("attention on flat logits (test_attention_block's f32 limit)", bad, ref, 1e-4)
+    NR.check_f32("softmax", "flat", bad, W, ref, 8)
+    # at spread 12 around zero f32's exp does not overflow (max logit ~50 < 88) and the unshifted form is as accurate in
+    # absolute terms as the shifted one: what max subtraction buys is RANGE.  A common offset of 60 on the logits (softmax
+    # is shift invariant; the float64 value and the float32 reference do not move) overflows the unshifted form.
+    shift = 60.0
+    bad, ref, W = pooled(12.0, _softmax_exp2_no_max)
+    assert bool(torch.isfinite(ref).all()) and not bool(torch.isfinite(bad).all())
+    with pytest.raises(AssertionError, match="non-finite"):
+        NR.check_f32("softmax no max", "peaked12", bad, W, ref, 8)
+
+
+def _layernorm_one_pass(x, g, b):
+    mean = x.mean(-1, keepdim=True)
+    var = (x * x).mean(-1, keepdim=True) - mean * mean
+    return (x - mean) * torch.rsqrt(var.clamp_min(0) + 1e-5) * g + b
+
+
+def test_one_pass_variance_is_rejected_at_mean_1e3_and_accepted_at_zero_mean():
+    a, b = rnd(37, 200, seed=4), rnd(37, 200, seed=5)
+    g, beta = 1 + 0.1 * rnd(200, seed=6), 0.1 * rnd(200, seed=7)
+    want = F.layer_norm(a + b, (200,), g, beta, 1e-5)
+    close("add_layernorm (test_layernorm_l2norm_convert's f32 limit)", _layernorm_one_pass(a + b, g, beta), want, 1e-5)
+    case = NR.layernorm_case("offset1e3", 64, 768, F32)
+    bad = _layernorm_one_pass(case["a"] + case["b"], case["g"], case["beta"])
+    with pytest.raises(AssertionError, match="float32 reference"):
+        NR.check_f32("layernorm one pass", "offset1e3", bad, case["W"], case["R"], 8)

@@ -269,15 +269,17 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   }
   __syncthreads();
 
-  // order on the composite (score desc, payload asc).  The composites are distinct (the payload is part of them), so an
-  // entry's position is the number of entries above it: every thread ranks ITS entry against the <= 256 survivors (all lanes
-  // read the same LDS word: a broadcast) and stores it at its rank -- one pass without a barrier instead of the 36
-  // barrier-separated stages of a 256-wide bitonic network.  Slots beyond the survivors (k > row length) stay empty rows.
+  // order on the composite (score desc, payload asc).  An entry's position is the number of entries that sort before it:
+  // every thread ranks ITS entry against the <= 256 survivors (all lanes read the same LDS word: a broadcast) and stores it
+  // at its rank -- one pass without a barrier instead of the 36 barrier-separated stages of a 256-wide bitonic network.
+  // Composites need NOT be distinct: a caller's payloads may repeat (the (-inf, 2^31-1) filler of a sharded merge does), so
+  // equal composites are ordered by their LDS slot -- the ranks are a permutation of 0 .. n_comp-1 and every output slot is
+  // written exactly once.  Slots beyond the survivors (k > row length) stay empty rows.
   const uint32_t n_comp = min(s_cnt, 256u);
   const unsigned long long mine = comp[tid];
   uint32_t rank = 0;
 #pragma unroll 8
-  for (uint32_t j = 0; j < n_comp; ++j) rank += comp[j] > mine ? 1u : 0u;
+  for (uint32_t j = 0; j < n_comp; ++j) rank += (comp[j] > mine || (comp[j] == mine && j < (uint32_t)tid)) ? 1u : 0u;
   const uint32_t pos = (uint32_t)tid < n_comp ? rank : (uint32_t)tid;
   if (pos < (uint32_t)k && ((uint32_t)tid < n_comp || tid < k)) {
     const float s = key_to_float((uint32_t)(mine >> 32));
