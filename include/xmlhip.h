@@ -161,6 +161,16 @@ int xml_cross_attention(const void* main_x, const float* main_mask, const void* 
  * --------------------------------------------------------------------------------------------- */
 int xml_modular_pool(const void* enc, const float* mask, const float* w_m, void* out, int64_t n,
                      int lq, int hidden, int n_mod, int dt, xml_stream_t stream);
+/* K5 that also returns its softmax weights (get_modularized_queries(return_modular_att=True), xml/model_xml.py:420-423;
+ * XML.get_visualization_data, :253-289):
+ *   att (n, lq, n_mod) f32 = a[l, m] above: exactly 0 at masked positions (exp(-1e10 - max) is 0 in f32) and, in the varlen
+ *   form, at the positions l >= the sequence's own length of its padded (n, max_len, n_mod) row.
+ * `out` is bitwise what xml_modular_pool / xml_modular_pool_varlen write for the same input (the same kernels with one more
+ * store; same shape rules, same requirements). */
+int xml_modular_pool_att(const void* enc, const float* mask, const float* w_m, void* out, float* att, int64_t n, int lq,
+                         int hidden, int n_mod, int dt, xml_stream_t stream);
+int xml_modular_pool_att_varlen(const void* enc, const int32_t* cu_seqlens, const float* w_m, void* out, float* att,
+                                int64_t n, int max_len, int hidden, int n_mod, int dt, xml_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Plain linear y = x W^T + b  (video_query_linear / sub_query_linear, xml/model_xml.py:459-460,524)
@@ -396,6 +406,24 @@ int xml_convse_rerank_ex(const xml_convse_desc* d, const void* q_lin0, const voi
                          const float* c_inv1, const float* mask0, const float* mask1, const int32_t* pair_vid,
                          const float* conv_w, const float* pair_w, int min_l, int max_l, const int32_t* vid_len,
                          float* st_out, float* ed_out, float* summ_out, void* ws, size_t ws_bytes, xml_stream_t stream);
+
+/* Span evidence: what K7 computes on the way to its logits, for P explicit (query, video) pairs -- the per-clip arrays of
+ * XML.get_visualization_data (xml/model_xml.py:253-289; get_merged_st_ed_prob(return_similaity=True), :455-502).
+ *   pair_q, pair_vid (n_pairs) int32: pair p = query row pair_q[p] of q_lin x video row pair_vid[p] of feat2.  A pair with
+ *     either index out of range is skipped: its five output rows are zero-filled, nothing is read through it.
+ *   sim0_out, sim1_out (n_pairs, lpad) f32: q_lin_m[q] . feat2_m[v, l] per modality, UNMASKED (sim1_out: n_mod == 2 only)
+ *   sim_out  (n_pairs, lpad) f32: (sim0 + sim1) / 2, or sim0 when n_mod == 1 -- with desc.merged the very row the taps run over
+ *   st_out, ed_out (n_pairs, lpad) f32: the masked LOGITS (-1e10 at masked positions l < l_ref), bitwise those of
+ *     xml_convse_rerank / _f16s with desc.softmax = 0 on the same pairs: the same kernel body, instantiated with the extra
+ *     stores.  Every row holds zeros in its columns l >= l_ref.
+ * desc: nq = rows of q_lin, nv = videos of feat2; kpairs and softmax are ignored; dt selects f32 / bf16 / split-f16 operands
+ * (q_inv_m (nq), c_inv_m (nv * lpad) f32 are read for XML_F16S only).  Requirements as for xml_convse_rerank. */
+size_t xml_span_evidence_workspace_bytes(const xml_convse_desc* d, int64_t n_pairs);
+int xml_span_evidence(const xml_convse_desc* d, const void* q_lin0, const void* q_lin1, const float* q_inv0,
+                      const float* q_inv1, const void* feat2_0, const void* feat2_1, const float* c_inv0,
+                      const float* c_inv1, const float* mask0, const float* mask1, const int32_t* pair_q,
+                      const int32_t* pair_vid, int64_t n_pairs, const float* conv_w, float* sim0_out, float* sim1_out,
+                      float* sim_out, float* st_out, float* ed_out, void* ws, size_t ws_bytes, xml_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K9+K10: banded moment candidates + per-query top-n

@@ -7,7 +7,8 @@ the reference state_dict, the inputs and the reference's outputs for the hot-pat
   (1) encode_context incl. padded rows   (2) encode_query   (3) get_pred_from_raw_query cross=True/False
   (4) the driver tail (top-k videos, flat-sorted moments) through the reference's own
       compute_context_info / compute_query2ctx_info with a duck-typed in-memory dataset
-  (5) temporal NMS output   (6) one training step (losses, grads, BertAdam update) with recorded negatives.
+  (5) temporal NMS output   (6) one training step (losses, grads, BertAdam update) with recorded negatives
+  (7) get_visualization_data: modular attention weights and per-clip span evidence of a batch.
 """
 import argparse
 import json
@@ -481,12 +482,75 @@ def gen_ingest_case(ns, name, seed, n, dims, max_l, bsz):
     print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
+def gen_visualization_case(ns, name, cfg, seed, n, len_lo, len_hi, lq_lo, lq_hi):
+    """XML.get_visualization_data (xml/model_xml.py:253-289) on a batch of n (query, video) examples: the modular
+    attention weights and the per-clip evidence behind the span logits.  The reference returns a list of per-example dicts
+    of ragged arrays; stored zero-padded to the batch maxima, with the lengths.  (n >= 2: the method's .squeeze() calls
+    collapse a batch of one.)"""
+    rng = np.random.default_rng(seed)
+    torch.manual_seed(seed)
+    model = ns.model_xml.XML(EasyDict(cfg))
+    perturb_weights(model, seed + 1)
+    model.eval()
+    lens = rng.integers(len_lo, len_hi + 1, size=n)
+    lens[rng.integers(0, n)] = len_hi
+    qlens = rng.integers(lq_lo, lq_hi + 1, size=n)
+    qlens[rng.integers(0, n)] = lq_hi
+    vfeat, vmask = make_inputs(rng, n, lens, cfg["visual_input_size"])
+    sfeat, smask = make_inputs(rng, n, lens, cfg["sub_input_size"])
+    qfeat, qmask = make_inputs(rng, n, qlens, cfg["query_input_size"])
+    st = np.array([rng.integers(0, l) for l in lens])
+    ed = np.array([rng.integers(s, l) for s, l in zip(st, lens)])
+    st_ed = np.stack([st, ed], axis=1).astype(np.int64)
+    tv = torch.from_numpy
+    with torch.no_grad():
+        data = model.get_visualization_data(tv(qfeat), tv(qmask), tv(vfeat), tv(vmask), tv(sfeat), tv(smask), None, None,
+                                            tv(st_ed))
+        # the same rows before the method cuts them to each video's length: masked logits (-1e10) and similarities at the
+        # padded positions, which the 5 taps of a video's last clips read
+        _, vf2, _, sf2 = model.encode_context(tv(vfeat), tv(vmask), tv(sfeat), tv(smask))
+        enc_q = model.encode_input(tv(qfeat), tv(qmask), model.query_input_proj, model.query_encoder, model.query_pos_embed)
+        vq, sq, _ = model.get_modularized_queries(enc_q, tv(qmask), return_modular_att=True)
+        full = model.get_merged_st_ed_prob(vq, vf2, sq, sf2, tv(vmask), cross=False, return_similaity=True)
+    assert len(data) == n
+    out = dict(cfg=json.dumps(cfg), ctx_lens=lens, q_lens=qlens, video_feat=vfeat, video_mask=vmask, sub_feat=sfeat,
+               sub_mask=smask, query_feat=qfeat, query_mask=qmask, st_ed_indices=st_ed)
+    out.update(sd_arrays(model))
+    keys = ("modular_att_scores", "st_prob", "ed_prob", "similarity_scores", "video_similarity", "sub_similarity")
+    assert sorted(data[0].keys()) == sorted(keys + ("st_ed_indices",))
+    out["keys"] = json.dumps(sorted(data[0].keys()))
+    for k in keys:
+        lmax = int(qlens.max() if k == "modular_att_scores" else lens.max())
+        arr = np.zeros((n, lmax) + data[0][k].shape[1:], dtype=np.float32)
+        for i, d in enumerate(data):
+            assert len(d[k]) == (qlens[i] if k == "modular_att_scores" else lens[i])
+            arr[i, :len(d[k])] = d[k]
+        out["viz/" + k] = arr
+    for k, t in zip(("st_prob", "ed_prob", "similarity_scores", "video_similarity", "sub_similarity"), full):
+        out["full/" + k] = t.numpy().copy()
+        for i, d in enumerate(data):
+            assert np.array_equal(out["full/" + k][i, :lens[i]], d[k])
+    out["viz/st_ed_indices"] = np.stack([d["st_ed_indices"] for d in data]).astype(np.int64)
+    path = os.path.join(OUT_DIR, name + ".npz")
+    # np.savez_compressed's archive at deflate level 9 instead of 6: the weights of the full two-stream model are 2 MB of
+    # the fixture, and the last 4 % keep the file under 1 MiB, no larger than the other model-case fixtures
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for k, v in out.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(),
+                        compress_type=zipfile.ZIP_DEFLATED, compresslevel=9)
+    print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 def main():
     only = sys.argv.pop(1) if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else ""
     if only:      # regenerate a subset: python tools/make_golden.py train_step
         g = globals()
         for fn in ("gen_model_case", "gen_pipeline_case", "gen_external_vr_case", "gen_eval_case", "gen_train_case",
-                   "gen_ingest_case"):
+                   "gen_ingest_case", "gen_visualization_case"):
             orig = g[fn]
             g[fn] = (lambda o: lambda ns, name, *a, **k: o(ns, name, *a, **k) if only in name else None)(orig)
     ap = argparse.ArgumentParser()
@@ -533,6 +597,7 @@ def main():
     gen_train_case(ns, "train_step_staged_video_sub_h128",
                    model_cfg(max_ctx_l=24, lw_st_ed=0.0, visual_input_size=48, sub_input_size=32, query_input_size=32), 33,
                    bsz=6, len_lo=6, len_hi=24, lw_st_ed_schedule=[0.0, 0.0, 0.01, 0.01, 0.01])
+    gen_visualization_case(ns, "xml_visualization_h128", model_cfg(), 15, n=7, len_lo=9, len_hi=40, lq_lo=3, lq_hi=12)
 
 
 if __name__ == "__main__":

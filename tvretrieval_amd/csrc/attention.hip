@@ -763,10 +763,14 @@ extern "C" int xml_cross_attention(const void* main_x, const float* main_mask, c
 // ---------------------------------------------------------------------------------------------------
 // public: K5 modular pooling.  One workgroup per query.
 // ---------------------------------------------------------------------------------------------------
-template <typename T>
+// ATT (xml_modular_pool_att[_varlen], all three kernels): the softmax weights leave as well, att (n, lq, n_mod) f32 in the
+// PADDED layout -- the values the weighting loop multiplies with, 0 at padded positions; nothing else changes, so the pooled
+// vectors are bitwise those of the plain instantiation.
+template <typename T, bool ATT = false>
 __global__ __launch_bounds__(256) void modular_pool_kernel(const T* __restrict__ enc, const float* __restrict__ mask,
                                                            const float* __restrict__ wm, T* __restrict__ out,
-                                                           int64_t n, int lq, int hidden, int n_mod) {
+                                                           int64_t n, int lq, int hidden, int n_mod,
+                                                           float* __restrict__ att = nullptr) {
   __shared__ float s_att[2][128];
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const T* e = enc + (int64_t)q * lq * hidden;
@@ -794,6 +798,9 @@ __global__ __launch_bounds__(256) void modular_pool_kernel(const T* __restrict__
     for (int l = 0; l < lq; ++l) s_att[tid][l] /= sum;
   }
   __syncthreads();
+  if constexpr (ATT) {
+    for (int i = tid; i < lq * n_mod; i += 256) att[(int64_t)q * lq * n_mod + i] = s_att[i % n_mod][i / n_mod];
+  }
   for (int h = tid; h < hidden; h += 256) {
     for (int m = 0; m < n_mod; ++m) {
       float acc = 0.f;
@@ -806,16 +813,18 @@ __global__ __launch_bounds__(256) void modular_pool_kernel(const T* __restrict__
 // Short sequences (lq <= 32, hidden % 8 == 0, hidden <= 1024 -- the query encoder: 30 tokens): every token row is
 // read ONCE with 16-byte loads and stays in registers (a wave owns tokens wave, wave + 4, ...); scores go through
 // LDS for the softmax, each wave weights its own rows, the four partial sums meet in LDS.
-template <typename T>
+template <typename T, bool ATT = false>
 __global__ __launch_bounds__(256) void modular_pool_small_kernel(const T* __restrict__ enc, const float* __restrict__ mask,
                                                                  const float* __restrict__ wm, T* __restrict__ out,
                                                                  int64_t n, int lq, int hidden, int n_mod,
-                                                                 const int32_t* __restrict__ cu) {
+                                                                 const int32_t* __restrict__ cu,
+                                                                 float* __restrict__ att = nullptr) {
   // cu != NULL (xml_modular_pool_varlen): packed tokens, query q = rows cu[q] .. cu[q+1]-1, all valid (mask unused)
   __shared__ float s_att[2][32];
   __shared__ float s_part[4][2][1024];
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nvec = hidden >> 3;
+  const int lq_pad = lq;                // (ATT: row length of the padded attention output)
   int64_t row0 = (int64_t)q * lq;
   if (cu) {
     const int r0 = cu[q], r1 = cu[q + 1];
@@ -897,6 +906,9 @@ __global__ __launch_bounds__(256) void modular_pool_small_kernel(const T* __rest
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if (on) s_att[m][l] = ev / sum;
+    if constexpr (ATT) {
+      if (m < n_mod && l < lq_pad) att[((int64_t)q * lq_pad + l) * n_mod + m] = on ? ev / sum : 0.f;
+    }
   }
   __syncthreads();
   float a0[16], a1[16];
@@ -930,15 +942,17 @@ __global__ __launch_bounds__(256) void modular_pool_small_kernel(const T* __rest
 // h, h + 2, ...; lane v of a half holds 8 consecutive features of each of its tokens (16 tokens x 8 floats in registers).
 // The workgroup-per-query kernel above spends its time on a workgroup's launch, two barriers and an LDS reduction for 9 KB
 // of data, and at hidden = 256 half its lanes hold nothing: 126 us for the 10 895 queries of TVR val, this one ~25.
-template <typename T>
+template <typename T, bool ATT = false>
 __global__ __launch_bounds__(256) void modular_pool_wave_kernel(const T* __restrict__ enc, const float* __restrict__ mask,
                                                                 const float* __restrict__ wm, T* __restrict__ out,
                                                                 int64_t n, int lq, int hidden, int n_mod,
-                                                                const int32_t* __restrict__ cu) {
+                                                                const int32_t* __restrict__ cu,
+                                                                float* __restrict__ att = nullptr) {
   const int lane = threadIdx.x & 63, half = lane >> 5, v = lane & 31;
   const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= n) return;
   const int nvec = hidden >> 3;
+  const int lq_pad = lq;                // (ATT: row length of the padded attention output)
   int64_t row0 = q * lq;
   if (cu) {
     const int r0 = cu[q], r1 = cu[q + 1];
@@ -997,17 +1011,41 @@ __global__ __launch_bounds__(256) void modular_pool_wave_kernel(const T* __restr
     if (half == 0) st8<T>(out + q * hidden + v * 8, a0);
     else if (n_mod > 1) st8<T>(out + ((int64_t)n + q) * hidden + v * 8, a1);
   }
+  if constexpr (ATT) {
+    // The weights, in a pass of their own BEHIND the pooled store: inside the weighting loop the extra use of p0 / p1 changed
+    // which of its multiply-adds hipcc fuses (packed multiplies + adds became fmas), i.e. the pooled bits.  Every lane of a
+    // half holds the exponentials of tokens 2 i + half; the same IEEE division gives the factor the loop multiplied with.
+    // Lane i of the half stores token 2 i + half (s0 / s1 are 0 beyond the query's own tokens).
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int l = 2 * i + half;
+      if (v == i && l < lq_pad) {
+        float* ap = att + (q * lq_pad + l) * n_mod;
+        ap[0] = s0[i] / sum0;
+        if (n_mod > 1) ap[1] = s1[i] / sum1;
+      }
+    }
+  }
 }
 
 template <typename T>
 static void launch_modular_pool_small(const void* enc, const float* mask, const float* w_m, void* out, int64_t n, int lq,
-                                      int hidden, int n_mod, const int32_t* cu, hipStream_t st) {
+                                      int hidden, int n_mod, const int32_t* cu, hipStream_t st, float* att = nullptr) {
+  if (att) {
+    if (hidden <= 256)
+      hipLaunchKernelGGL((modular_pool_wave_kernel<T, true>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const T*)enc,
+                         mask, w_m, (T*)out, n, lq, hidden, n_mod, cu, att);
+    else
+      hipLaunchKernelGGL((modular_pool_small_kernel<T, true>), dim3((unsigned)n), dim3(256), 0, st, (const T*)enc, mask, w_m,
+                         (T*)out, n, lq, hidden, n_mod, cu, att);
+    return;
+  }
   if (hidden <= 256)
     hipLaunchKernelGGL(modular_pool_wave_kernel<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const T*)enc, mask, w_m,
-                       (T*)out, n, lq, hidden, n_mod, cu);
+                       (T*)out, n, lq, hidden, n_mod, cu, (float*)nullptr);
   else
     hipLaunchKernelGGL(modular_pool_small_kernel<T>, dim3((unsigned)n), dim3(256), 0, st, (const T*)enc, mask, w_m, (T*)out,
-                       n, lq, hidden, n_mod, cu);
+                       n, lq, hidden, n_mod, cu, (float*)nullptr);
 }
 
 extern "C" int xml_modular_pool(const void* enc, const float* mask, const float* w_m, void* out, int64_t n, int lq,
@@ -1025,10 +1063,10 @@ extern "C" int xml_modular_pool(const void* enc, const float* mask, const float*
   }
   if (dt == XML_F32)
     hipLaunchKernelGGL(modular_pool_kernel<float>, dim3((unsigned)n), dim3(256), 0, st, (const float*)enc, mask, w_m,
-                       (float*)out, n, lq, hidden, n_mod);
+                       (float*)out, n, lq, hidden, n_mod, (float*)nullptr);
   else if (dt == XML_BF16)
     hipLaunchKernelGGL(modular_pool_kernel<bf16_t>, dim3((unsigned)n), dim3(256), 0, st, (const bf16_t*)enc, mask,
-                       w_m, (bf16_t*)out, n, lq, hidden, n_mod);
+                       w_m, (bf16_t*)out, n, lq, hidden, n_mod, (float*)nullptr);
   else
     return XML_ERR_BAD_ARG;
   XML_CHECK_LAUNCH();
@@ -1045,6 +1083,48 @@ extern "C" int xml_modular_pool_varlen(const void* enc, const int32_t* cu_seqlen
   hipStream_t st = (hipStream_t)stream;
   if (dt == XML_F32) launch_modular_pool_small<float>(enc, nullptr, w_m, out, n, max_len, hidden, n_mod, cu_seqlens, st);
   else if (dt == XML_BF16) launch_modular_pool_small<bf16_t>(enc, nullptr, w_m, out, n, max_len, hidden, n_mod, cu_seqlens, st);
+  else return XML_ERR_BAD_ARG;
+  XML_CHECK_LAUNCH();
+  return XML_OK;
+}
+
+// K5 + its softmax weights (XML.get_modularized_queries(return_modular_att=True), xml/model_xml.py:410-423): the ATT
+// instantiations of the three kernels above, chosen by the same shape rules as xml_modular_pool / _varlen.
+extern "C" int xml_modular_pool_att(const void* enc, const float* mask, const float* w_m, void* out, float* att, int64_t n,
+                                    int lq, int hidden, int n_mod, int dt, xml_stream_t stream) {
+  XML_ENTER();
+  if (!enc || !mask || !w_m || !out || !att || n <= 0 || lq <= 0 || hidden <= 0) return XML_ERR_BAD_ARG;
+  if (n_mod < 1 || n_mod > 2 || lq > 128) return XML_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (lq <= 32 && hidden % 8 == 0 && hidden <= 1024) {
+    if (dt == XML_F32) launch_modular_pool_small<float>(enc, mask, w_m, out, n, lq, hidden, n_mod, nullptr, st, att);
+    else if (dt == XML_BF16) launch_modular_pool_small<bf16_t>(enc, mask, w_m, out, n, lq, hidden, n_mod, nullptr, st, att);
+    else return XML_ERR_BAD_ARG;
+    XML_CHECK_LAUNCH();
+    return XML_OK;
+  }
+  if (dt == XML_F32)
+    hipLaunchKernelGGL((modular_pool_kernel<float, true>), dim3((unsigned)n), dim3(256), 0, st, (const float*)enc, mask, w_m,
+                       (float*)out, n, lq, hidden, n_mod, att);
+  else if (dt == XML_BF16)
+    hipLaunchKernelGGL((modular_pool_kernel<bf16_t, true>), dim3((unsigned)n), dim3(256), 0, st, (const bf16_t*)enc, mask,
+                       w_m, (bf16_t*)out, n, lq, hidden, n_mod, att);
+  else
+    return XML_ERR_BAD_ARG;
+  XML_CHECK_LAUNCH();
+  return XML_OK;
+}
+
+extern "C" int xml_modular_pool_att_varlen(const void* enc, const int32_t* cu_seqlens, const float* w_m, void* out,
+                                           float* att, int64_t n, int max_len, int hidden, int n_mod, int dt,
+                                           xml_stream_t stream) {
+  XML_ENTER();
+  if (!enc || !cu_seqlens || !w_m || !out || !att || n <= 0 || max_len <= 0 || hidden <= 0) return XML_ERR_BAD_ARG;
+  if (n_mod < 1 || n_mod > 2 || max_len > 32 || hidden % 8 || hidden > 1024) return XML_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (dt == XML_F32) launch_modular_pool_small<float>(enc, nullptr, w_m, out, n, max_len, hidden, n_mod, cu_seqlens, st, att);
+  else if (dt == XML_BF16)
+    launch_modular_pool_small<bf16_t>(enc, nullptr, w_m, out, n, max_len, hidden, n_mod, cu_seqlens, st, att);
   else return XML_ERR_BAD_ARG;
   XML_CHECK_LAUNCH();
   return XML_OK;

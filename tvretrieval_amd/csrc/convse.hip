@@ -250,11 +250,20 @@ struct ConvseArgs {
   // end there) and entries l >= vid_len[v] of st_out / ed_out -- exactly 0 after the masked softmax -- are NOT WRITTEN: the
   // consumer (xml_moment_topk_ex with the same vid_len) does not read them.  TVR: 51 of 128 clip rows on average.
   const int32_t* vid_len;
+  // span evidence (xml_span_evidence, the EV instantiations): the pairs are explicit -- pair p is query row pair_q[p] -- and
+  // the similarities leave next to the logits: ev_sim[m] (P, lpad) = q_lin_m . feat2_m[v, l], unmasked; ev_merged (P, lpad) =
+  // the row the taps run over when the streams are merged, ((sim_0 + sim_1) / 2 or the single stream's row) otherwise
+  const int32_t* pair_q;
+  float* ev_sim[2];
+  float* ev_merged;
 };
 
 // 3 waves per SIMD (<= 168 VGPRs) for the f32 / bf16 instantiations.  The split-f16 one holds both halves of every fragment:
 // at 3 waves it spills 24 VGPRs, at 2 (191 VGPRs, no scratch) it is 1.6 % faster (4.54 vs 4.62 ms, same box).
-template <typename T>
+// EV (xml_span_evidence): the same body -- the same accumulation order, patch and epilogue, hence the same logits bit for
+// bit -- that also stores every similarity row it forms.  Merged streams share one accumulator, so the second stream's own
+// row comes from one extra product in front of the loop; the accumulators of the loop itself are untouched by it.
+template <typename T, bool EV = false>
 __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kernel(ConvseArgs a) {
   using Cfg = GemmCfg<T, TM, 128, 1, 4>;
   // dynamic LDS: [ GEMM staging | similarity patches ].  With ONE similarity patch (merged streams or a single
@@ -274,12 +283,16 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
   const int b_rows = a.vid_len ? max(1, min(a.lpad, vlen + (a.ksize >> 1))) : a.lpad;   // clip rows the GEMM needs
   constexpr bool SPLIT = IsSplit16<T>::value;
   __shared__ float s_qinv[SPLIT ? 2 : 1][SPLIT ? TM : 1];
+  auto q_of = [&](int p) -> int {                  // query row of pair p
+    if constexpr (EV) return a.pair_q[p];
+    else return p / a.kpairs;
+  };
   if (tid < TM) {
     const int p = tid < cnt ? a.bucket[first + tid] : -1;
     s_pair[tid] = p;
     if constexpr (SPLIT) {
 #pragma unroll
-      for (int m = 0; m < 2; ++m) s_qinv[m][tid] = (p >= 0 && m < a.n_mod) ? a.q_inv[m][p / a.kpairs] : 1.f;
+      for (int m = 0; m < 2; ++m) s_qinv[m][tid] = (p >= 0 && m < a.n_mod) ? a.q_inv[m][q_of(p)] : 1.f;
     }
   }
   __syncthreads();
@@ -289,7 +302,13 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
   const int n_sim = a.merged ? 1 : a.n_mod;
   const int mt_used = (cnt + 15) >> 4;             // a video has ~46 pairs at the TVR shape: 3 of the 4 row tiles
   f32x4 acc[Cfg::MT][Cfg::NT];
-  for (int m = 0; m < a.n_mod; ++m) {
+  auto ev_store = [&](float* dst, int mt, int nt, int r, float x) {      // accumulator element -> its pair's output row
+    const int row = mt * 16 + fg * 4 + r, col = wn * 32 + nt * 16 + fr;
+    if (row < cnt && col < a.lpad) dst[(int64_t)s_pair[row] * a.lpad + col] = col < a.l_ref ? x : 0.f;
+  };
+  for (int pass = (EV && a.merged) ? -1 : 0; pass < a.n_mod; ++pass) {
+    const bool pre = EV && pass < 0;               // EV, merged: the second stream's own similarity, ahead of the loop
+    const int m = pre ? 1 : pass;
     float cinv[Cfg::NT];                           // SPLIT: 1 / S of this lane's clip columns, this modality
 #pragma unroll
     for (int nt = 0; nt < Cfg::NT; ++nt) {
@@ -300,7 +319,7 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
     const T* f2 = reinterpret_cast<const T*>(a.feat2[m]);
     auto a_row = [&](int r) -> const char* {
       const int p = s_pair[r];
-      return p >= 0 ? reinterpret_cast<const char*>(ql + (int64_t)(p / a.kpairs) * a.hidden) : nullptr;
+      return p >= 0 ? reinterpret_cast<const char*>(ql + (int64_t)q_of(p) * a.hidden) : nullptr;
     };
     auto b_row = [&](int r) -> const char* {
       return r < b_rows ? reinterpret_cast<const char*>(f2 + ((int64_t)v * a.lpad + r) * a.hidden) : nullptr;
@@ -308,7 +327,7 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
     const int k_bytes = a.hidden * (int)sizeof(T);
     auto a_off = [&](int r) -> uint32_t {             // rows beyond the chunk: any valid row (their products are never read)
       const int p = s_pair[r] >= 0 ? s_pair[r] : s_pair[0];
-      return (uint32_t)(p / a.kpairs) * (uint32_t)k_bytes;
+      return (uint32_t)q_of(p) * (uint32_t)k_bytes;
     };
     // (rows the taps of a valid clip cannot reach re-read the last needed row: an L1 / L2 hit instead of an HBM fetch)
     auto b_off = [&](int r) -> uint32_t { return (uint32_t)min(r, b_rows - 1) * (uint32_t)k_bytes; };
@@ -323,14 +342,32 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
       // than the register-staged loop in bf16 -- the epilogue of one workgroup needs the GEMM phases of two others to
       // hide behind --, two stages 1 % / 7 % faster in bf16 / f32: tools/bench_k7.py, ablations 40 / 41.)
       if (m > 0) __syncthreads();                     // the previous modality's last step is still being read
-      if (a.merged && m > 0)
+      if (a.merged && m > 0 && !pre)
         gemm_mainloop_dma<T, Cfg, false, 2>(acc, reinterpret_cast<const char*>(ql), a_off, b_base, b_off, k_bytes, smem, mt_used);
       else
         gemm_mainloop_dma<T, Cfg, true, 2>(acc, reinterpret_cast<const char*>(ql), a_off, b_base, b_off, k_bytes, smem, mt_used);
-    } else if (a.merged && m > 0)
+    } else if (a.merged && m > 0 && !pre)
       gemm_mainloop<T, Cfg, false>(acc, a_row, b_row, a.hidden * (int)sizeof(T), smem, mt_used);
     else
       gemm_mainloop<T, Cfg, true>(acc, a_row, b_row, a.hidden * (int)sizeof(T), smem, mt_used);
+    if constexpr (EV) {
+      if (a.merged && (pre || m == 0)) {           // one stream's products alone are in the accumulators
+#pragma unroll
+        for (int mt = 0; mt < Cfg::MT; ++mt)
+#pragma unroll
+          for (int nt = 0; nt < Cfg::NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float x = acc[mt][nt][r];
+              if constexpr (SPLIT) x *= s_qinv[m][mt * 16 + fg * 4 + r] * cinv[nt];
+              ev_store(a.ev_sim[m], mt, nt, r, x);
+            }
+      }
+      if (pre) {
+        __syncthreads();                           // the loop's first product stages over what this one still reads
+        continue;
+      }
+    }
     if constexpr (SPLIT) {
       if (a.merged && m + 1 < a.n_mod) {
         // the next modality accumulates on top: move the accumulators into ITS units (exact: ratios of powers of two)
@@ -362,6 +399,17 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
             float x = acc[mt][nt][r] * scale;
             if constexpr (SPLIT) x *= s_qinv[m][mt * 16 + fg * 4 + r] * cinv[nt];
             sim[si][mt * 16 + fg * 4 + r][LH + wn * 32 + nt * 16 + fr] = x;
+            if constexpr (EV) {
+              if (a.merged) {
+                ev_store(a.ev_merged, mt, nt, r, x);
+              } else {
+                ev_store(a.ev_sim[m], mt, nt, r, x);
+                // (stream 0's value of this element is this lane's own write of the previous pass)
+                if (m == a.n_mod - 1)
+                  ev_store(a.ev_merged, mt, nt, r,
+                           m ? (sim[0][mt * 16 + fg * 4 + r][LH + wn * 32 + nt * 16 + fr] + x) * 0.5f : x);
+              }
+            }
           }
     }
   }
@@ -647,11 +695,18 @@ struct ConvseSumm {          // optional candidate summaries / ragged-corpus len
   int min_l, max_l;
   const int32_t* vid_len;
 };
+struct ConvseEv {            // explicit pairs + similarity outputs (xml_span_evidence); pair_q == NULL: plain K7
+  const int32_t* pair_q;
+  int64_t n_pairs;
+  float* sim[2];
+  float* merged;
+};
 static int convse_rerank_impl(const xml_convse_desc* d, const void* q_lin0, const void* q_lin1, const void* feat2_0,
                               const void* feat2_1, const float* mask0, const float* mask1, const int32_t* pair_vid,
                               const float* conv_w, float* st_out, float* ed_out, void* ws, size_t ws_bytes,
                               const float* q_inv0, const float* q_inv1, const float* c_inv0, const float* c_inv1,
-                              xml_stream_t stream, ConvseSumm sm = ConvseSumm{nullptr, nullptr, 0, 0, nullptr});
+                              xml_stream_t stream, ConvseSumm sm = ConvseSumm{nullptr, nullptr, 0, 0, nullptr},
+                              ConvseEv ev = ConvseEv{nullptr, 0, {nullptr, nullptr}, nullptr});
 
 // xml_convse_rerank / xml_convse_rerank_f16s (by desc.dt) + the candidate summaries K9 starts from
 extern "C" int xml_convse_rerank_ex(const xml_convse_desc* d, const void* q_lin0, const void* q_lin1, const float* q_inv0,
@@ -723,12 +778,16 @@ static int convse_rerank_impl(const xml_convse_desc* d, const void* q_lin0, cons
                               const void* feat2_1, const float* mask0, const float* mask1, const int32_t* pair_vid,
                               const float* conv_w, float* st_out, float* ed_out, void* ws, size_t ws_bytes,
                               const float* q_inv0, const float* q_inv1, const float* c_inv0, const float* c_inv1,
-                              xml_stream_t stream, ConvseSumm sm) {
-  if (ws_bytes < xml_convse_rerank_workspace_bytes(d)) return XML_ERR_WORKSPACE;
+                              xml_stream_t stream, ConvseSumm sm, ConvseEv ev) {
+  // the pair list as the inversion sees it: (nq, kpairs) of K7, or the P explicit pairs of xml_span_evidence (which has
+  // checked its own workspace)
+  xml_convse_desc dl = *d;
+  if (ev.pair_q) { dl.nq = (int)ev.n_pairs; dl.kpairs = 1; }
+  if (!ev.pair_q && ws_bytes < xml_convse_rerank_workspace_bytes(d)) return XML_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   ConvseWs w;
-  convse_ws_layout(d, &w, (char*)ws);
-  const int64_t P = (int64_t)d->nq * d->kpairs;
+  convse_ws_layout(&dl, &w, (char*)ws);
+  const int64_t P = (int64_t)dl.nq * dl.kpairs;
   int sub = 1;
   if (P <= CONVSE_SMALL_P && d->nv <= CONVSE_SMALL_NV) {
     hipLaunchKernelGGL(convse_invert_small_kernel, dim3(1), dim3(1024), 0, st, pair_vid, w.offsets, w.chunk_off, w.chunk_vid,
@@ -764,7 +823,8 @@ static int convse_rerank_impl(const xml_convse_desc* d, const void* q_lin0, cons
   a.mask[0] = mask0; a.mask[1] = mask1 ? mask1 : mask0;
   a.conv_w = conv_w; a.st_out = st_out; a.ed_out = ed_out;
   a.offsets = w.offsets; a.chunk_off = w.chunk_off; a.bucket = w.bucket; a.chunk_vid = w.chunk_vid;
-  a.nv = d->nv; a.kpairs = d->kpairs; a.lpad = d->lpad; a.l_ref = d->l_ref; a.hidden = d->hidden;
+  a.pair_q = ev.pair_q; a.ev_sim[0] = ev.sim[0]; a.ev_sim[1] = ev.sim[1]; a.ev_merged = ev.merged;
+  a.nv = d->nv; a.kpairs = dl.kpairs; a.lpad = d->lpad; a.l_ref = d->l_ref; a.hidden = d->hidden;
   a.n_mod = d->n_mod; a.merged = d->merged; a.ksize = d->ksize; a.softmax = d->softmax & 1;
   a.dbg = g_q2c_ablation;       // constant 0 in the product build (debug.h)
   a.pair_w = sm.pair_w; a.summ = sm.summ; a.min_l = sm.min_l; a.max_l = sm.max_l; a.vid_len = sm.vid_len;
@@ -783,23 +843,110 @@ static int convse_rerank_impl(const xml_convse_desc* d, const void* q_lin0, cons
     using Cfg = GemmCfg<f16s_t, TM, 128, 1, 4>;
     constexpr size_t stg = Cfg::LDS_BYTES;
     const size_t lds = n_sim == 1 ? (stg > patch ? stg : patch) : stg + 2 * patch;
-    if (!xml_lds_attr_once<convse_kernel<f16s_t>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
-    hipLaunchKernelGGL(convse_kernel<f16s_t>, dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    if (ev.pair_q) {
+      if (!xml_lds_attr_once<convse_kernel<f16s_t, true>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
+      hipLaunchKernelGGL((convse_kernel<f16s_t, true>), dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    } else {
+      if (!xml_lds_attr_once<convse_kernel<f16s_t>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
+      hipLaunchKernelGGL(convse_kernel<f16s_t>, dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    }
   } else if (d->dt == XML_F32) {
     using Cfg = GemmCfg<float, TM, 128, 1, 4>;
     constexpr size_t stg = Cfg::LDS_BYTES;           // = GemmDma<Cfg, 2>::LDS_BYTES: both mainloops stage two steps
     const size_t lds = n_sim == 1 ? (stg > patch ? stg : patch) : stg + 2 * patch;
-    if (!xml_lds_attr_once<convse_kernel<float>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
-    hipLaunchKernelGGL(convse_kernel<float>, dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    if (ev.pair_q) {
+      if (!xml_lds_attr_once<convse_kernel<float, true>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
+      hipLaunchKernelGGL((convse_kernel<float, true>), dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    } else {
+      if (!xml_lds_attr_once<convse_kernel<float>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
+      hipLaunchKernelGGL(convse_kernel<float>, dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    }
   } else {
     using Cfg = GemmCfg<bf16_t, TM, 128, 1, 4>;
     constexpr size_t stg = Cfg::LDS_BYTES;           // = GemmDma<Cfg, 2>::LDS_BYTES: both mainloops stage two steps
     const size_t lds = n_sim == 1 ? (stg > patch ? stg : patch) : stg + 2 * patch;
-    if (!xml_lds_attr_once<convse_kernel<bf16_t>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
-    hipLaunchKernelGGL(convse_kernel<bf16_t>, dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    if (ev.pair_q) {
+      if (!xml_lds_attr_once<convse_kernel<bf16_t, true>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
+      hipLaunchKernelGGL((convse_kernel<bf16_t, true>), dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    } else {
+      if (!xml_lds_attr_once<convse_kernel<bf16_t>>((int)(stg + 2 * patch))) return XML_ERR_LAUNCH;
+      hipLaunchKernelGGL(convse_kernel<bf16_t>, dim3((unsigned)max_chunks), dim3(256), lds, st, a);
+    }
   }
   XML_CHECK_LAUNCH();
   return XML_OK;
+}
+
+// ---- span evidence (xml_span_evidence) ------------------------------------------------------------------------------
+// K7's EV instantiation over P explicit (query row, video row) pairs.  The pair list is taken from device memory, so it is
+// sanitised on the device first: a pair whose query or video row is out of range becomes a skipped pair (video -1) -- its
+// five output rows are zero-filled and nothing is read through it.
+__global__ void evidence_pairs_kernel(const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_vid,
+                                      int32_t* __restrict__ vid_ok, int64_t P, int nq, int nv) {
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  const int q = pair_q[p], v = pair_vid[p];
+  vid_ok[p] = (q >= 0 && q < nq && v >= 0 && v < nv) ? v : -1;
+}
+
+static size_t evidence_ws_layout(const xml_convse_desc* d, int64_t n_pairs, size_t* vid_off) {
+  xml_convse_desc dl = *d;
+  dl.nq = (int)n_pairs; dl.kpairs = 1;
+  const size_t base = convse_ws_layout(&dl, nullptr, nullptr);
+  if (vid_off) *vid_off = base;
+  return base + align_up((size_t)n_pairs * 4, 256);
+}
+
+extern "C" size_t xml_span_evidence_workspace_bytes(const xml_convse_desc* d, int64_t n_pairs) {
+  if (!d || n_pairs <= 0 || n_pairs > INT32_MAX) return 0;
+  return evidence_ws_layout(d, n_pairs, nullptr);
+}
+
+extern "C" int xml_span_evidence(const xml_convse_desc* d, const void* q_lin0, const void* q_lin1, const float* q_inv0,
+                                 const float* q_inv1, const void* feat2_0, const void* feat2_1, const float* c_inv0,
+                                 const float* c_inv1, const float* mask0, const float* mask1, const int32_t* pair_q,
+                                 const int32_t* pair_vid, int64_t n_pairs, const float* conv_w, float* sim0_out,
+                                 float* sim1_out, float* sim_out, float* st_out, float* ed_out, void* ws, size_t ws_bytes,
+                                 xml_stream_t stream) {
+  XML_ENTER();
+  if (!d || !q_lin0 || !feat2_0 || !mask0 || !pair_q || !pair_vid || !conv_w || !sim0_out || !sim_out || !st_out ||
+      !ed_out || !ws)
+    return XML_ERR_BAD_ARG;
+  if (d->nq <= 0 || d->nv <= 0 || n_pairs <= 0 || n_pairs > INT32_MAX || d->hidden <= 0) return XML_ERR_BAD_ARG;
+  if (d->n_mod < 1 || d->n_mod > 2 || (d->n_mod == 2 && (!q_lin1 || !feat2_1 || !sim1_out))) return XML_ERR_BAD_ARG;
+  if (d->n_mod == 2 && !d->merged && !mask1) return XML_ERR_BAD_ARG;
+  if (d->merged && d->n_mod != 2) return XML_ERR_BAD_ARG;
+  if (d->lpad % 16 || d->lpad > 128 || d->l_ref > d->lpad || d->l_ref <= 0 || d->hidden % 8) return XML_ERR_UNSUPPORTED;
+  if (!(d->ksize & 1) || d->ksize > 15 || d->ksize < 1) return XML_ERR_UNSUPPORTED;
+  const bool split = d->dt == XML_F16S;
+  if (split) {
+    if (!q_inv0 || !c_inv0 || (d->n_mod == 2 && (!q_inv1 || !c_inv1))) return XML_ERR_BAD_ARG;
+    if (d->hidden % 32) return XML_ERR_UNSUPPORTED;
+  } else if (d->dt != XML_F32 && d->dt != XML_BF16) {
+    return XML_ERR_BAD_ARG;
+  }
+  size_t vid_off = 0;
+  if (ws_bytes < evidence_ws_layout(d, n_pairs, &vid_off)) return XML_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* vid_ok = (int32_t*)((char*)ws + vid_off);
+  hipLaunchKernelGGL(evidence_pairs_kernel, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pair_q, pair_vid, vid_ok, n_pairs,
+                     d->nq, d->nv);
+  XML_CHECK_LAUNCH();
+  // similarity rows of skipped pairs (the inversion zero-fills their st / ed rows)
+  hipLaunchKernelGGL(convse_zero_skipped_kernel, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, vid_ok, sim0_out, sim_out,
+                     n_pairs, d->nv, d->lpad / 4);
+  XML_CHECK_LAUNCH();
+  if (d->n_mod == 2) {
+    hipLaunchKernelGGL(convse_zero_skipped_kernel, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, vid_ok, sim1_out, sim1_out,
+                       n_pairs, d->nv, d->lpad / 4);
+    XML_CHECK_LAUNCH();
+  }
+  xml_convse_desc dd = *d;
+  dd.softmax = 0;                                     // masked logits, skipped rows zero-filled
+  return convse_rerank_impl(&dd, q_lin0, q_lin1, feat2_0, feat2_1, mask0, mask1, vid_ok, conv_w, st_out, ed_out, ws, ws_bytes,
+                            split ? q_inv0 : nullptr, split ? q_inv1 : nullptr, split ? c_inv0 : nullptr,
+                            split ? c_inv1 : nullptr, stream, ConvseSumm{nullptr, nullptr, 0, 0, nullptr},
+                            ConvseEv{pair_q, n_pairs, {sim0_out, d->n_mod == 2 ? sim1_out : nullptr}, sim_out});
 }
 
 extern "C" size_t xml_q2c_rescore_workspace_bytes(int nq, int nv, int kpairs) {

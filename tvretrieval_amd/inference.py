@@ -757,6 +757,91 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     return out
 
 
+def _as_pairs(t, name, device):
+    t = torch.as_tensor(t)
+    if t.dim() != 1 or (t.numel() and t.dtype.is_floating_point):
+        raise ValueError("explain_moments: %s must be a 1-D integer array" % name)
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def explain_moments(model, index, query_feat, query_mask, pair_q, pair_vid, ops=hip_ops, with_q2c=True, to_host=False):
+    """Why did video v rank / localise where it did for query q: the arrays of the reference's XML.get_visualization_data
+    (xml/model_xml.py:253-289) for P listed (query, video) pairs against the RESIDENT index -- the corpus is not re-encoded.
+
+      pair_q (P,)   row of query_feat; pair_vid (P,) index-LOCAL video row (a record's video_idx - index.video_offset)
+
+    The queries are encoded once (packed when encode_query would pack them) with K5 keeping its softmax weights, the query
+    linears are applied, and K7's evidence variant reads index.feat2 / index.mask in place (bf16, f32 or split-f16 rows).
+    Returns a dict of device tensors (to_host=True: numpy arrays):
+      modular_att (Nq, Lq, n_mod)  pooling weight of every query token per stream, 0 at padded tokens
+      video_similarity, sub_similarity, similarity (P, l_ref)  per-clip q' . feat2 of each stream (unmasked; the stream a
+                    model does not have is None) and their mean -- what the span filters run over in a merged model
+      st_logits, ed_logits (P, l_ref)  masked logits, bitwise K7's (ops.convse_rerank(softmax=False)): -1e10 at masked clips
+      ctx_len (P,)  valid clips of the pair's video (1 + its last unmasked clip); columns beyond it hold what K7 holds there
+      q2c (P,)      video-level score of the pair: its entry of stage_q2c's matrix, or the re-scored f32-grade value on an
+                    exact-rank index (with_q2c=False: None -- on a plain index the score costs a K6 pass over the corpus)
+    Corpus shards (tvretrieval_amd.dist) are not handled: every pair_vid must lie in [0, index.n_videos)."""
+    if not hasattr(ops, "span_evidence"):
+        raise NotImplementedError("explain_moments needs a backend with span_evidence (the HIP ops)")
+    mods = index.modalities
+    dev = index.device
+    pq, pv = _as_pairs(pair_q, "pair_q", dev), _as_pairs(pair_vid, "pair_vid", dev)
+    if pq.shape != pv.shape:
+        raise ValueError("explain_moments: pair_q and pair_vid differ in length (%d, %d)" % (pq.numel(), pv.numel()))
+    nq, n_pairs = int(query_feat.shape[0]), int(pq.numel())
+    if n_pairs:
+        lo_v, hi_v, lo_q, hi_q = (int(x) for x in torch.stack([pv.min(), pv.max(), pq.min(), pq.max()]).tolist())
+        if lo_v < 0 or hi_v >= index.n_videos:
+            raise ValueError("explain_moments: pair_vid must be index-local rows in [0, %d) (a record's video_idx minus "
+                             "index.video_offset = %d); got values in [%d, %d]"
+                             % (index.n_videos, index.video_offset, lo_v, hi_v))
+        if lo_q < 0 or hi_q >= nq:
+            raise ValueError("explain_moments: pair_q must be rows of query_feat in [0, %d); got values in [%d, %d]"
+                             % (nq, lo_q, hi_q))
+    l_ref, lq, n_mod = index.l_ref, int(query_feat.shape[1]), len(mods)
+    finish = lambda d: {k: (v.cpu().numpy() if (to_host and v is not None) else v) for k, v in d.items()}   # noqa: E731
+    if nq:            # (an out-of-range check above: no queries means no pairs)
+        with torch.no_grad():
+            vq, sq, att = model.encode_query(query_feat, query_mask, return_modular_att=True)
+        qvec = {m: q for m, q in (("video", vq), ("sub", sq)) if m in mods}
+    else:
+        att = torch.zeros((0, lq, n_mod), dtype=torch.float32, device=dev)
+    if n_pairs == 0:
+        rows = lambda m: torch.zeros((0, l_ref), dtype=torch.float32, device=dev) if m in mods else None   # noqa: E731
+        return finish(dict(modular_att=att, video_similarity=rows("video"), sub_similarity=rows("sub"),
+                           similarity=rows(mods[0]), st_logits=rows(mods[0]), ed_logits=rows(mods[0]),
+                           ctx_len=torch.zeros((0,), dtype=torch.int32, device=dev),
+                           q2c=torch.zeros((0,), dtype=torch.float32, device=dev) if with_q2c else None))
+    with torch.no_grad():
+        q_lin = query_linears(model, index, qvec)
+        split = getattr(index.feat2[mods[0]], "dtype", None) is getattr(ops, "F16S", object())
+        if split:
+            q_lin = [ops.split_f16_rows(q.float().contiguous()) for q in q_lin]      # per-row scales, as stage_span_probs
+        merged = bool(model.config.merge_two_stream and n_mod == 2)
+        ev = ops.span_evidence(q_lin, [index.feat2[m] for m in mods], [index.mask[m] for m in mods], pq, pv,
+                               model._conv_weights(), l_ref, merged, model.config.conv_kernel_size)
+        per_stream = dict(zip(mods, (ev.video_similarity, ev.sub_similarity)))     # (operand order = index.modalities)
+        cut = lambda t: None if t is None else t[:, :l_ref]          # noqa: E731
+        ar = torch.arange(1, index.lpad + 1, device=dev, dtype=torch.int32)
+        ctx_len = None
+        for m in mods:
+            last = ((index.mask[m].index_select(0, pv.long()) != 0).to(torch.int32) * ar).amax(1)
+            ctx_len = last if ctx_len is None else torch.maximum(ctx_len, last)
+        q2c = None
+        if with_q2c and index.exact is not None:
+            pv1 = pv.reshape(-1, 1).contiguous()
+            qn = [ops.l2norm_rows(qvec[m].float().contiguous()).index_select(0, pq.long()).contiguous() for m in mods]
+            if index.exact.mode == "f16s":
+                qn = [ops.split_f16_rows(q, ops.F16_UNIT_LOG2) for q in qn]
+            q2c = ops.q2c_rescore(qn, [index.exact.feat1n_f32[m] for m in mods], [index.mask[m] for m in mods], pv1)[:, 0]
+        elif with_q2c:
+            q2c = stage_q2c(index, qvec, ops)[pq.long(), pv.long()]
+    out = dict(modular_att=att, video_similarity=cut(per_stream.get("video")), sub_similarity=cut(per_stream.get("sub")),
+               similarity=cut(ev.similarity), st_logits=cut(ev.st_logits), ed_logits=cut(ev.ed_logits),
+               ctx_len=ctx_len.clamp_max(l_ref), q2c=q2c)
+    return finish(out)
+
+
 _HOST_STREAMS = {}
 
 

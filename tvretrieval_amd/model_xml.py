@@ -431,29 +431,40 @@ class XML(nn.Module):
 
     def get_modularized_queries(self, encoded_query, query_mask, return_modular_att=False):
         """xml/model_xml.py:399-423."""
-        if return_modular_att:
-            raise NotImplementedError("visualisation outputs are out of scope")
         wm = _f(self.modular_vector_mapping.weight)
+        if return_modular_att:
+            # (N, D), (N, D), (N, Lq, 2): the softmax weights K5 pools with (xml/model_xml.py:416-418)
+            if wm.shape[0] != 2:
+                raise ValueError("return_modular_att needs both modalities (modular_queries.shape[1] == 2); this model's "
+                                 "ctx_mode is %r" % (self.config.ctx_mode,))
+            out, att = ops.modular_pool(encoded_query.contiguous(), query_mask.float().contiguous(), wm, return_att=True)
+            return out[0], out[1], att
         out = ops.modular_pool(encoded_query.contiguous(), query_mask.float().contiguous(), wm)
         return (out[0], out[1]) if out.shape[0] == 2 else (out[0], out[0])
 
-    def encode_query(self, query_feat, query_mask, n_valid_tokens=None):
+    def encode_query(self, query_feat, query_mask, n_valid_tokens=None, return_modular_att=False):
         """xml/model_xml.py:291-295.
         n_valid_tokens (host int, not a reference argument): query_mask.sum() when the caller built the masks on the host
-        and every row is a non-empty prefix of ones -- the packed encoder then needs no read-back (ops.pack_plan)."""
+        and every row is a non-empty prefix of ones -- the packed encoder then needs no read-back (ops.pack_plan).
+        return_modular_att (not a reference argument): -> (video_query, sub_query, att (N, Lq, n_mod) f32), the pooling
+        weights of either path (0 at padded tokens); the query vectors are bitwise those of the plain call."""
         # (not while a HIP graph is being captured: the packing plan needs a host read-back and the packed launch shapes
         # depend on the number of valid tokens of THIS batch -- a graph would bake the warm-up batch's in)
         if PACK_QUERY_TOKENS and query_feat.is_cuda and query_feat.shape[0] * query_feat.shape[1] >= PACK_MIN_ROWS \
                 and query_feat.shape[1] <= 32 and self.config.hidden_size <= 1024 \
                 and not torch.cuda.is_current_stream_capturing():
-            packed = self._encode_query_packed(query_feat, query_mask, n_valid_tokens)
+            packed = self._encode_query_packed(query_feat, query_mask, n_valid_tokens, return_modular_att)
             if packed is not None:
                 return packed
         enc = self.encode_input(query_feat, query_mask, self.query_input_proj, self.query_encoder,
                                 self.query_pos_embed)
+        if return_modular_att:
+            out, att = ops.modular_pool(enc.contiguous(), query_mask.float().contiguous(),
+                                        _f(self.modular_vector_mapping.weight), return_att=True)
+            return (out[0], out[1], att) if out.shape[0] == 2 else (out[0], out[0], att)
         return self.get_modularized_queries(enc, query_mask)
 
-    def _encode_query_packed(self, query_feat, query_mask, n_valid_tokens=None):
+    def _encode_query_packed(self, query_feat, query_mask, n_valid_tokens=None, return_modular_att=False):
         """encode_query without the padding rows.  The reference pads every query to the batch maximum (30 tokens on TVR,
         17.5 valid on average) and runs the projections, the attention and the LayerNorms on all of them; here the valid
         tokens of the batch are packed back to back (include/xmlhip.h "PACKED variable-length sequences"): 42 % fewer rows
@@ -478,6 +489,9 @@ class XML(nn.Module):
         max_len = int(lq)
         x = ops.attention_block_varlen(x, cu, n, max_len, a["wqkv"], a["bqkv"], o["wo"], o["bo"], o["ln_g"], o["ln_b"],
                                        self.query_encoder.self.num_attention_heads)
+        if return_modular_att:
+            out, att = ops.modular_pool_varlen(x, cu, n, max_len, _f(self.modular_vector_mapping.weight), return_att=True)
+            return (out[0], out[1], att) if out.shape[0] == 2 else (out[0], out[0], att)
         out = ops.modular_pool_varlen(x, cu, n, max_len, _f(self.modular_vector_mapping.weight))
         return (out[0], out[1]) if out.shape[0] == 2 else (out[0], out[0])
 
@@ -530,10 +544,58 @@ class XML(nn.Module):
 
     def get_merged_st_ed_prob(self, video_query, video_feat, sub_query, sub_feat, context_mask, cross=False,
                               return_similaity=False):
-        """xml/model_xml.py:455-502 (masked logits)."""
-        assert self.use_video and self.use_sub and not return_similaity
+        """xml/model_xml.py:455-502 (masked logits).  return_similaity (the reference's spelling): also the merged and the
+        per-stream similarities, (st, ed, similarity, video_similarity, sub_similarity), each (N, L) -- cross=False only."""
+        assert self.use_video and self.use_sub
+        if return_similaity:
+            if cross:
+                raise ValueError("return_similaity is defined for cross=False only (xml/model_xml.py:499)")
+            return self._span_evidence(video_query, video_feat, sub_query, sub_feat, context_mask)
         return self._span_logits([video_query, sub_query], [video_feat, sub_feat], [context_mask, context_mask],
                                  ["video", "sub"], cross)
+
+    def _span_evidence(self, video_query, video_feat, sub_query, sub_feat, context_mask):
+        """K7's evidence variant on the pairs (query i, video i): (st, ed, similarity, video_similarity, sub_similarity)."""
+        l_ref = video_feat.shape[1]
+        lpad = _round_up(l_ref, 16)
+        if not self.config.merge_two_stream:
+            raise ValueError("return_similaity needs a merge_two_stream model: the similarities are the merged span "
+                             "predictors' input (xml/model_xml.py:482-487)")
+        q_lin = [getattr(self, n + "_query_linear")(q.contiguous()) for n, q in (("video", video_query), ("sub", sub_query))]
+        f2 = [self.pad_context(f, lpad) for f in (video_feat, sub_feat)]
+        mk = self.pad_context(context_mask.float(), lpad)
+        nq, nv = q_lin[0].shape[0], f2[0].shape[0]
+        assert nq == nv, "cross=False pairs query i with video i"
+        pairs = torch.arange(nv, dtype=torch.int32, device=q_lin[0].device)
+        ev = ops.span_evidence(q_lin, f2, [mk, mk], pairs, pairs, self._conv_weights(), l_ref, True,
+                               self.config.conv_kernel_size)
+        return tuple(t[:, :l_ref] for t in (ev.st_logits, ev.ed_logits, ev.similarity, ev.video_similarity,
+                                            ev.sub_similarity))
+
+    def get_visualization_data(self, query_feat, query_mask, video_feat, video_mask, sub_feat, sub_mask, tef_feat, tef_mask,
+                               st_ed_indices):
+        """xml/model_xml.py:253-289 -> list of N dicts of numpy arrays: modular_att_scores (Lq_i, 2) and, per clip of
+        video i, st_prob / ed_prob (masked logits), similarity_scores, video_similarity, sub_similarity, st_ed_indices.
+        Runs the inference kernels in the model's compute dtype; tef_feat / tef_mask are unused, as in the reference."""
+        if not (self.config.merge_two_stream and self.use_video and self.use_sub and not self.config.get("no_modular", False)):
+            raise ValueError("get_visualization_data needs a two-stream model with merge_two_stream and modular queries "
+                             "(xml/model_xml.py:255)")
+        with torch.no_grad():
+            _, video_feat2, _, sub_feat2 = self.encode_context(video_feat, video_mask, sub_feat, sub_mask)
+            encoded_query = self.encode_input(query_feat, query_mask, self.query_input_proj, self.query_encoder,
+                                              self.query_pos_embed)
+            video_query, sub_query, att = self.get_modularized_queries(encoded_query, query_mask, return_modular_att=True)
+            st, ed, sim, vsim, ssim = self.get_merged_st_ed_prob(video_query, video_feat2, sub_query, sub_feat2, video_mask,
+                                                                 cross=False, return_similaity=True)
+        data = dict(modular_att_scores=att.cpu().numpy(), st_prob=st.cpu().numpy(), ed_prob=ed.cpu().numpy(),
+                    similarity_scores=sim.cpu().numpy(), video_similarity=vsim.cpu().numpy(),
+                    sub_similarity=ssim.cpu().numpy(), st_ed_indices=st_ed_indices.cpu().numpy())
+        query_lengths = query_mask.sum(1).to(torch.long).cpu().tolist()
+        ctx_lengths = video_mask.sum(1).to(torch.long).cpu().tolist()
+        for k, v in data.items():
+            lengths = query_lengths if k == "modular_att_scores" else ctx_lengths
+            data[k] = [e[:l] for l, e in zip(lengths, v)]
+        return [{k: v[i] for k, v in data.items()} for i in range(len(data["modular_att_scores"]))]
 
     def get_st_ed_prob(self, modularied_query, context_feat2, context_mask, module_name="video", cross=False):
         """xml/model_xml.py:504-551 (masked logits, single stream)."""

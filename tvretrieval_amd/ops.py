@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory (torch.empty), the current HIP s
 Every function launches hand-written gfx950 kernels from libxmlhip.so and fails loudly when the library or a
 GPU tensor is missing -- there is no eager/CPU fallback.
 """
+import collections
 import ctypes
 
 import os
@@ -248,12 +249,18 @@ def cross_attention(main_x, main_mask, side_x, side_mask, wq, bq, wkv, bkv, ln_g
     return y
 
 
-def modular_pool(enc, mask, w_m):
-    """K5.  enc (N, Lq, H); mask (N, Lq) f32; w_m (n_mod, H) f32 -> (n_mod, N, H)."""
+def modular_pool(enc, mask, w_m, return_att=False):
+    """K5.  enc (N, Lq, H); mask (N, Lq) f32; w_m (n_mod, H) f32 -> (n_mod, N, H).
+    return_att: -> (pooled, att (N, Lq, n_mod) f32), the softmax weights (0 at masked tokens); pooled is bitwise the same."""
     _req(enc, "enc"); _req(mask, "mask", torch.float32); _req(w_m, "w_m", torch.float32)
     n, lq, hidden = enc.shape
     n_mod = w_m.shape[0]
     out = torch.empty((n_mod, n, hidden), dtype=enc.dtype, device=enc.device)
+    if return_att:
+        att = torch.empty((n, lq, n_mod), dtype=torch.float32, device=enc.device)
+        check(_lib.load().xml_modular_pool_att(_p(enc), _p(mask), _p(w_m), _p(out), _p(att), n, lq, hidden, n_mod,
+                                               dt_of(enc), _stream()), "xml_modular_pool_att")
+        return out, att
     check(_lib.load().xml_modular_pool(_p(enc), _p(mask), _p(w_m), _p(out), n, lq, hidden, n_mod, dt_of(enc),
                                        _stream()), "xml_modular_pool")
     return out
@@ -793,6 +800,49 @@ def convse_rerank(q_lin, feat2, masks, pair_vid, conv_w, l_ref, merged, ksize, s
     return st, ed
 
 
+SpanEvidence = collections.namedtuple("SpanEvidence", "video_similarity sub_similarity similarity st_logits ed_logits")
+
+
+def span_evidence(q_lin, feat2, masks, pair_q, pair_vid, conv_w, l_ref, merged, ksize):
+    """What K7 computes on the way to its logits, for P explicit pairs (xml_span_evidence).  q_lin / feat2 / masks as for
+    convse_rerank (f32, bf16 or SplitRows); pair_q, pair_vid (P,) int32: pair p = query row pair_q[p] x video row pair_vid[p].
+    Returns SpanEvidence of (P, Lpad) f32 rows: the per-stream similarities (unmasked; sub_similarity is None for one-stream
+    models), their mean, and the masked start / end LOGITS -- bitwise those of convse_rerank(..., softmax=False) on the same
+    pairs.  Pairs with an index out of range come back as zero rows."""
+    n_mod = len(q_lin)
+    for m in range(n_mod):
+        _req(q_lin[m], "q_lin"); _req(feat2[m], "feat2", q_lin[m].dtype); _req(masks[m], "mask", torch.float32)
+    _req(pair_q, "pair_q", torch.int32); _req(pair_vid, "pair_vid", torch.int32); _req(conv_w, "conv_w", torch.float32)
+    if pair_q.dim() != 1 or pair_q.shape != pair_vid.shape:
+        raise ValueError("span_evidence: pair_q and pair_vid must be 1-D and of equal length")
+    nq, hidden = q_lin[0].shape
+    nv, lpad, _ = feat2[0].shape
+    P = pair_q.numel()
+    dev = pair_q.device
+    n_conv = 1 if merged else n_mod
+    assert conv_w.numel() == 2 * n_conv * ksize
+    rows = [torch.empty((P, lpad), dtype=torch.float32, device=dev) for _ in range(5)]
+    if n_mod == 1:
+        rows[1] = None
+    if P == 0 or nq == 0:
+        for r in rows:
+            if r is not None:
+                r.zero_()
+        return SpanEvidence(*rows)
+    d = ConvseDesc(nq=nq, nv=nv, kpairs=1, lpad=lpad, l_ref=int(l_ref), hidden=hidden, n_mod=n_mod, merged=int(merged),
+                   ksize=int(ksize), softmax=0, dt=dt_of(q_lin[0]))
+    lib = _lib.load()
+    ws = _workspace(lib.xml_span_evidence_workspace_bytes(ctypes.byref(d), P), dev)
+    one, sp = n_mod == 1, q_lin[0].dtype is F16S
+    inv = lambda t: _p(t.inv) if sp else None          # noqa: E731
+    check(lib.xml_span_evidence(ctypes.byref(d), _p(q_lin[0]), None if one else _p(q_lin[1]), inv(q_lin[0]),
+                                None if one else inv(q_lin[1]), _p(feat2[0]), None if one else _p(feat2[1]), inv(feat2[0]),
+                                None if one else inv(feat2[1]), _p(masks[0]), None if one else _p(masks[1]), _p(pair_q),
+                                _p(pair_vid), P, _p(conv_w), _p(rows[0]), _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(rows[4]),
+                                _p(ws), ws.numel(), _stream()), "xml_span_evidence")
+    return SpanEvidence(*rows)
+
+
 def moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=None, pair_vid=None, vid_len=None):
     """K9/K10.  st, ed (Nq, K, Lpad) f32 probabilities; w (Nq, K) f32 or None.
     summ (Nq, K, 8) f32: the candidate summaries convse_rerank(..., band=(min_l, max_l), pair_w=w) returned for THESE rows.
@@ -962,12 +1012,18 @@ def attention_block_varlen(x, cu_seqlens, n, max_len, wqkv, bqkv, wo, bo, ln_g, 
     return y
 
 
-def modular_pool_varlen(enc, cu_seqlens, n, max_len, w_m):
-    """K5 on packed tokens.  enc (rows, H); w_m (n_mod, H) f32 -> (n_mod, n, H)."""
+def modular_pool_varlen(enc, cu_seqlens, n, max_len, w_m, return_att=False):
+    """K5 on packed tokens.  enc (rows, H); w_m (n_mod, H) f32 -> (n_mod, n, H).
+    return_att: -> (pooled, att (n, max_len, n_mod) f32) in the PADDED layout, 0 beyond every query's own tokens."""
     _req(enc, "enc"); _req(cu_seqlens, "cu_seqlens", torch.int32); _req(w_m, "w_m", torch.float32)
     hidden = enc.shape[1]
     n_mod = w_m.shape[0]
     out = torch.empty((n_mod, n, hidden), dtype=enc.dtype, device=enc.device)
+    if return_att:
+        att = torch.empty((n, int(max_len), n_mod), dtype=torch.float32, device=enc.device)
+        check(_lib.load().xml_modular_pool_att_varlen(_p(enc), _p(cu_seqlens), _p(w_m), _p(out), _p(att), n, int(max_len),
+                                                      hidden, n_mod, dt_of(enc), _stream()), "xml_modular_pool_att_varlen")
+        return out, att
     check(_lib.load().xml_modular_pool_varlen(_p(enc), _p(cu_seqlens), _p(w_m), _p(out), n, int(max_len), hidden, n_mod,
                                               dt_of(enc), _stream()), "xml_modular_pool_varlen")
     return out
