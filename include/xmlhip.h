@@ -273,6 +273,20 @@ int xml_topk_rows(const float* scores, int64_t ld, const int32_t* idx_in, float*
                   int32_t* out_idx, int rows, int n, int k, float alpha, void* ws, size_t ws_bytes,
                   xml_stream_t stream);
 
+/* K8 over an allowed set of columns per row: xml_topk_rows on the row that consists only of its allowed columns -- the
+ * same order and tie rule, the same value bits, indices (or payloads) of the full row.
+ *   allow (allow_rows, ld_allow) uint32 words, allow_rows = 1 (one set for every row) or rows; column c of a row is allowed
+ *   when bit (col0 + c) & 31 of word (col0 + c) >> 5 of its allow row is set -- the COLUMN is tested, also when idx_in gives
+ *   payloads.  col0 >= 0 need not be a multiple of 32 (a shard-local matrix against a corpus-wide bit row);
+ *   ld_allow >= ceil((col0 + n) / 32); bits outside [col0, col0 + n) are ignored.
+ *   A row with a < k allowed columns: its a columns first, then k - a EMPTY slots, out_idx = -1 and out_val = 0 when
+ *   alpha != 0 (expf(alpha * -inf)), -inf when alpha == 0.  a = 0 is legal.  An allowed column that holds -inf ranks above
+ *   every disallowed column.  out_cnt (rows) int32 or NULL = min(k, a).  k <= 256, k <= n. */
+int xml_topk_rows_allowed(const float* scores, int64_t ld, const int32_t* idx_in, const uint32_t* allow,
+                          int64_t ld_allow, int allow_rows, int col0, float* out_val, int32_t* out_idx,
+                          int32_t* out_cnt, int rows, int n, int k, float alpha, void* ws, size_t ws_bytes,
+                          xml_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Exact-rank mode: the bf16 K6 pass as a FILTER in front of f32 scores (inference.vcmr_search on an index built with
  * exact_filter=True).  The reference ranks videos by f32 scores (torch.topk, xml/inference.py:347-348); a bf16 K6 moves
@@ -306,6 +320,11 @@ int xml_round_bf16_rows_err(const float* y, void* yb, float* err, int64_t rows, 
  * lower bound of the final k-th score, and a video below thr has an f32 score < thr + eps_q = T_k. */
 int xml_select_ge_rows(const float* scores, int64_t ld, const float* thr, int32_t* idx, int cap, int32_t* cnt, int rows,
                        int n, xml_stream_t stream);
+/* xml_select_ge_rows over an allowed set of columns per row: allow / ld_allow / allow_rows / col0 as for
+ * xml_topk_rows_allowed; a disallowed column is never selected and never counted. */
+int xml_select_ge_rows_allowed(const float* scores, int64_t ld, const float* thr, const uint32_t* allow, int64_t ld_allow,
+                               int allow_rows, int col0, int32_t* idx, int cap, int32_t* cnt, int rows, int n,
+                               xml_stream_t stream);
 size_t xml_q2c_rescore_workspace_bytes(int nq, int nv, int kpairs);
 int xml_q2c_rescore(int n_mod, const void* qn0, const void* qn1, const void* cn0, const void* cn1, const float* mask0,
                     const float* mask1, const int32_t* pair_vid, float* out, int nq, int nv, int kpairs, int lpad,

@@ -83,6 +83,8 @@ SIGNATURES = {
     "xml_topk_rows_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "xml_topk_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                               c_void_p, c_size_t, c_void_p]),
+    "xml_topk_rows_allowed": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_size_t, c_void_p]),
     # ---- exact-rank mode (exact.hip, convse.hip) ----
     "xml_round_bf16_rows_err": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "xml_split_f16_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
@@ -101,6 +103,8 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
     "xml_select_ge_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "xml_select_ge_rows_allowed": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int,
+                                           c_void_p, c_int, c_int, c_void_p]),
     "xml_q2c_rescore_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "xml_q2c_rescore": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -75,9 +75,22 @@ __global__ void exact_certificate_kernel(const float* __restrict__ filt, int m, 
 }
 
 // one workgroup per row: the columns whose score reaches the row's threshold.  idx == NULL: count only.
+// ALLOW (xml_select_ge_rows_allowed): column c also needs bit col0 + c of the row's allow words (K8's layout, topk.hip);
+// the word is fetched beside the score.  ALLOW = false is the kernel as it was.
+template <bool ALLOW>
+struct SelectAllow {};
+template <>
+struct SelectAllow<true> {
+  const uint32_t* bits;   // (allow_rows, ld) words
+  int64_t ld;
+  int rows;               // 1: every row uses row 0
+  int col0;
+};
+
+template <bool ALLOW = false>
 __global__ __launch_bounds__(256) void select_ge_rows_kernel(const float* __restrict__ scores, int64_t ld, const float* __restrict__ thr,
                                                              int32_t* __restrict__ idx, int cap, int32_t* __restrict__ cnt,
-                                                             int n) {
+                                                             int n, SelectAllow<ALLOW> aw) {
   __shared__ int s_cnt;
   const int row = blockIdx.x, lane = threadIdx.x & 63;
   if (threadIdx.x == 0) s_cnt = 0;
@@ -86,7 +99,12 @@ __global__ __launch_bounds__(256) void select_ge_rows_kernel(const float* __rest
   const float* r = scores + (int64_t)row * ld;
   for (int base = 0; base < n; base += 256) {
     const int i = base + threadIdx.x;
-    const bool take = i < n && r[i] >= t;
+    bool take = i < n && r[i] >= t;
+    if constexpr (ALLOW) {
+      const uint32_t c = (uint32_t)aw.col0 + (uint32_t)i;
+      const uint32_t word = i < n ? aw.bits[(aw.rows > 1 ? (int64_t)row * aw.ld : 0) + (c >> 5)] : 0u;
+      take = take && ((word >> (c & 31u)) & 1u);
+    }
     const unsigned long long bal = __ballot(take);
     if (bal) {
       int off = 0;
@@ -106,7 +124,21 @@ extern "C" int xml_select_ge_rows(const float* scores, int64_t ld, const float* 
                                   int rows, int n, xml_stream_t stream) {
   XML_ENTER();
   if (!scores || !thr || !cnt || rows <= 0 || n <= 0 || ld < n || (idx && cap <= 0)) return XML_ERR_BAD_ARG;
-  hipLaunchKernelGGL(select_ge_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, scores, ld, thr, idx, cap, cnt, n);
+  hipLaunchKernelGGL(select_ge_rows_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, scores, ld, thr, idx, cap, cnt,
+                     n, SelectAllow<false>{});
+  XML_CHECK_LAUNCH();
+  return XML_OK;
+}
+
+extern "C" int xml_select_ge_rows_allowed(const float* scores, int64_t ld, const float* thr, const uint32_t* allow,
+                                          int64_t ld_allow, int allow_rows, int col0, int32_t* idx, int cap, int32_t* cnt,
+                                          int rows, int n, xml_stream_t stream) {
+  XML_ENTER();
+  if (!scores || !thr || !allow || !cnt || rows <= 0 || n <= 0 || ld < n || (idx && cap <= 0) || col0 < 0) return XML_ERR_BAD_ARG;
+  if ((int64_t)col0 + n > INT32_MAX || ld_allow < ((int64_t)col0 + n + 31) / 32) return XML_ERR_BAD_ARG;
+  if (allow_rows != 1 && allow_rows != rows) return XML_ERR_BAD_ARG;
+  hipLaunchKernelGGL(select_ge_rows_kernel<true>, dim3(rows), dim3(256), 0, (hipStream_t)stream, scores, ld, thr, idx, cap, cnt,
+                     n, SelectAllow<true>{allow, ld_allow, allow_rows, col0});
   XML_CHECK_LAUNCH();
   return XML_OK;
 }

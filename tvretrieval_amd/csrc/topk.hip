@@ -28,11 +28,32 @@ __device__ __forceinline__ float key_to_float(uint32_t k) {
 //   c. if the list holds between k and 1024 entries (and the threshold ties need no column-ordered tie-break), the exact
 //      selection runs on the list; otherwise -- adversarially ordered rows, massive ties -- the kernel falls back to
 //      re-reading the row for every radix pass.  Either way the result is the exact top-k with the same tie rule.
-template <int VPT>
+//
+// ALLOW (xml_topk_rows_allowed): the same body with one more reason for key 0.  Column c of the row takes part only if bit
+// col0 + c of the row's allow words is set; a disallowed column is key 0 and not valid, exactly like a column past the row
+// end, so it is never counted, never a candidate and never emitted -- the result is the top-k of the row's allowed columns.
+// The words are fetched beside the scores (the register-resident class once, long rows next to the eight-at-a-time loads;
+// the 64 lanes of a wave share two or three words).  A row with a < k allowed columns selects its a columns; the other
+// slots are written as empty (idx -1, value exp(alpha * -inf) = 0, or -inf when alpha == 0).  The sample of a long row sees
+// only its allowed columns, so r is scaled by their share: the r-th largest of the a_s allowed sample columns stands for
+// about 3 k of the a_n allowed columns of the row.  A mask that leaves fewer than r columns in the sample sends the row to
+// the multi-pass fallback; the result is exact either way.  ALLOW = false compiles to the code it was before the flag.
+template <bool ALLOW>
+struct TopkAllow {};      // (no operand: the kernel's arguments are those it had before the flag)
+template <>
+struct TopkAllow<true> {
+  const uint32_t* bits;   // (allow_rows, ld) words
+  int64_t ld;
+  int rows;               // 1: every row uses row 0
+  int col0;
+  int32_t* out_cnt;       // (rows) or NULL
+};
+
+template <int VPT, bool ALLOW = false>
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ scores, int64_t ld,
                                                         const int32_t* __restrict__ idx_in,
                                                         float* __restrict__ out_val, int32_t* __restrict__ out_idx,
-                                                        int n, int k, float alpha) {
+                                                        int n, int k, float alpha, TopkAllow<ALLOW> aw) {
   constexpr int CAND_CAP = VPT > 0 ? 1 : 1024;
   constexpr int SAMPLE = 2048;
   __shared__ uint32_t hist[256];
@@ -45,17 +66,69 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   const int32_t* pay = idx_in ? idx_in + (int64_t)blockIdx.x * ld : nullptr;
   constexpr int NK = VPT > 0 ? VPT : SAMPLE / 256;
   const int n_reg = VPT > 0 ? n : min(n, SAMPLE);
+  // ALLOW: the row's words, the bit test, and how many columns are allowed in the row (a_n) and in the sample (a_s)
+  const uint32_t* arow = nullptr;
+  uint32_t col0 = 0;
+  if constexpr (ALLOW) {
+    arow = aw.bits + (aw.rows > 1 ? (int64_t)blockIdx.x * aw.ld : 0);
+    col0 = (uint32_t)aw.col0;
+  }
+  auto bit_of = [&](uint32_t word, int i) { return ((word >> ((col0 + (uint32_t)i) & 31u)) & 1u) != 0u; };
+  auto key_at = [&](int j) -> uint32_t {            // rare paths: one column re-read from the row
+    if constexpr (ALLOW) {
+      if (!bit_of(arow[(col0 + (uint32_t)j) >> 5], j)) return 0u;
+    }
+    return ord_key(row[j]);
+  };
+  uint32_t k_sel = (uint32_t)k, a_n = (uint32_t)n, a_s = (uint32_t)n_reg;      // (ALLOW: k_sel = min(k, a_n))
+  if constexpr (ALLOW) {
+    __shared__ uint32_t s_an, s_as;
+    if (tid == 0) { s_an = 0; s_as = 0; }
+    __syncthreads();
+    const uint32_t lo = col0, hi = col0 + (uint32_t)n, hs = col0 + (uint32_t)n_reg;      // bits [lo, hi), sample [lo, hs)
+    uint32_t c_n = 0, c_s = 0;
+    for (uint32_t w = (lo >> 5) + (uint32_t)tid; w <= ((hi - 1) >> 5); w += 256) {
+      uint32_t v = arow[w];
+      if (w == (lo >> 5)) v &= 0xffffffffu << (lo & 31u);
+      uint32_t vs = v;
+      if (w == ((hi - 1) >> 5) && (hi & 31u)) v &= 0xffffffffu >> (32u - (hi & 31u));
+      if (w > ((hs - 1) >> 5)) vs = 0u;
+      else if (w == ((hs - 1) >> 5) && (hs & 31u)) vs &= 0xffffffffu >> (32u - (hs & 31u));
+      c_n += (uint32_t)__popc(v);
+      c_s += (uint32_t)__popc(vs);
+    }
+    if (c_n) atomicAdd(&s_an, c_n);
+    if (c_s) atomicAdd(&s_as, c_s);
+    __syncthreads();
+    a_n = s_an;
+    a_s = s_as;
+    k_sel = min((uint32_t)k, a_n);
+    if (tid == 0 && aw.out_cnt) aw.out_cnt[blockIdx.x] = (int32_t)k_sel;
+    if (k_sel == 0) {                   // (block-uniform) nothing allowed: k empty slots
+      if (tid < k) {
+        out_val[(int64_t)blockIdx.x * k + tid] = (alpha != 0.f) ? 0.f : -INFINITY;
+        out_idx[(int64_t)blockIdx.x * k + tid] = -1;
+      }
+      return;
+    }
+  }
   uint32_t keys[NK];
   {   // all loads first, then the conversions: written as load -> convert per element, hipcc waits for each load in turn
     float raw[NK];
+    uint32_t abit[ALLOW ? NK : 1];
 #pragma unroll
     for (int j = 0; j < NK; ++j) {
       const int i = tid + j * 256;
       raw[j] = i < n_reg ? row[i] : 0.f;
+      if constexpr (ALLOW) abit[j] = i < n_reg ? arow[(col0 + (uint32_t)i) >> 5] : 0u;
     }
 #pragma unroll
-    for (int j = 0; j < NK; ++j)
+    for (int j = 0; j < NK; ++j) {
       keys[j] = tid + j * 256 < n_reg ? ord_key(raw[j]) : 0u;   // 0 sorts below every real key (ord_key(x) >= 1)
+      if constexpr (ALLOW) {
+        if (!bit_of(abit[j], tid + j * 256)) keys[j] = 0u;
+      }
+    }
   }
   enum { SRC_REG = 0, SRC_ROW = 1, SRC_CAND = 2 };
   int src = VPT > 0 ? SRC_REG : SRC_ROW;
@@ -64,19 +137,26 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   auto walk = [&](auto&& f) {
     if (src == SRC_REG) {
 #pragma unroll
-      for (int j = 0; j < NK; ++j) f(keys[j], tid + j * 256, tid + j * 256 < n_reg);
+      for (int j = 0; j < NK; ++j) f(keys[j], tid + j * 256, ALLOW ? keys[j] != 0u : tid + j * 256 < n_reg);
     } else if (src == SRC_ROW) {
       for (int base = 0; base < n; base += 256 * 8) {        // eight loads in flight per thread (see above)
         float raw[8];
+        uint32_t abit[ALLOW ? 8 : 1];
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int i = base + u * 256 + tid;
           raw[u] = i < n ? row[i] : 0.f;
+          if constexpr (ALLOW) abit[u] = i < n ? arow[(col0 + (uint32_t)i) >> 5] : 0u;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
           const int i = base + u * 256 + tid;
-          if (base + u * 256 < n) f(i < n ? ord_key(raw[u]) : 0u, i, i < n);      // (wave-uniform condition)
+          if constexpr (ALLOW) {
+            const bool ok = i < n && bit_of(abit[u], i);
+            if (base + u * 256 < n) f(ok ? ord_key(raw[u]) : 0u, i, ok);
+          } else {
+            if (base + u * 256 < n) f(i < n ? ord_key(raw[u]) : 0u, i, i < n);      // (wave-uniform condition)
+          }
         }
       }
     } else {
@@ -152,8 +232,10 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
 
   bool done = false;
   if constexpr (VPT == 0) {
-    const uint32_t r = (uint32_t)(((int64_t)3 * k * SAMPLE + n - 1) / n) + 2;
-    if (n >= 2 * SAMPLE && r <= SAMPLE / 8) {
+    // (ALLOW: a_s of the row's a_n allowed columns lie in the sample -- the same estimate over the allowed columns alone)
+    const uint32_t r = ALLOW ? (uint32_t)(((int64_t)3 * k_sel * a_s + a_n - 1) / a_n) + 2
+                             : (uint32_t)(((int64_t)3 * k * SAMPLE + n - 1) / n) + 2;
+    if (n >= 2 * SAMPLE && r <= SAMPLE / 8 && (!ALLOW || r <= a_s)) {
       src = SRC_REG;
       select(r);                                           // a. threshold from the sample
       const uint32_t t0 = s_prefix;
@@ -175,10 +257,10 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
       __syncthreads();
       const uint32_t cnt = s_cnt;
       __syncthreads();
-      if (cnt >= (uint32_t)k && cnt <= (uint32_t)CAND_CAP) {   // c. exact selection on the candidates
+      if (cnt >= k_sel && cnt <= (uint32_t)CAND_CAP) {         // c. exact selection on the candidates
         n_cand = (int)cnt;
         src = SRC_CAND;
-        select((uint32_t)k);
+        select(k_sel);
         if (s_eq_total == s_need) {
           const uint32_t T = s_prefix;
           if (tid == 0) s_cnt = 0;
@@ -195,7 +277,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   }
   if (!done) {
     __syncthreads();                          // (the pre-filter's readers of s_need / s_eq_total are done)
-    select((uint32_t)k);
+    select(k_sel);
     const uint32_t T = s_prefix;
     const uint32_t need_eq = s_need;          // elements == T still to take (>= 1)
     const uint32_t eq_total = s_eq_total;     // elements == T in the row
@@ -213,7 +295,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
       // 10 000 queries at the TVR shape ended on a different one of two equal-score moments than the single-GPU pass.)
       // Rare path, short rows (merges: n = world x c): one block-wide minimum per element taken.
       for (int j = tid; j < n; j += 256) {
-        const uint32_t kj = ord_key(row[j]);
+        const uint32_t kj = key_at(j);
         if (kj > T) emit(kj, j);
       }
       __shared__ unsigned long long s_min;
@@ -223,7 +305,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         __syncthreads();
         unsigned long long best = ~0ull;
         for (int j = tid; j < n; j += 256) {
-          if (ord_key(row[j]) == T) {
+          if (key_at(j) == T) {
             const unsigned long long c = ((unsigned long long)(uint32_t)pay[j] << 32) | (unsigned long long)(uint32_t)j;
             if ((t == 0 || c > last) && c < best) best = c;
           }
@@ -241,7 +323,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         uint32_t key = 0;
         bool eq = false;
         if (i < n) {
-          key = ord_key(row[i]);      // rare path: plain re-read (dynamic register indexing would go to scratch)
+          key = key_at(i);            // rare path: plain re-read (dynamic register indexing would go to scratch)
           if (key > T) emit(key, i);
           eq = key == T;
         }
@@ -259,7 +341,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
         if (s_eq_taken >= need_eq) {
           // remaining chunks can only contribute elements > T
           for (int j = base + 256 + tid; j < n; j += 256) {
-            const uint32_t kj = ord_key(row[j]);
+            const uint32_t kj = key_at(j);
             if (kj > T) emit(kj, j);
           }
           break;
@@ -283,8 +365,14 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   const uint32_t pos = (uint32_t)tid < n_comp ? rank : (uint32_t)tid;
   if (pos < (uint32_t)k && ((uint32_t)tid < n_comp || tid < k)) {
     const float s = key_to_float((uint32_t)(mine >> 32));
-    out_val[(int64_t)blockIdx.x * k + pos] = (alpha != 0.f) ? expf(alpha * s) : s;
-    out_idx[(int64_t)blockIdx.x * k + pos] = (int32_t)(0xffffffffu - (uint32_t)(mine & 0xffffffffull));
+    if constexpr (ALLOW) {                    // fewer than k allowed columns: the slots beyond them are written as empty
+      const bool empty = (uint32_t)tid >= n_comp;
+      out_val[(int64_t)blockIdx.x * k + pos] = empty ? ((alpha != 0.f) ? 0.f : -INFINITY) : ((alpha != 0.f) ? expf(alpha * s) : s);
+      out_idx[(int64_t)blockIdx.x * k + pos] = empty ? -1 : (int32_t)(0xffffffffu - (uint32_t)(mine & 0xffffffffull));
+    } else {
+      out_val[(int64_t)blockIdx.x * k + pos] = (alpha != 0.f) ? expf(alpha * s) : s;
+      out_idx[(int64_t)blockIdx.x * k + pos] = (int32_t)(0xffffffffu - (uint32_t)(mine & 0xffffffffull));
+    }
   }
 }
 
@@ -304,7 +392,24 @@ extern "C" int xml_topk_rows(const float* scores, int64_t ld, const int32_t* idx
   // L2 re-read variant measured faster (1.45 vs 1.88 ms per 10 000 rows)
   auto kern = n <= 256 * 12 ? topk_rows_kernel<12> : topk_rows_kernel<0>;
   hipLaunchKernelGGL(kern, dim3(rows), dim3(256), 0, (hipStream_t)stream, scores, ld, idx_in, out_val,
-                     out_idx, n, k, alpha);
+                     out_idx, n, k, alpha, TopkAllow<false>{});
+  XML_CHECK_LAUNCH();
+  return XML_OK;
+}
+
+extern "C" int xml_topk_rows_allowed(const float* scores, int64_t ld, const int32_t* idx_in, const uint32_t* allow,
+                                     int64_t ld_allow, int allow_rows, int col0, float* out_val, int32_t* out_idx,
+                                     int32_t* out_cnt, int rows, int n, int k, float alpha, void* ws, size_t ws_bytes,
+                                     xml_stream_t stream) {
+  XML_ENTER();
+  (void)ws; (void)ws_bytes;
+  if (!scores || !allow || !out_val || !out_idx || rows <= 0 || n <= 0 || k <= 0 || ld < n || col0 < 0) return XML_ERR_BAD_ARG;
+  if ((int64_t)col0 + n > INT32_MAX || ld_allow < ((int64_t)col0 + n + 31) / 32) return XML_ERR_BAD_ARG;
+  if (allow_rows != 1 && allow_rows != rows) return XML_ERR_BAD_ARG;
+  if (k > 256 || k > n) return XML_ERR_UNSUPPORTED;
+  auto kern = n <= 256 * 12 ? topk_rows_kernel<12, true> : topk_rows_kernel<0, true>;    // (the dispatch of xml_topk_rows)
+  hipLaunchKernelGGL(kern, dim3(rows), dim3(256), 0, (hipStream_t)stream, scores, ld, idx_in, out_val, out_idx, n, k, alpha,
+                     TopkAllow<true>{allow, ld_allow, allow_rows, col0, out_cnt});
   XML_CHECK_LAUNCH();
   return XML_OK;
 }

@@ -419,14 +419,59 @@ def exact_slack(hidden):
     return 2.0 * (hidden + 1) * 2.0 ** -24
 
 
-def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False):
+def pack_video_allow(allowed):
+    """The allow-bit matrix of a restricted search (vcmr_search(video_allow=)) from booleans.
+    allowed: (Nv,) or (R, Nv) bool array or tensor, host or device -> (R, ceil(Nv / 32)) int32 words on the same side (a numpy
+    array for host input, numpy or CPU tensor alike; a device tensor for a device tensor): video v is allowed when bit v & 31
+    of word v >> 5 is set; the padding bits of the last word are 0."""
+    on_device = torch.is_tensor(allowed) and allowed.is_cuda
+    a = allowed if on_device else (allowed.numpy() if torch.is_tensor(allowed) else np.asarray(allowed))
+    if (a.dtype != torch.bool) if on_device else (a.dtype != np.bool_):
+        raise ValueError("pack_video_allow: a bool array is expected, got dtype %s" % (a.dtype,))
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError("pack_video_allow: (Nv,) or (R, Nv) with Nv >= 1 expected, got shape %s" % (tuple(allowed.shape),))
+    r, nv = int(a.shape[0]), int(a.shape[1])
+    nw = (nv + 31) // 32
+    if not on_device:
+        bits = np.zeros((r, nw * 32), dtype=np.uint8)
+        bits[:, :nv] = a
+        words = (bits.reshape(r, nw, 32).astype(np.uint32) << np.arange(32, dtype=np.uint32)).sum(-1, dtype=np.uint32)
+        return np.ascontiguousarray(words).view(np.int32)
+    bits = torch.zeros((r, nw * 32), dtype=torch.int64, device=a.device)
+    bits[:, :nv] = a
+    words = (bits.reshape(r, nw, 32) << torch.arange(32, device=a.device)).sum(-1)           # 0 .. 2^32 - 1
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+
+
+def _check_video_allow(video_allow, index, nq):
+    """video_allow of a search over index for nq queries: int32 words on the index's device, 1 or nq rows."""
+    nw = (index.n_videos + 31) // 32
+    if not torch.is_tensor(video_allow) or video_allow.dtype != torch.int32 or video_allow.dim() != 2:
+        raise ValueError("video_allow must be a 2-D int32 tensor of bit words (pack_video_allow)")
+    if video_allow.shape[1] < nw or video_allow.shape[0] not in (1, nq):
+        raise ValueError("video_allow must be (1 | %d, >= %d) words for %d videos and %d queries, got %s"
+                         % (nq, nw, index.n_videos, nq, tuple(video_allow.shape)))
+    return video_allow
+
+
+def _allow_rows(video_allow, rows):
+    """The allow rows of a subset / permutation `rows` of the queries (a shared row serves every subset)."""
+    if video_allow is None or video_allow.shape[0] == 1:
+        return video_allow
+    return video_allow.index_select(0, rows).contiguous()
+
+
+def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None):
     """Exact-rank replacement of K6 + K8: dispatches on index.exact.mode (round-3 f32 re-score / split-f16 pipeline)."""
+    kw = dict(video_allow=video_allow) if video_allow is not None else {}
     if index.exact.mode == "f16s":
-        return stage_exact_topk_f16s(index, qvec, k, alpha, ops, defer_check)
-    return stage_exact_topk_f32(index, qvec, k, alpha, ops)
+        return stage_exact_topk_f16s(index, qvec, k, alpha, ops, defer_check, **kw)
+    return stage_exact_topk_f32(index, qvec, k, alpha, ops, **kw)
 
 
-def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False):
+def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None):
     """The exact-rank chain on the 16-bit MFMA pipe, with no host read-back on the common path (capturable):
       1. q normalised (f32) and split: hi plane (f16) -> K6 FILTER over the corpus's hi planes; rounding-error norms e_q;
       2. K8: the M best filter scores per query (M = 128: the f16 filter's error bound is 8x tighter than bf16's);
@@ -438,6 +483,9 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False)
       6. only if more than R queries fail or a query has more than C such videos (scores closer together than any 16-bit
          filter resolves) the overflow flag is raised: eager callers (defer_check=False) read it -- one 4-byte read-back
          after everything is enqueued -- and re-score those queries against the whole corpus; graphed callers get the flag.
+    video_allow (pack_video_allow's words, 1 or Nq rows): every selection over corpus columns -- the candidate K8, the second
+    tier's select_ge_rows, the third tier's full row -- takes the mask; candidate slots a short row leaves empty are id -1,
+    which the re-score turns into -inf.  The certificate is unchanged (conservative: a -inf at the candidates' end passes).
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
     ex = index.exact
     mods = index.modalities
@@ -445,6 +493,8 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False)
         raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
                          "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
     masks = [index.mask[m] for m in mods]
+    akw = (lambda rows=None: dict(allow=_allow_rows(video_allow, rows) if rows is not None else video_allow)) \
+        if video_allow is not None else (lambda rows=None: {})
     q_sr, q_hi, eq = [], [], []
     for m in mods:
         q = qvec[m].contiguous()
@@ -460,7 +510,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False)
     nq, hidden = q_hi[0].shape
     filt = _k6(index, q_hi, ops)
     m_c = min(ex.n_candidates, index.n_videos)
-    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0)
+    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, **akw())
     rows_c = [ex.feat1n_f32[m] for m in mods]                    # SplitRows (Nv, lpad, H)
     cand_r = ops.q2c_rescore(q_sr, rows_c, masks, cand_i)
     top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
@@ -480,7 +530,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False)
         is_fail = fail.index_select(0, order) != 0
         inf_ = torch.full((), float("inf"), device=fail.device)
         thr = torch.where(is_fail, thr_all.index_select(0, order), inf_).contiguous()      # passing slots select nothing
-        cand2, cnt2 = ops.select_ge_rows(filt.index_select(0, order).contiguous(), thr, c_cap)
+        cand2, cnt2 = ops.select_ge_rows(filt.index_select(0, order).contiguous(), thr, c_cap, **akw(order))
         q_sub = [sr[order] for sr in q_sr]
         q_sub = [ops.SplitRows(sr.data.contiguous(), sr.inv.contiguous()) for sr in q_sub]
         full = ops.q2c_rescore(q_sub, rows_c, masks, cand2)
@@ -507,7 +557,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False)
                     qs = [ops.SplitRows(sr.data.index_select(0, rows).contiguous(), sr.inv.index_select(0, rows).contiguous())
                           for sr in q_sr]
                     allv = ops.q2c_rescore(qs, rows_c, masks, every.repeat(rows.numel(), 1).contiguous())
-                    fw, fi = ops.topk_rows(allv, k, alpha=alpha)
+                    fw, fi = ops.topk_rows(allv, k, alpha=alpha, **akw(rows))
                     top_w.index_copy_(0, rows, fw)
                     top_i.index_copy_(0, rows, fi)
                 info["n_full_rows"] = int(bad.numel())
@@ -516,7 +566,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False)
     return top_w, top_i, info
 
 
-def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops):
+def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
     """Exact-rank replacement of K6 + K8 (index.exact is set, f32 query vectors): the f32 path's top-k videos per query.
       1. q_b = rne_bf16(normalize(q)) with its rounding-error norm e_q; bf16 K6 over the filter image (the timed K6);
       2. K8 proposes the M best filter scores per query (raw values + ids);
@@ -525,9 +575,12 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops):
       5. per-query certificate  b_M + eps_q < T_k ; the few queries that fail get a second tier -- every video whose filter
          score reaches T_k - eps_q (nothing below that line can enter the top-k) is re-scored too -- or, when the scores are
          too close together for that (> EXACT_TIER2_CAP such videos), a full f32 K6 row (the f32 path itself).
+    video_allow: as in stage_exact_topk_f16s -- the candidate K8, both select_ge_rows calls and the fallback's full row.
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
     ex = index.exact
     mods = index.modalities
+    akw = (lambda rows=None: dict(allow=_allow_rows(video_allow, rows) if rows is not None else video_allow)) \
+        if video_allow is not None else (lambda rows=None: {})
     if k > min(ex.n_candidates, index.n_videos):
         raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
                          "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
@@ -541,7 +594,7 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops):
         qb.append(b), eq.append(e)
     filt = _k6(index, qb, ops)
     m_c = min(ex.n_candidates, index.n_videos)
-    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0)
+    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, **akw())
     f32rows = [ex.feat1n_f32[m] for m in mods]
     cand_r = ops.q2c_rescore(qn, f32rows, masks, cand_i)
     top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
@@ -556,15 +609,17 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops):
         # score reaches T_k - eps can still enter: usually a few dozen more than M.  Re-score exactly those.
         thr = thr_all.index_select(0, rows).contiguous()
         frows = filt.index_select(0, rows).contiguous()
-        cap = int(ops.select_ge_rows(frows, thr).max())
+        cap = int(ops.select_ge_rows(frows, thr, **akw(rows)).max())
+        if video_allow is not None:
+            cap = max(cap, k)          # (rows with fewer than k allowed videos: the list is filled up with id -1 = -inf)
         if cap <= EXACT_TIER2_CAP:
-            cand2, _ = ops.select_ge_rows(frows, thr, cap)
+            cand2, _ = ops.select_ge_rows(frows, thr, cap, **akw(rows))
             full = ops.q2c_rescore(qsub, f32rows, masks, cand2)                       # (-inf where a row has fewer candidates)
             fw, fi = ops.topk_rows(full, k, alpha=alpha, idx_in=cand2)
         else:   # scores so close together that the filter cannot separate them: the f32 K6 row itself
             n_full = nf
             full = ops.q2c_scores_fused(qsub, f32rows, masks)
-            fw, fi = ops.topk_rows(full, k, alpha=alpha)
+            fw, fi = ops.topk_rows(full, k, alpha=alpha, **akw(rows))
         top_w.index_copy_(0, rows, fw)
         top_i.index_copy_(0, rows, fi)
     info = dict(n_fail=nf, n_full_rows=n_full, fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s,
@@ -682,20 +737,29 @@ def pad_moment_tail(flat_scores, flat_indices, k_videos, l_ref, min_pred_l=None,
 
 
 def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops=hip_ops, external_top=None,
-                     defer_exact_check=False):
+                     defer_exact_check=False, video_allow=None):
     """K6 + K8 (or the exact-rank chain, or a caller's video lists): (q2c or None, top_w (Nq, K) f32 = exp(alpha s) desc,
-    top_i (Nq, K) int32, exact-rank info or None).  Per query independent of the rest of the batch."""
+    top_i (Nq, K) int32, exact-rank info or None).  Per query independent of the rest of the batch.
+    video_allow (pack_video_allow's words, 1 or Nq rows, on the device): every query's list is the list of the corpus that
+    holds only its allowed videos (indices in this index's numbering); a query with a < K of them ends in K - a empty slots
+    (top_i -1, top_w 0, or -inf when alpha == 0), which yield no moments.  K6 still scores every video."""
     exact = None
+    akw = {}
+    if video_allow is not None:
+        if external_top is not None:
+            raise ValueError("video_allow and external_top exclude each other: a caller's video lists replace the ranking "
+                             "the mask restricts (filter the lists instead)")
+        akw = dict(video_allow=_check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0]))
     if external_top is None and index.exact is not None:
         q2c = None          # (the f32 (Nq, Nv) matrix is never formed; exact["q2c_filter"] is the bf16 pass's)
         # defer_exact_check (split-f16 exact mode): no host read-back inside the pass; out["exact"]["overflow_dev"] (device
         # bool, None when every video is a candidate) says whether the on-device second tier's capacity was exceeded
         top_w, top_i, exact = stage_exact_topk(index, qvec, min(max_vcmr_video, index.n_videos), q2c_alpha, ops,
-                                               **(dict(defer_check=True) if defer_exact_check else {}))
+                                               **(dict(defer_check=True) if defer_exact_check else {}), **akw)
     elif external_top is None:
         q2c = stage_q2c(index, qvec, ops)
         k = min(max_vcmr_video, index.n_videos)
-        top_w, top_i = ops.topk_rows(q2c, k, alpha=q2c_alpha)
+        top_w, top_i = ops.topk_rows(q2c, k, alpha=q2c_alpha, **(dict(allow=akw["video_allow"]) if akw else {}))
     else:   # external video-retrieval results replace K6/K8 (xml/inference.py:349-355): (meta idx int32, exp(alpha*s))
         q2c = None
         top_i, top_w = external_top
@@ -723,7 +787,7 @@ def stage_moments(model, index, qvec, top_w, top_i, min_pred_l=2, max_pred_l=16,
 
 def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_before_nms=200, q2c_alpha=20.0,
                 min_pred_l=2, max_pred_l=16, svmr_video=None, ops=hip_ops, external_top=None, pad_tail=False,
-                defer_exact_check=False, n_valid_tokens=None):
+                defer_exact_check=False, n_valid_tokens=None, video_allow=None):
     """Device part of compute_query2ctx_info for one query batch (xml/inference.py:308-386), single GPU.
 
     Returns device tensors:
@@ -734,11 +798,17 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     pad_tail=True: always max_before_nms rows, the reference's shape -- missing candidates become zero-score rows at
     length-masked positions (pad_moment_tail) instead of flat = -1.
     n_valid_tokens (host int): query_mask.sum() when the masks were built on the host (prefix masks) -- the packed query
-    encoder of large batches then needs no read-back and the whole pass is enqueued without a host synchronisation."""
+    encoder of large batches then needs no read-back and the whole pass is enqueued without a host synchronisation.
+    video_allow (pack_video_allow: (1 | Nq, ceil(Nv / 32)) int32 words on the device): the search restricted to each query's
+    allowed videos -- exactly the unrestricted result on the corpus of those videos, in this index's numbering (see
+    stage_video_topk for queries with fewer than K allowed videos).  Not with external_top or pad_tail=True."""
+    if video_allow is not None and pad_tail:
+        raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
+                         "rows in the empty video slots of a restricted list")
     qvec = stage_query_vectors(model, query_feat, query_mask, n_valid_tokens)
     forked = fork_query_linears(model, index, qvec, ops) if not (hasattr(ops, "MOMENT_SUMM") and K7_SUMMARIES) else None
     q2c, top_w, top_i, exact = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, external_top,
-                                                defer_exact_check)
+                                                defer_exact_check, **(dict(video_allow=video_allow) if video_allow is not None else {}))
     q_lin = None
     if forked is not None:
         q_lin, lin_done = forked
@@ -909,7 +979,7 @@ def host_chunks(nq, first=1024, growth=3, largest=16384):
 
 def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, meta2vid=None, chunk=1024, lq=None,
                      clip_length=1.5, buffers=None, timings=None, ops=hip_ops, max_vcmr_video=100, max_before_nms=200,
-                     q2c_alpha=20.0, min_pred_l=2, max_pred_l=16, pad_tail=False, chunk_growth=3, wait=True):
+                     q2c_alpha=20.0, min_pred_l=2, max_pred_l=16, pad_tail=False, chunk_growth=3, wait=True, video_allow=None):
     """VCMR from host memory to host memory: the path of the reference's query loop (xml/inference.py:302-314 moves every
     batch host -> device, :383-386 moves the lists device -> host; start_end_dataset.py:362-370) for a whole query set.
 
@@ -931,13 +1001,22 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     i and the device never idles between query sets -- an idle gap of a few milliseconds costs the next K6 launch 2-3 % by
     itself (clock / cache state; tools/bench_idle_effect.py).  The records of a pass stay valid until the second next pass.
     timings (dict, optional): h2d_s / device_s / decode_s / d2h_s from HIP events (copy and compute overlap: the wall clock
-    is the caller's to take)."""
+    is the caller's to take).
+    video_allow: DEVICE-resident allow words (pack_video_allow), 1 row or one per query of the whole set; every chunk uses
+    its own rows.  Not with pad_tail=True."""
     from .results import MOMENT_DTYPE
     import time as _time
     t_enter = _time.perf_counter()
     dev = next(model.parameters()).device
     ragged = row_start is not None
     nq = (row_start.numel() - 1) if ragged else query_feat.shape[0]
+    if video_allow is not None:
+        if pad_tail:
+            raise ValueError("video_allow and pad_tail=True exclude each other (see vcmr_search)")
+        _check_video_allow(video_allow, index, nq)
+        if not video_allow.is_cuda:
+            raise ValueError("vcmr_search_host: video_allow must already be on the device (a mask is part of the request's "
+                             "state, not of the query stream)")
     d_in = query_feat.shape[-1]
     lq = int(lq if lq is not None else (model.config.max_desc_l if ragged else query_feat.shape[1]))
     width = int(max_before_nms)
@@ -1014,7 +1093,10 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
             done = evt()
             done.record(main)                            # the staging set is free once the query encoder has read it
             freed[c & 1] = done
-            _, tw, ti, _ = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops)
+            akw = {}
+            if video_allow is not None:
+                akw = dict(video_allow=video_allow if video_allow.shape[0] == 1 else video_allow[b:e])
+            _, tw, ti, _ = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, **akw)
             qvecs.append(qvec), tws.append(tw), tis.append(ti)
         one = len(bounds) == 1
         qvec = {m: (qvecs[0][m] if one else torch.cat([q[m] for q in qvecs])) for m in qvecs[0]}
@@ -1056,7 +1138,13 @@ class GraphedVcmrSearch(object):
     two eager warm-up passes before the capture; the corpus index and the model weights must not be re-allocated
     afterwards (re-create the object after load_state_dict / an optimizer step)."""
 
-    def __init__(self, model, index, nq, lq, d_in, **search_kwargs):
+    def __init__(self, model, index, nq, lq, d_in, video_allow_rows=None, **search_kwargs):
+        """video_allow_rows = None | 1 | nq: a restricted search -- a static (rows, ceil(Nv / 32)) allow-word buffer (all videos
+        allowed until a call passes a mask) is part of the captured pass; __call__(..., video_allow=) copies into it."""
+        if video_allow_rows not in (None, 1, nq):
+            raise ValueError("GraphedVcmrSearch: video_allow_rows must be None, 1 or nq = %d, got %r" % (nq, video_allow_rows))
+        if "video_allow" in search_kwargs:
+            raise ValueError("GraphedVcmrSearch: pass video_allow_rows= here and the mask itself to every call")
         if index.exact is not None and index.exact.mode != "f16s":
             raise ValueError("the f32 exact-rank mode reads its certificate on the host (the fallback's launch shape "
                              "depends on it): not capturable -- build the index from an ops.F16S model")
@@ -1068,6 +1156,10 @@ class GraphedVcmrSearch(object):
         self.query_feat = torch.zeros((nq, lq, d_in), dtype=torch.float32, device=dev)
         self.query_mask = torch.zeros((nq, lq), dtype=torch.float32, device=dev)
         self.query_mask[:, 0] = 1.0
+        self.video_allow = None
+        if video_allow_rows is not None:
+            self.video_allow = torch.full((video_allow_rows, (index.n_videos + 31) // 32), -1, dtype=torch.int32, device=dev)
+            search_kwargs["video_allow"] = self.video_allow
         self._args = (model, index)
         self._kw = search_kwargs
         # the packed-token query encoder (large batches) reads its plan back on the host and launches shapes that depend on
@@ -1089,11 +1181,20 @@ class GraphedVcmrSearch(object):
         finally:
             model_xml.PACK_QUERY_TOKENS = pack_was
 
-    def __call__(self, query_feat, query_mask):
+    def __call__(self, query_feat, query_mask, video_allow=None):
         if tuple(query_feat.shape) != tuple(self.query_feat.shape) or tuple(query_mask.shape) != tuple(self.query_mask.shape):
             raise ValueError("GraphedVcmrSearch was captured for queries %s / masks %s, got %s / %s"
                              % (tuple(self.query_feat.shape), tuple(self.query_mask.shape), tuple(query_feat.shape),
                                 tuple(query_mask.shape)))
+        if video_allow is not None:
+            if self.video_allow is None:
+                raise ValueError("GraphedVcmrSearch was captured without a video mask (video_allow_rows=None)")
+            if tuple(video_allow.shape) != tuple(self.video_allow.shape) or video_allow.dtype != torch.int32:
+                raise ValueError("GraphedVcmrSearch was captured for an int32 video mask of shape %s, got %s %s"
+                                 % (tuple(self.video_allow.shape), video_allow.dtype, tuple(video_allow.shape)))
+            self.video_allow.copy_(video_allow)
+        elif self.video_allow is not None:
+            self.video_allow.fill_(-1)          # no mask for this call: every video allowed
         self.query_feat.copy_(query_feat)
         self.query_mask.copy_(query_mask)
         self.graph.replay()

@@ -697,17 +697,51 @@ def q2c_scores_fused(qn, cn, masks, out=None, normalize_q=False):
     return out
 
 
-def topk_rows(scores, k, alpha=0.0, idx_in=None):
-    """K8.  scores (rows, n) f32 -> (values (rows, k) f32 [exp(alpha*s) if alpha], indices (rows, k) int32)."""
+def _allow_args(allow, col0, rows, n, device, what):
+    """Validate an allow-bit matrix (inference.pack_video_allow's layout) against a (rows, n) score matrix."""
+    if not torch.is_tensor(allow) or allow.dtype != torch.int32:
+        raise ValueError("%s: allow must be an int32 tensor of bit words (inference.pack_video_allow), got %s"
+                         % (what, getattr(allow, "dtype", type(allow).__name__)))
+    if allow.device != device:
+        raise ValueError("%s: allow is on %s, the scores are on %s" % (what, allow.device, device))
+    col0 = int(col0)
+    if col0 < 0:
+        raise ValueError("%s: col0 must be >= 0, got %d" % (what, col0))
+    need = (col0 + n + 31) // 32
+    if allow.dim() != 2 or allow.shape[1] < need:
+        raise ValueError("%s: allow must be (R, >= %d) words for columns %d .. %d, got %s"
+                         % (what, need, col0, col0 + n - 1, tuple(allow.shape)))
+    if allow.shape[0] not in (1, rows):
+        raise ValueError("%s: allow has %d rows; 1 (shared) or %d (one per score row) expected" % (what, allow.shape[0], rows))
+    if allow.stride(1) != 1 or allow.stride(0) < allow.shape[1]:
+        allow = allow.contiguous()
+    return allow, col0
+
+
+def topk_rows(scores, k, alpha=0.0, idx_in=None, allow=None, col0=0, return_count=False):
+    """K8.  scores (rows, n) f32 -> (values (rows, k) f32 [exp(alpha*s) if alpha], indices (rows, k) int32).
+    allow (1 | rows, >= ceil((col0 + n) / 32)) int32 bit words: the top-k of each row's ALLOWED columns only (column c needs
+    bit col0 + c); rows with fewer than k allowed columns end in empty slots (index -1, value 0, or -inf when alpha == 0).
+    return_count=True: additionally counts (rows,) int32 = min(k, allowed columns)."""
     _req(scores, "scores", torch.float32)
     rows, n = scores.shape
     if idx_in is not None:
         _req(idx_in, "idx_in", torch.int32)
         assert idx_in.shape == scores.shape
+    if allow is None and (col0 or return_count):
+        raise ValueError("topk_rows: col0 / return_count belong to allow=")
+    if allow is not None:
+        allow, col0 = _allow_args(allow, col0, rows, n, scores.device, "topk_rows")
     vals = torch.empty((rows, k), dtype=torch.float32, device=scores.device)
     idx = torch.empty((rows, k), dtype=torch.int32, device=scores.device)
     lib = _lib.load()
     ws = _workspace(lib.xml_topk_rows_workspace_bytes(rows, n, k), scores.device)      # header contract: caller's scratch
+    if allow is not None:
+        cnt = torch.empty((rows,), dtype=torch.int32, device=scores.device) if return_count else None
+        check(lib.xml_topk_rows_allowed(_p(scores), scores.stride(0), _p(idx_in), _p(allow), allow.stride(0), allow.shape[0],
+                                        col0, _p(vals), _p(idx), _p(cnt), rows, n, k, float(alpha), _p(ws), ws.numel(),
+                                        _stream()), "xml_topk_rows_allowed")
+        return (vals, idx, cnt) if return_count else (vals, idx)
     check(lib.xml_topk_rows(_p(scores), scores.stride(0), _p(idx_in), _p(vals), _p(idx), rows, n, k,
                             float(alpha), _p(ws), ws.numel(), _stream()), "xml_topk_rows")
     return vals, idx
@@ -1029,17 +1063,27 @@ def modular_pool_varlen(enc, cu_seqlens, n, max_len, w_m, return_att=False):
     return out
 
 
-def select_ge_rows(scores, thr, cap=None):
+def select_ge_rows(scores, thr, cap=None, allow=None, col0=0):
     """Columns of every row of scores (rows, n) f32 that reach thr (rows,) f32.  cap None -> counts (rows,) int32;
-    else -> (idx (rows, cap) int32 filled with -1 beyond each row's count, counts)."""
+    else -> (idx (rows, cap) int32 filled with -1 beyond each row's count, counts).
+    allow / col0 (as in topk_rows): only allowed columns are selected or counted."""
     _req(scores, "scores", torch.float32); _req(thr, "thr", torch.float32)
     rows, n = scores.shape
+    if allow is None and col0:
+        raise ValueError("select_ge_rows: col0 belongs to allow=")
+    if allow is not None:
+        allow, col0 = _allow_args(allow, col0, rows, n, scores.device, "select_ge_rows")
     cnt = torch.empty((rows,), dtype=torch.int32, device=scores.device)
     idx = None
     if cap is not None:
         idx = torch.full((rows, int(cap)), -1, dtype=torch.int32, device=scores.device)
-    check(_lib.load().xml_select_ge_rows(_p(scores), scores.stride(0), _p(thr), _p(idx), int(cap or 0), _p(cnt), rows, n,
-                                         _stream()), "xml_select_ge_rows")
+    if allow is not None:
+        check(_lib.load().xml_select_ge_rows_allowed(_p(scores), scores.stride(0), _p(thr), _p(allow), allow.stride(0),
+                                                     allow.shape[0], col0, _p(idx), int(cap or 0), _p(cnt), rows, n,
+                                                     _stream()), "xml_select_ge_rows_allowed")
+    else:
+        check(_lib.load().xml_select_ge_rows(_p(scores), scores.stride(0), _p(thr), _p(idx), int(cap or 0), _p(cnt), rows, n,
+                                             _stream()), "xml_select_ge_rows")
     return cnt if idx is None else (idx, cnt)
 
 
