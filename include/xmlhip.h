@@ -509,6 +509,35 @@ int xml_moments_decode(const int32_t* flat, const float* score, const int32_t* t
                        const int32_t* meta2vid, int nq, int n, int64_t ld_in, int k, int l_ref, float clip_length,
                        int seconds, xml_moment* out, int64_t ld_out, int32_t* out_count, xml_stream_t stream);
 
+/* K11: greedy temporal NMS of K10's records ON THE DEVICE -- the semantics of xml_nms_vcmr_host / xml_nms_svmr_host (below) on
+ * device-resident xml_moment rows, one more launch behind xml_moments_decode; the host entries stay the default path.
+ *   in   (nq, n) xml_moment, row stride ld_in >= n records, 16-byte aligned; row q holds count[q] valid records as a prefix
+ *        (count == NULL: the whole row).  Rows need not be sorted by score.
+ *   Input range: m = min(clamp(count[q], 0, n), max_before); only entries 0 .. m-1 take part.
+ *   Widening:    st_d = (double)st * scale, ed_d = (double)ed * scale (scale = 1.0 for VCMR records in seconds, clip_length for
+ *                SVMR records in clip units -- what MomentResults.from_records(scale=) does).
+ *   IoU:         inter = max(0, min(e0, e1) - max(s0, s1)), uni = max(e0, e1) - min(s0, s1) (the hull, as in the reference),
+ *                iou = uni == 0 ? 0 : inter / uni in float64 with one IEEE division; suppressed when iou > thd (strictly).
+ *   Groups:      by_video = 1: entries with equal vid form a group (filter_vcmr_by_nms); by_video = 0: the row is one group
+ *                (post_processing_svmr_nms).
+ *   In a group:  order by (score descending, position ascending); walk it: an entry not yet suppressed is kept and suppresses
+ *                every later unsuppressed entry of its group with iou > thd; at most 100 kept entries per group (the
+ *                reference's inner default cap).
+ *   Output:      the kept entries of all groups ordered by (score descending, first position of the entry's group ascending,
+ *                position ascending) -- the reference's "dict by first appearance, then stable sort by score" -- truncated to
+ *                max_after.
+ *   out_index (nq, ld_index >= max_after) int32: position in the input row of the r-th result, -1 for count <= r < max_after
+ *   out       (nq, ld_out >= max_after) xml_moment, 16-byte aligned: that input record, copied bitwise; {-1, 0, 0, 0} for
+ *             count <= r < max_after
+ *   out_count (nq) int32: the number of results.  Any of the three may be NULL, not all of them.
+ * 1 <= n <= 1024 (xml_moment_topk's n_out limit), max_before >= 0, max_after >= 0, thd and scale not NaN: XML_ERR_BAD_ARG
+ * otherwise, before any launch.  No workspace, no host synchronisation, no allocation; re-entrant per stream and capturable
+ * into a HIP graph.  The result equals the host entries' on the widened columns exactly: it is a selection and an order of
+ * existing records, decided by the same float64 operations on the same values. */
+int xml_nms_moments(const xml_moment* in, int64_t ld_in, const int32_t* count, int nq, int n, int by_video, double thd,
+                    double scale, int max_before, int max_after, xml_moment* out, int64_t ld_out, int32_t* out_index,
+                    int64_t ld_index, int32_t* out_count, xml_stream_t stream);
+
 /* Row-wise LayerNorm of (a [+ b]) -- exposed for the host-side mirror and tests.
  *   y = LN(a + b) * g + beta;  a,b,y (rows, d) dt (b may be NULL), x_dt of `a` may be XML_F32. */
 int xml_add_layernorm(const void* a, int a_dt, const void* b, const float* g, const float* beta,

@@ -4,6 +4,7 @@
 //              post_processing_svmr_nms           baselines/clip_alignment_with_language/inference.py:247-265
 // This runs on the host CPU on purpose: it is O(200^2) scalar work per query on lists that are already on the
 // host (the step after the all-gather); inputs are doubles because the reference operates on Python floats.
+// (Records that are still on the device go through nms.hip, xml_nms_moments: the same decisions, bit for bit.)
 // The *_batched entries take the (Nq, n) arrays the engine's K10 epilogue produces (one D2H per batch) and spread the
 // queries over host threads; the per-query entries are the same core on one row.
 #include <algorithm>

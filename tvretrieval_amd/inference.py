@@ -787,7 +787,8 @@ def stage_moments(model, index, qvec, top_w, top_i, min_pred_l=2, max_pred_l=16,
 
 def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_before_nms=200, q2c_alpha=20.0,
                 min_pred_l=2, max_pred_l=16, svmr_video=None, ops=hip_ops, external_top=None, pad_tail=False,
-                defer_exact_check=False, n_valid_tokens=None, video_allow=None):
+                defer_exact_check=False, n_valid_tokens=None, video_allow=None, nms_thd=None, max_after_nms=100,
+                meta2vid=None, clip_length=1.5):
     """Device part of compute_query2ctx_info for one query batch (xml/inference.py:308-386), single GPU.
 
     Returns device tensors:
@@ -801,7 +802,13 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     encoder of large batches then needs no read-back and the whole pass is enqueued without a host synchronisation.
     video_allow (pack_video_allow: (1 | Nq, ceil(Nv / 32)) int32 words on the device): the search restricted to each query's
     allowed videos -- exactly the unrestricted result on the corpus of those videos, in this index's numbering (see
-    stage_video_topk for queries with fewer than K allowed videos).  Not with external_top or pad_tail=True."""
+    stage_video_topk for queries with fewer than K allowed videos).  Not with external_top or pad_tail=True.
+    nms_thd (None: off): the search ends in the FINAL list on the device -- K10 (xml_moments_decode, meta2vid / clip_length as
+    in vcmr_search_host) and temporal NMS (xml_nms_moments) follow on the same stream.  out additionally holds records /
+    record_count (K10 of flat_scores / flat_indices: (Nq, n, 4) int32 xml_moment rows in seconds, (Nq,) int32) and nms_records
+    (Nq, max_after_nms, 4) / nms_index (Nq, max_after_nms) positions in `records` / nms_count (Nq,) = filter_vcmr_by_nms of
+    them; with svmr_video also svmr_records / svmr_record_count (clip units) and svmr_nms_records / svmr_nms_index /
+    svmr_nms_count = post_processing_svmr_nms on the spans scaled by clip_length in float64."""
     if video_allow is not None and pad_tail:
         raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
                          "rows in the empty video slots of a restricted list")
@@ -817,6 +824,11 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     out = dict(q2c=q2c, top_scores=top_w, top_indices=top_i, flat_scores=fs, flat_indices=fi)
     if exact is not None:
         out["exact"] = exact
+    if nms_thd is not None:
+        rec, cnt = ops.moments_decode(fs, flat=fi, top_idx=top_i, meta2vid=meta2vid, l_ref=index.l_ref,
+                                      clip_length=clip_length, seconds=True)
+        nrec, nidx, ncnt = ops.nms_moments(rec, cnt, True, nms_thd, max_before=max_before_nms, max_after=max_after_nms)
+        out.update(records=rec, record_count=cnt, nms_records=nrec, nms_index=nidx, nms_count=ncnt)
     if svmr_video is not None:
         pv = svmr_video.to(torch.int32).reshape(-1, 1).contiguous()
         st1, ed1 = stage_span_probs(model, index, qvec, pv, ops, q_lin=q_lin)
@@ -824,6 +836,13 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         if pad_tail:
             pad_moment_tail(ss, sf, 1, index.l_ref, min_pred_l, max_pred_l)
         out.update(svmr_scores=ss, svmr_flat=sf, svmr_st=st1[:, 0], svmr_ed=ed1[:, 0])
+        if nms_thd is not None:
+            rec, cnt = ops.moments_decode(ss, flat=sf, row_vid=pv.reshape(-1), meta2vid=meta2vid, l_ref=index.l_ref,
+                                          seconds=False)
+            nrec, nidx, ncnt = ops.nms_moments(rec, cnt, False, nms_thd, scale=clip_length, max_before=max_before_nms,
+                                               max_after=max_after_nms)
+            out.update(svmr_records=rec, svmr_record_count=cnt, svmr_nms_records=nrec, svmr_nms_index=nidx,
+                       svmr_nms_count=ncnt)
     return out
 
 
@@ -926,11 +945,18 @@ class HostSearchBuffers(object):
     """Pinned host memory + device staging of vcmr_search_host, allocated once and reused across calls (pinning a gigabyte of
     queries is a page-locking system call, not part of a search)."""
 
-    def __init__(self, n_queries, width, chunk, lq, d_in, ragged_rows, device, dtype):
-        self.rec = torch.empty((n_queries, width, 4), dtype=torch.int32, pin_memory=True)      # xml_moment records
+    def __init__(self, n_queries, width, chunk, lq, d_in, ragged_rows, device, dtype, nms_width=None):
+        """nms_width: the pass ends in temporal NMS on the device -- the pinned records and the device -> host copy have this
+        (max_after_nms) width; the pre-NMS records (width = max_before_nms) stay on the device."""
+        host_width = width if nms_width is None else nms_width
+        self.rec = torch.empty((n_queries, host_width, 4), dtype=torch.int32, pin_memory=True)      # xml_moment records
         self.cnt = torch.empty((n_queries,), dtype=torch.int32, pin_memory=True)
         self.rec_dev = torch.empty((n_queries, width, 4), dtype=torch.int32, device=device)
         self.cnt_dev = torch.zeros((n_queries,), dtype=torch.int32, device=device)
+        self.nms_dev = self.nms_cnt_dev = None
+        if nms_width is not None:
+            self.nms_dev = torch.empty((n_queries, nms_width, 4), dtype=torch.int32, device=device)
+            self.nms_cnt_dev = torch.zeros((n_queries,), dtype=torch.int32, device=device)
         # two staging sets: chunk c + 1 is copied in while chunk c is searched
         if ragged_rows:
             self.stage = [dict(rows=torch.empty((ragged_rows, d_in), dtype=dtype, device=device),
@@ -979,7 +1005,8 @@ def host_chunks(nq, first=1024, growth=3, largest=16384):
 
 def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, meta2vid=None, chunk=1024, lq=None,
                      clip_length=1.5, buffers=None, timings=None, ops=hip_ops, max_vcmr_video=100, max_before_nms=200,
-                     q2c_alpha=20.0, min_pred_l=2, max_pred_l=16, pad_tail=False, chunk_growth=3, wait=True, video_allow=None):
+                     q2c_alpha=20.0, min_pred_l=2, max_pred_l=16, pad_tail=False, chunk_growth=3, wait=True, video_allow=None,
+                     nms_thd=None, max_after_nms=100):
     """VCMR from host memory to host memory: the path of the reference's query loop (xml/inference.py:302-314 moves every
     batch host -> device, :383-386 moves the lists device -> host; start_end_dataset.py:362-370) for a whole query set.
 
@@ -1003,7 +1030,11 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     timings (dict, optional): h2d_s / device_s / decode_s / d2h_s from HIP events (copy and compute overlap: the wall clock
     is the caller's to take).
     video_allow: DEVICE-resident allow words (pack_video_allow), 1 row or one per query of the whole set; every chunk uses
-    its own rows.  Not with pad_tail=True."""
+    its own rows.  Not with pad_tail=True.
+    nms_thd (None: off, the records are the pre-NMS lists): temporal NMS per video (filter_vcmr_by_nms at this threshold, first
+    max_before_nms candidates in, at most max_after_nms out) runs on the device behind K10 (xml_nms_moments, same stream); the
+    pinned buffer and the device -> host copy then carry (Nq, max_after_nms) records -- the kept ones, best first, {-1, 0, 0, 0}
+    behind each row's count -- instead of (Nq, max_before_nms).  timings gains nms_s."""
     from .results import MOMENT_DTYPE
     import time as _time
     t_enter = _time.perf_counter()
@@ -1020,17 +1051,20 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     d_in = query_feat.shape[-1]
     lq = int(lq if lq is not None else (model.config.max_desc_l if ragged else query_feat.shape[1]))
     width = int(max_before_nms)
+    nms_width = None if nms_thd is None else max(int(max_after_nms), 1)
     bounds = host_chunks(nq, chunk, chunk_growth)
     rs_host = row_start.numpy() if ragged else None
     max_q = max(e - b for b, e in bounds)
     max_rows = max(int(rs_host[e] - rs_host[b]) for b, e in bounds) if ragged else 0
     if buffers is None:
         # kept on the index between calls: pinning host pages and mapping device memory are system calls, not search time
-        key = (nq, width, max_q, lq, d_in, max_rows, str(dev), query_feat.dtype)
+        key = (nq, width, max_q, lq, d_in, max_rows, str(dev), query_feat.dtype) + (() if nms_width is None else (nms_width,))
         cache = index.__dict__.setdefault("_host_search_buffers", {})
         if key not in cache:
             cache.clear()
-            cache[key] = [[HostSearchBuffers(nq, width, max_q, lq, d_in, max_rows, dev, query_feat.dtype) for _ in range(2)], 0]
+            nkw = {} if nms_width is None else dict(nms_width=nms_width)
+            cache[key] = [[HostSearchBuffers(nq, width, max_q, lq, d_in, max_rows, dev, query_feat.dtype, **nkw)
+                           for _ in range(2)], 0]
         ring = cache[key]
         buffers = ring[0][ring[1]]
         ring[1] ^= 1
@@ -1108,12 +1142,21 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
         ops.moments_decode(fs, flat=fi, top_idx=top_i, meta2vid=meta2vid, l_ref=index.l_ref, clip_length=clip_length,
                            seconds=True, out=buffers.rec_dev, out_count=buffers.cnt_dev)
         t2.record(main)
+        rec_src, cnt_src, t_out = buffers.rec_dev, buffers.cnt_dev, t2
+        if nms_thd is not None:
+            if buffers.nms_dev is None or buffers.nms_dev.shape[1] != nms_width:
+                raise ValueError("vcmr_search_host: buffers were not made for nms_width = %d" % nms_width)
+            ops.nms_moments(buffers.rec_dev, buffers.cnt_dev, True, nms_thd, max_before=max_before_nms,
+                            max_after=max_after_nms, want_index=False, out=buffers.nms_dev, out_count=buffers.nms_cnt_dev)
+            t_out = evt()
+            t_out.record(main)
+            rec_src, cnt_src = buffers.nms_dev, buffers.nms_cnt_dev
         back = buffers.back_stream                       # the records leave on their own stream: `main` is free for the next pass
-        back.wait_event(t2)
+        back.wait_event(t_out)
         with torch.cuda.stream(back):
             t2b.record(back)
-            buffers.rec.copy_(buffers.rec_dev, non_blocking=True)
-            buffers.cnt.copy_(buffers.cnt_dev, non_blocking=True)
+            buffers.rec.copy_(rec_src, non_blocking=True)
+            buffers.cnt.copy_(cnt_src, non_blocking=True)
             t3.record(back)
         buffers.last_done = t3
     t_enq = _time.perf_counter()
@@ -1124,6 +1167,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
                        h2d_exposed_s=ev_h2d[0][0].elapsed_time(ev_h2d[0][1]) * 1e-3,
                        device_s=t_first.elapsed_time(t1) * 1e-3, decode_s=t1.elapsed_time(t2) * 1e-3,
                        d2h_s=t2b.elapsed_time(t3) * 1e-3, chunks=len(bounds), chunk_queries=[e - b for b, e in bounds])
+        if nms_thd is not None:
+            timings.update(nms_s=t2.elapsed_time(t_out) * 1e-3)
     pending = PendingHostSearch(buffers, t3, fill if timings is not None else None)
     return pending.result() if wait else pending
 
@@ -1271,10 +1316,34 @@ class _ResultSink(object):
         self.rec = torch.empty((n_queries, width, 4), dtype=torch.int32, device=device)
         self.cnt = torch.zeros((n_queries,), dtype=torch.int32, device=device)
         self.n = 0
+        self.nms_scale = 1.0         # float64 factor on st / ed in front of NMS (SVMR records are in clip units)
 
     def rows(self, b, nb):
         self.n = max(self.n, b + nb)
         return dict(out=self.rec[b:b + nb], out_count=self.cnt[b:b + nb])
+
+    def nms(self, task, opt, max_after_nms):
+        """opt.nms_on_device: ONE xml_nms_moments launch over the whole buffer; the kept records stay on the device until
+        fetch_nms.  The reference quirk of eval_epoch is kept: unless opt.nms_on_full_lists is set, NMS sees only the first
+        max_after_nms candidates of a list (get_submission_top_n has truncated it in place by then)."""
+        max_before = int(opt.max_before_nms)
+        if not getattr(opt, "nms_on_full_lists", False):
+            max_before = min(max_before, int(max_after_nms))
+        n = self.n
+        self.kept_rec, _, self.kept_cnt = hip_ops.nms_moments(
+            self.rec[:n], self.cnt[:n], task == "VCMR", opt.nms_thd, scale=self.nms_scale,
+            max_before=min(max_before, self.rec.shape[1]), max_after=max_after_nms, want_index=False)
+
+    def fetch_nms(self, desc_ids, descs):
+        """The kept lists as a MomentResults -- what MomentResults.take makes of the raw lists and host NMS's index lists
+        (zeros behind each row's count), without the gather on the host: the device has copied the records."""
+        from .results import MOMENT_DTYPE, MomentResults
+        n = self.n
+        rec = self.kept_rec.cpu().numpy().view(MOMENT_DTYPE)[..., 0]
+        cnt = self.kept_cnt.cpu().numpy()
+        res = MomentResults.from_records(desc_ids[:n], descs[:n], rec, cnt, scale=None if self.nms_scale == 1.0 else self.nms_scale)
+        res.vid[np.arange(res.width)[None, :] >= cnt[:, None]] = 0
+        return res
 
     def fetch(self, desc_ids, descs, scale=None, int_spans=False):
         from .results import MOMENT_DTYPE, MomentResults
@@ -1284,8 +1353,12 @@ class _ResultSink(object):
                                           int_spans=int_spans)
 
 
+def _nms_on_device(opt):
+    return bool(getattr(opt, "nms_on_device", False)) and getattr(opt, "nms_thd", -1) != -1
+
+
 def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=1000, max_n_videos=100,
-                           tasks=("SVMR",), ops=hip_ops, as_arrays=False):
+                           tasks=("SVMR",), ops=hip_ops, as_arrays=False, max_after_nms=100):
     """Mirror of compute_query2ctx_info (xml/inference.py:252-445).  Same result dict:
     {"VCMR"|"SVMR"|"VR": [dict(desc_id, desc, predictions=[[video_idx, st, ed, score], ...]), ...]}.
     opt.external_inference_vr_res_path (xml/inference.py:264-273,349-355): re-rank the videos of another model's VR
@@ -1294,7 +1367,10 @@ def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=10
     where fewer candidates exist -- instead of the positive-score prefix.
     as_arrays=True: each task as a results.MomentResults (the (Nq, n) columns K10 produced) instead of nested lists; the
     reference's "numpy tail" (:391-445) is the device epilogue xml_moments_decode either way -- the lists, when asked for,
-    are built from the columns in one C call (results.MomentResults.to_list)."""
+    are built from the columns in one C call (results.MomentResults.to_list).
+    opt.nms_on_device=True with opt.nms_thd != -1 (not reference options): temporal NMS runs on the device, one launch per
+    task over the whole result buffer after the last batch; the kept lists (at most max_after_nms entries each) come back next
+    to the raw ones as "VCMR_nms" / "SVMR_nms" -- what post_processing_{vcmr,svmr}_nms makes of the raw lists in eval_epoch."""
     is_svmr, is_vr, is_vcmr = "SVMR" in tasks, "VR" in tasks, "VCMR" in tasks
     index = ctx_info["index"]
     video2idx = eval_dataset.video2idx
@@ -1400,10 +1476,21 @@ def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=10
                 gt = torch.tensor([name2meta[e["meta"]["vid_name"]] for e in items], dtype=torch.int32, device=opt.device)
             emit(vcmr_search(model, index, qf, qm, svmr_video=gt, **search_kw), b, len(items), gt)
     res = {}
+    kept = {}
+    if _nms_on_device(opt):         # enqueued before the first fetch
+        if is_svmr:
+            sink_svmr.nms_scale = float(clip)
+            kept["SVMR"] = sink_svmr
+        if is_vcmr:
+            kept["VCMR"] = sink_vcmr
+        for k, sink in kept.items():
+            sink.nms(k, opt, max_after_nms)
     if is_svmr:
         res["SVMR"] = sink_svmr.fetch(desc_ids, descs, scale=clip)
     if is_vcmr:
         res["VCMR"] = sink_vcmr.fetch(desc_ids, descs)
+    for k, sink in kept.items():
+        res[k + "_nms"] = sink.fetch_nms(desc_ids, descs)
     if is_vr and sink_vr is not None:
         res["VR"] = sink_vr.fetch(desc_ids, descs, int_spans=True)
     res = {k: v for k, v in res.items() if len(v) != 0}
@@ -1414,7 +1501,7 @@ def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=10
 
 
 def compute_query2ctx_info_svmr_only(model, eval_dataset, opt, ctx_info, max_before_nms=1000, max_n_videos=200,
-                                     tasks=("SVMR",), ops=hip_ops, as_arrays=False):
+                                     tasks=("SVMR",), ops=hip_ops, as_arrays=False, max_after_nms=100):
     """Mirror of compute_query2ctx_info_svmr_only (xml/inference.py:107-167): every query is scored against its
     ground-truth video only (K7 with one pair per query + K9 with k = 1); no corpus-wide similarity."""
     index = ctx_info["index"]
@@ -1443,8 +1530,14 @@ def compute_query2ctx_info_svmr_only(model, eval_dataset, opt, ctx_info, max_bef
         ops.moments_decode(ss, flat=sf, row_vid=gt, meta2vid=meta2vid, l_ref=l_ref, seconds=False, **sink.rows(b, len(metas)))
         if getattr(opt, "debug", False):
             break
+    if _nms_on_device(opt):         # (see compute_query2ctx_info)
+        sink.nms_scale = float(clip)
+        sink.nms("SVMR", opt, max_after_nms)
     res = sink.fetch(desc_ids, descs, scale=clip)
-    return dict(SVMR=res if as_arrays else res.to_list())
+    out = dict(SVMR=res)
+    if _nms_on_device(opt):
+        out["SVMR_nms"] = sink.fetch_nms(desc_ids, descs)
+    return out if as_arrays else {k: v.to_list() for k, v in out.items()}
 
 
 def get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=hip_ops, as_arrays=False):
@@ -1452,11 +1545,12 @@ def get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=hip_ops, as
     context_info = compute_context_info(model, eval_dataset, opt, ops=ops)
     if "VCMR" in tasks or "VR" in tasks:
         eval_res = compute_query2ctx_info(model, eval_dataset, opt, context_info, max_before_nms=opt.max_before_nms,
-                                          max_n_videos=opt.max_vcmr_video, tasks=tasks, ops=ops, as_arrays=as_arrays)
+                                          max_n_videos=opt.max_vcmr_video, tasks=tasks, ops=ops, as_arrays=as_arrays,
+                                          max_after_nms=max_after_nms)
     else:
         eval_res = compute_query2ctx_info_svmr_only(model, eval_dataset, opt, context_info,
                                                     max_before_nms=opt.max_before_nms, max_n_videos=max_after_nms,
-                                                    tasks=tasks, ops=ops, as_arrays=as_arrays)
+                                                    tasks=tasks, ops=ops, as_arrays=as_arrays, max_after_nms=max_after_nms)
     eval_res["video2idx"] = eval_dataset.video2idx
     return eval_res
 
@@ -1476,7 +1570,10 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
     Reference quirk kept on purpose: get_submission_top_n truncates the RAW lists in place (clip_alignment_with_language/
     inference.py:503-515), so the NMS stage (xml/inference.py:507-515) only ever sees the first max_after_nms (100)
     candidates, not max_before_nms, and the after-NMS metrics are computed with eval_retrieval's default
-    use_desc_type=True.  opt.nms_on_full_lists=True runs NMS on the untruncated lists instead (not the reference)."""
+    use_desc_type=True.  opt.nms_on_full_lists=True runs NMS on the untruncated lists instead (not the reference).
+    opt.nms_on_device=True (not a reference option; host NMS is the default): the after-NMS lists come from xml_nms_moments on
+    the device-resident records (compute_query2ctx_info) instead of post_processing_*_nms on the fetched arrays -- the same
+    lists, entry for entry."""
     import time
     from . import evaluate, postproc
     from .results import to_lists
@@ -1490,12 +1587,16 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
         raw = get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=ops, as_arrays=True)
     elif "VCMR" in tasks or "VR" in tasks:
         raw = compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=opt.max_before_nms,
-                                     max_n_videos=opt.max_vcmr_video, tasks=tasks, ops=ops, as_arrays=True)
+                                     max_n_videos=opt.max_vcmr_video, tasks=tasks, ops=ops, as_arrays=True,
+                                     max_after_nms=max_after_nms)
         raw["video2idx"] = eval_dataset.video2idx
     else:
         raw = compute_query2ctx_info_svmr_only(model, eval_dataset, opt, ctx_info, max_before_nms=opt.max_before_nms,
-                                               max_n_videos=max_after_nms, tasks=tasks, ops=ops, as_arrays=True)
+                                               max_n_videos=max_after_nms, tasks=tasks, ops=ops, as_arrays=True,
+                                               max_after_nms=max_after_nms)
         raw["video2idx"] = eval_dataset.video2idx
+    # opt.nms_on_device: the kept lists were made on the device, next to the raw ones
+    dev_nms = {k[:-4]: raw.pop(k) for k in [k for k in raw if k.endswith("_nms")]}
     lap("search")
     full = None
     if getattr(opt, "nms_on_full_lists", False):
@@ -1514,7 +1615,9 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
     if getattr(opt, "nms_thd", -1) != -1:
         sub_nms = dict(video2idx=raw["video2idx"])
         for k, fn in (("SVMR", postproc.post_processing_svmr_nms), ("VCMR", postproc.post_processing_vcmr_nms)):
-            if k in raw:
+            if k in dev_nms:
+                sub_nms[k] = dev_nms[k]
+            elif k in raw:
                 sub_nms[k] = fn(raw[k], nms_thd=opt.nms_thd, max_before_nms=opt.max_before_nms,
                                 max_after_nms=max_after_nms)         # (arrays in, new arrays out: nothing to deep-copy)
         lap("nms")

@@ -933,6 +933,52 @@ def moments_decode(scores, flat=None, top_idx=None, row_vid=None, meta2vid=None,
     return out, out_count
 
 
+def nms_moments(records, count, by_video, thd, scale=1.0, max_before=None, max_after=100, want_records=True,
+                want_index=True, out=None, out_index=None, out_count=None):
+    """K11: greedy temporal NMS of K10's records on the device (xml_nms_moments; the semantics of postproc.nms_batched).
+    records (Nq, n, 4) int32 = xml_moment rows (row stride >= n records: a view of a wider buffer is fine), count (Nq,) int32
+    valid prefix per row or None (whole rows); by_video: True = filter_vcmr_by_nms (NMS per video, merged by score), False =
+    post_processing_svmr_nms (the row is one video).  scale: float64 factor on st / ed (clip_length for records in clip units).
+    max_before (default n): only the first min(count, max_before) entries of a row take part.
+    -> (records (Nq, max_after, 4) int32 or None, index (Nq, max_after) int32 into each input row or None, count (Nq,) int32);
+    beyond a row's count the records are {-1, 0, 0, 0} and the indices -1.  out / out_index / out_count: destinations to use
+    instead of new tensors (rows of a larger buffer; at least max_after wide)."""
+    if not isinstance(records, torch.Tensor) or not records.is_cuda:
+        raise _lib.XmlHipError("records: tensor must live on the GPU; the HIP path has no CPU fallback")
+    if records.dtype != torch.int32 or records.dim() != 3 or records.shape[2] != 4 or records.stride(2) != 1 \
+            or records.stride(1) != 4 or records.stride(0) % 4 != 0:
+        raise _lib.XmlHipError("records: expected (Nq, n, 4) int32 xml_moment rows, got %s %s strides %s"
+                               % (records.dtype, tuple(records.shape), tuple(records.stride())))
+    nq, n = records.shape[0], records.shape[1]
+    if count is not None:
+        _req(count, "count", torch.int32)
+        assert count.numel() == nq
+    max_before = n if max_before is None else int(max_before)
+    max_after = int(max_after)
+    width = max(max_after, 1)
+    dev = records.device
+    if out is None and want_records:
+        out = torch.empty((nq, width, 4), dtype=torch.int32, device=dev)
+    if out_index is None and want_index:
+        out_index = torch.empty((nq, width), dtype=torch.int32, device=dev)
+    if out_count is None:
+        out_count = torch.empty((nq,), dtype=torch.int32, device=dev)
+    if out is not None:
+        assert out.is_cuda and out.dtype == torch.int32 and out.dim() == 3 and out.shape[0] == nq and out.shape[2] == 4 \
+            and out.stride(2) == 1 and out.stride(1) == 4 and out.stride(0) % 4 == 0 and out.shape[1] >= max_after
+    if out_index is not None:
+        assert out_index.is_cuda and out_index.dtype == torch.int32 and out_index.dim() == 2 and out_index.shape[0] == nq \
+            and out_index.stride(1) == 1 and out_index.shape[1] >= max_after
+    assert out_count.is_cuda and out_count.dtype == torch.int32 and out_count.is_contiguous() and out_count.numel() == nq
+    if nq:
+        check(_lib.load().xml_nms_moments(_p(records), records.stride(0) // 4, _p(count), nq, n, 1 if by_video else 0,
+                                          float(thd), float(scale), max_before, max_after, _p(out),
+                                          out.stride(0) // 4 if out is not None else 0, _p(out_index),
+                                          out_index.stride(0) if out_index is not None else 0, _p(out_count), _stream()),
+              "xml_nms_moments")
+    return out, out_index, out_count
+
+
 # ---- exact-rank mode (bf16 K6 as a filter in front of f32 scores; include/xmlhip.h "Exact-rank mode") --------------------
 def round_bf16_rows_err(y):
     """y (..., d) f32 L2-normalised rows -> (yb bf16 = rne(y), err (...) f32 = ||y - yb||_2 per row)."""

@@ -77,6 +77,18 @@ def nms_batched(res, task, nms_thd, max_before_nms=1000, max_after_nms=100, n_th
     return idx, cnt
 
 
+def nms_batched_device(records, count, task, nms_thd, max_before_nms=1000, max_after_nms=100, scale=None):
+    """nms_batched on the device: records (Nq, n, 4) int32 device tensor of K10's xml_moment rows, count (Nq,) int32 device
+    tensor (or None: whole rows) -> (index (Nq, max(max_after, 1)) int32, count (Nq,) int32) as numpy arrays, ready for
+    MomentResults.take on the fetched records.  ONE xml_nms_moments launch (ops.nms_moments) and a D2H of the index lists.
+    task "VCMR": NMS per video; "SVMR": the row is one video and scale = clip_length widens its clip units to seconds."""
+    from . import ops
+    _, idx, cnt = ops.nms_moments(records, count, task == "VCMR", nms_thd, scale=1.0 if scale is None else scale,
+                                  max_before=min(int(max_before_nms), records.shape[1]), max_after=max_after_nms,
+                                  want_records=False)
+    return idx.cpu().numpy(), cnt.cpu().numpy()
+
+
 def _post_nms(task_res, task, nms_thd, max_before_nms, max_after_nms):
     from .results import MomentResults
     if isinstance(task_res, MomentResults):         # the engine's arrays: stays arrays
