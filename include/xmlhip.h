@@ -538,6 +538,39 @@ int xml_nms_moments(const xml_moment* in, int64_t ld_in, const int32_t* count, i
                     double scale, int max_before, int max_after, xml_moment* out, int64_t ld_out, int32_t* out_index,
                     int64_t ld_index, int32_t* out_count, xml_stream_t stream);
 
+/* K12: the retrieval metrics of K10 / K11 records ON THE DEVICE -- eval_by_task_type (standalone_eval/eval.py:83-276) on
+ * device-resident xml_moment rows and a device-resident ground truth; the result is the recall COUNTERS, so nothing but a few
+ * integers has to leave the device.  The host evaluator (tvretrieval_amd/evaluate.py) stays the default path.
+ *   rec   (nq, n) xml_moment, row stride ld_rec >= n records, 16-byte aligned; row q takes part with its first
+ *         m = min(clamp(count[q], 0, n), max_pred) records (count == NULL: n)
+ *   task  0 VCMR, 1 SVMR, 2 VR
+ *   Ground truth, one row per query row: gt_vid (nq) int32; gt_ts (nq, n_ts, 2) f32 [st, ed]; n_gt (nq) int32: 0 = the row has
+ *         no ground truth and is counted nowhere (match_number=False on an id the ground truth lacks), >= 4 = a DiDeMo row with
+ *         that many spans (at most n_ts), anything else = one span gt_ts[q, 0]; desc_type (nq) int32 in {0 v, 1 t, 2 vt} or
+ *         NULL (groups 1-3 stay zero)
+ *   iou_thd (n_thd) f32 and topk (n_k) int32 are HOST arrays, read at call time (they travel as kernel arguments)
+ *   Arithmetic: f32, as numpy does it on the host's array of predictions.  st = (float)((double)rec.st * scale), ed likewise
+ *         (scale = 1.0 for records in seconds, clip_length for SVMR records in clip units: MomentResults.from_records(scale=)
+ *         and the cast that follows); inter = max(0, min(ed, g_ed) - max(st, g_st)); uni = max(ed, g_ed) - min(st, g_st) (the
+ *         hull); iou = uni != 0 ? inter / uni : 0 with one correctly rounded division, times the 0/1 video match
+ *         rec.vid == gt_vid[q]; a span hits when iou >= iou_thd[t] (NaN: no hit); min / max propagate NaN like numpy's
+ *   A prediction is correct when its span hits (one-span rows), when >= 2 of the row's spans hit (DiDeMo rows), or, for VR,
+ *         when the video matches: VR uses the ground truth for the skip rule only and n_thd counts as 1 (first_hit is (nq, 1),
+ *         hits (4, 1, n_k); iou_thd may be NULL)
+ *   first_hit (nq, n_thd) int32: 1-based, 0 = none.  VCMR / VR: the position of the first correct prediction; SVMR: its rank
+ *         among the row's predictions whose video matches (the reference's "first k predictions of the ground-truth video")
+ *   hits (4, n_thd, n_k) int32: counted rows with 1 <= first_hit[q, t] <= topk[k]; group 0 = all rows, group 1 + desc_type =
+ *         the rows of that type; rows (4) int32: the denominators.  Both are OVERWRITTEN (by kernels: a replayed graph gets
+ *         fresh counters); recall = hits / rows.
+ * 1 <= n <= 1024, 1 <= n_thd <= 4, 1 <= n_k <= 8 with topk positive and strictly ascending, 1 <= n_ts <= 16, max_pred >= 0,
+ * scale not NaN, task in 0..2: XML_ERR_BAD_ARG otherwise, before any launch.  nq == 0: returns 0, launches nothing, leaves the
+ * outputs untouched.  No workspace, no allocation, no host synchronisation; re-entrant per stream and capturable.  The counters
+ * are integers: exact, and independent of execution order. */
+int xml_eval_moments(const xml_moment* rec, int64_t ld_rec, const int32_t* count, int nq, int n, int task, double scale,
+                     int max_pred, const int32_t* gt_vid, const float* gt_ts, int n_ts, const int32_t* n_gt,
+                     const int32_t* desc_type, const float* iou_thd, int n_thd, const int32_t* topk, int n_k,
+                     int32_t* first_hit, int32_t* hits, int32_t* rows, xml_stream_t stream);
+
 /* Row-wise LayerNorm of (a [+ b]) -- exposed for the host-side mirror and tests.
  *   y = LN(a + b) * g + beta;  a,b,y (rows, d) dt (b may be NULL), x_dt of `a` may be XML_F32. */
 int xml_add_layernorm(const void* a, int a_dt, const void* b, const float* g, const float* beta,

@@ -136,6 +136,9 @@ SIGNATURES = {
                                    c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "xml_nms_moments": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int,
                                 c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "xml_eval_moments": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,
+                                 c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
     "xml_add_layernorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                   c_void_p]),
     # ---- multi-GPU collectives (collectives.hip) ----

@@ -162,3 +162,127 @@ def eval_retrieval(submission, ground_truth, iou_thds=(0.5, 0.7), verbose=True, 
         for t in tasks:
             out[t + "_by_type"] = raw[t + "_by_type"]
     return out
+
+
+# ---- the same metrics from the device's counters (xml_eval_moments, ops.eval_moments; include/xmlhip.h K12) ----------------
+class DeviceGroundTruth(object):
+    """The ground truth of one evaluation run as the five device operands of xml_eval_moments, one row per entry of `desc_ids`
+    -- the rows of the result sinks, in their order.  Built once per run; every task and both metric sets share it.
+    gt_vid (n,) int32, gt_ts (n, n_ts, 2) f32, n_gt (n,) int32, desc_type (n,) int32 or None (use_desc_type=False).
+    DiDeMo entries (>= 4 spans) as in _ground_truth_arrays; ids the ground truth lacks get n_gt = 0 and are counted nowhere
+    (match_number=False); with match_number=True the two id sets must be equal, as on the host.  A desc_id listed twice is
+    evaluated on its last row, like the host's dict of predictions."""
+
+    def __init__(self, ground_truth, video2idx, desc_ids, device, use_desc_type=True, match_number=True):
+        import torch
+        gt_by_id = {e["desc_id"]: e for e in ground_truth}
+        desc_ids = list(desc_ids)
+        last_row = {d: i for i, d in enumerate(desc_ids)}
+        if match_number:
+            assert set(gt_by_id.keys()) == set(last_row.keys()), "desc_ids in predictions and ground_truth must match"
+        n = len(desc_ids)
+        n_ts = max([len(g["ts"]) if len(g["ts"]) >= 4 else 1 for d, g in gt_by_id.items() if d in last_row] or [1])
+        gt_vid = np.zeros(n, dtype=np.int32)
+        desc_types = np.zeros(n, dtype=np.int32)
+        gt_ts = np.zeros((n, n_ts, 2), dtype=np.float32)
+        n_gt = np.zeros(n, dtype=np.int32)
+        for i, d in enumerate(desc_ids):
+            g = gt_by_id.get(d)
+            if g is None or last_row[d] != i:
+                continue
+            gt_vid[i] = video2idx[g["vid_name"]]
+            if use_desc_type:
+                desc_types[i] = DESC_TYPE2IDX[g["type"]]
+            if len(g["ts"]) >= 4:                                   # didemo: list of [st, ed]
+                ts = np.asarray(g["ts"], dtype=np.float32)
+                gt_ts[i, :len(ts)] = ts
+                n_gt[i] = len(ts)
+            else:
+                gt_ts[i, 0] = np.asarray(g["ts"], dtype=np.float32)
+                n_gt[i] = 1
+        self.n, self.n_ts, self.use_desc_type = n, n_ts, bool(use_desc_type)
+        self.gt_vid = torch.from_numpy(gt_vid).to(device)
+        self.gt_ts = torch.from_numpy(gt_ts).to(device)
+        self.n_gt = torch.from_numpy(n_gt).to(device)
+        self.desc_type = torch.from_numpy(desc_types).to(device) if use_desc_type else None
+
+    def without_desc_type(self):
+        """The same operands for a call with use_desc_type=False (groups 1-3 of the counters stay zero)."""
+        import copy
+        g = copy.copy(self)
+        g.desc_type, g.use_desc_type = None, False
+        return g
+
+
+def records_from_results(res):
+    """A MomentResults as xml_moment records: ((Nq, width, 4) int32, (Nq,) int32 counts).  st / ed are rounded to f32 -- the
+    cast the host evaluator applies to them -- so the device evaluates these records with scale = 1.0."""
+    from .results import MOMENT_DTYPE
+    w = int(res.width)
+    rec = np.zeros((len(res.count), max(w, 1)), dtype=MOMENT_DTYPE)
+    for name in ("vid", "st", "ed", "score"):
+        rec[name][:, :w] = getattr(res, name)
+    return rec.view(np.int32).reshape(rec.shape[0], rec.shape[1], 4), np.asarray(res.count).astype(np.int32)
+
+
+def metrics_from_hits(hits, rows, task, iou_thds=(0.5, 0.7), topks=(1, 5, 10, 100), use_desc_type=True,
+                      desc_type_ratio_rows=None):
+    """(metrics, metrics_by_type) of eval_by_task_type from xml_eval_moments' counters: hits (4, n_thd, n_k), rows (4,) --
+    the same keys in the same order, the same get_rounded_percentage(count / rows) in float64 (NaN where a description type
+    has no row).  desc_type_ratio_rows: the (4,) row counts behind "desc_type_ratio" when they are not `rows`."""
+    assert task in TASK_TYPES
+    hits = np.asarray(hits).astype(np.int64).reshape(4, -1, len(topks))
+    rows = np.asarray(rows).astype(np.int64).reshape(4)
+    ratio_rows = rows if desc_type_ratio_rows is None else np.asarray(desc_type_ratio_rows).astype(np.int64).reshape(4)
+    metrics, metrics_by_type = OrderedDict(), OrderedDict()
+
+    def pct(count, total):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return get_rounded_percentage(np.float64(count) / np.float64(total))
+
+    def fill(out, g, prefix):
+        if task == "VR":
+            for ki, k in enumerate(topks):
+                out["{}r{}".format(prefix, k)] = pct(hits[g, 0, ki], rows[g])
+        else:
+            for ti, thd in enumerate(iou_thds):
+                for ki, k in enumerate(topks):
+                    out["{}{}-r{}".format(prefix, thd, k)] = pct(hits[g, ti, ki], rows[g])
+    fill(metrics, 0, "")
+    if use_desc_type:
+        for dt, di in DESC_TYPE2IDX.items():
+            fill(metrics_by_type, 1 + di, dt + "-")
+        metrics_by_type["desc_type_ratio"] = "v {} t {} vt {}".format(
+            *[pct(ratio_rows[1 + DESC_TYPE2IDX[k]], ratio_rows[0]) for k in ["v", "t", "vt"]])
+    return metrics, metrics_by_type
+
+
+def eval_retrieval_device(records_by_task, gt, iou_thds=(0.5, 0.7), topks=(1, 5, 10, 100), max_pred=100,
+                          use_desc_type=True):
+    """eval_retrieval's dict from device-resident records: records_by_task maps "VCMR" / "SVMR" / "VR" to (records, count) or
+    (records, count, scale) as ops.eval_moments takes them, gt is the DeviceGroundTruth of the same rows.  One xml_eval_moments
+    call per task into one counter buffer, and ONE small copy to the host for all tasks together."""
+    import torch
+    from . import ops
+    tasks = [t for t in TASK_TYPES if t in records_by_task]
+    if use_desc_type and gt.desc_type is None:
+        raise ValueError("use_desc_type=True needs a DeviceGroundTruth built with use_desc_type=True")
+    g = gt if use_desc_type else gt.without_desc_type()
+    n_hits = 4 * len(iou_thds) * len(topks)
+    buf = torch.zeros((max(len(tasks), 1), n_hits + 4), dtype=torch.int32, device=gt.gt_vid.device)
+    for i, t in enumerate(tasks):
+        rec, count = records_by_task[t][0], records_by_task[t][1]
+        scale = records_by_task[t][2] if len(records_by_task[t]) > 2 else 1.0
+        used = 4 * (1 if t == "VR" else len(iou_thds)) * len(topks)
+        ops.eval_moments(rec, count, t, g, scale=scale, max_pred=max_pred, iou_thds=iou_thds, topks=topks,
+                         hits=buf[i, :used], rows=buf[i, n_hits:])
+    host = buf.cpu().numpy()
+    raw = {}
+    for i, t in enumerate(tasks):
+        used = 4 * (1 if t == "VR" else len(iou_thds)) * len(topks)
+        raw[t], raw[t + "_by_type"] = metrics_from_hits(host[i, :used], host[i, n_hits:], t, iou_thds, topks, use_desc_type)
+    out = OrderedDict((t, raw[t]) for t in tasks)
+    if use_desc_type:
+        for t in tasks:
+            out[t + "_by_type"] = raw[t + "_by_type"]
+    return out

@@ -1345,6 +1345,15 @@ class _ResultSink(object):
         res.vid[np.arange(res.width)[None, :] >= cnt[:, None]] = 0
         return res
 
+    def eval_raw(self, top_n):
+        """(records, count) of the raw lists as eval_epoch evaluates them: cut to the first top_n entries (a view)."""
+        n = self.n
+        return self.rec[:n, :max(min(int(top_n), self.rec.shape[1]), 1)], self.cnt[:n]
+
+    def eval_kept(self):
+        """(records, count, scale) of K11's kept lists."""
+        return self.kept_rec, self.kept_cnt, self.nms_scale
+
     def fetch(self, desc_ids, descs, scale=None, int_spans=False):
         from .results import MOMENT_DTYPE, MomentResults
         n = self.n
@@ -1358,7 +1367,7 @@ def _nms_on_device(opt):
 
 
 def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=1000, max_n_videos=100,
-                           tasks=("SVMR",), ops=hip_ops, as_arrays=False, max_after_nms=100):
+                           tasks=("SVMR",), ops=hip_ops, as_arrays=False, max_after_nms=100, _sinks=None):
     """Mirror of compute_query2ctx_info (xml/inference.py:252-445).  Same result dict:
     {"VCMR"|"SVMR"|"VR": [dict(desc_id, desc, predictions=[[video_idx, st, ed, score], ...]), ...]}.
     opt.external_inference_vr_res_path (xml/inference.py:264-273,349-355): re-rank the videos of another model's VR
@@ -1370,7 +1379,9 @@ def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=10
     are built from the columns in one C call (results.MomentResults.to_list).
     opt.nms_on_device=True with opt.nms_thd != -1 (not reference options): temporal NMS runs on the device, one launch per
     task over the whole result buffer after the last batch; the kept lists (at most max_after_nms entries each) come back next
-    to the raw ones as "VCMR_nms" / "SVMR_nms" -- what post_processing_{vcmr,svmr}_nms makes of the raw lists in eval_epoch."""
+    to the raw ones as "VCMR_nms" / "SVMR_nms" -- what post_processing_{vcmr,svmr}_nms makes of the raw lists in eval_epoch.
+    _sinks (eval_epoch's, for opt.eval_on_device): "also" adds the device-resident result buffers to the result under
+    "_sinks"; "only" returns nothing else -- no record buffer is fetched."""
     is_svmr, is_vr, is_vcmr = "SVMR" in tasks, "VR" in tasks, "VCMR" in tasks
     index = ctx_info["index"]
     video2idx = eval_dataset.video2idx
@@ -1485,6 +1496,13 @@ def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=10
             kept["VCMR"] = sink_vcmr
         for k, sink in kept.items():
             sink.nms(k, opt, max_after_nms)
+    handed = None
+    if _sinks is not None:
+        handed = dict(desc_ids=desc_ids, descs=descs, kept=kept, raw={
+            k: (s, sc) for k, s, sc in (("SVMR", sink_svmr, float(clip)), ("VCMR", sink_vcmr, 1.0), ("VR", sink_vr, 1.0))
+            if s is not None and s.n > 0})
+        if _sinks == "only":
+            return {"_sinks": handed}
     if is_svmr:
         res["SVMR"] = sink_svmr.fetch(desc_ids, descs, scale=clip)
     if is_vcmr:
@@ -1497,13 +1515,16 @@ def compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=10
     if not as_arrays:
         from .results import to_lists
         res = to_lists(res)
+    if handed is not None:
+        res["_sinks"] = handed
     return res
 
 
 def compute_query2ctx_info_svmr_only(model, eval_dataset, opt, ctx_info, max_before_nms=1000, max_n_videos=200,
-                                     tasks=("SVMR",), ops=hip_ops, as_arrays=False, max_after_nms=100):
+                                     tasks=("SVMR",), ops=hip_ops, as_arrays=False, max_after_nms=100, _sinks=None):
     """Mirror of compute_query2ctx_info_svmr_only (xml/inference.py:107-167): every query is scored against its
-    ground-truth video only (K7 with one pair per query + K9 with k = 1); no corpus-wide similarity."""
+    ground-truth video only (K7 with one pair per query + K9 with k = 1); no corpus-wide similarity.
+    _sinks: as in compute_query2ctx_info."""
     index = ctx_info["index"]
     video2idx = eval_dataset.video2idx
     video_metas = ctx_info["video_metas"]
@@ -1533,24 +1554,34 @@ def compute_query2ctx_info_svmr_only(model, eval_dataset, opt, ctx_info, max_bef
     if _nms_on_device(opt):         # (see compute_query2ctx_info)
         sink.nms_scale = float(clip)
         sink.nms("SVMR", opt, max_after_nms)
+    handed = None
+    if _sinks is not None:
+        handed = dict(desc_ids=desc_ids, descs=descs, kept=dict(SVMR=sink) if _nms_on_device(opt) else {},
+                      raw=dict(SVMR=(sink, float(clip))) if sink.n > 0 else {})
+        if _sinks == "only":
+            return {"_sinks": handed}
     res = sink.fetch(desc_ids, descs, scale=clip)
     out = dict(SVMR=res)
     if _nms_on_device(opt):
         out["SVMR_nms"] = sink.fetch_nms(desc_ids, descs)
-    return out if as_arrays else {k: v.to_list() for k, v in out.items()}
+    out = out if as_arrays else {k: v.to_list() for k, v in out.items()}
+    if handed is not None:
+        out["_sinks"] = handed
+    return out
 
 
-def get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=hip_ops, as_arrays=False):
+def get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=hip_ops, as_arrays=False, _sinks=None):
     """Mirror of get_eval_res (xml/inference.py:448-464)."""
     context_info = compute_context_info(model, eval_dataset, opt, ops=ops)
     if "VCMR" in tasks or "VR" in tasks:
         eval_res = compute_query2ctx_info(model, eval_dataset, opt, context_info, max_before_nms=opt.max_before_nms,
                                           max_n_videos=opt.max_vcmr_video, tasks=tasks, ops=ops, as_arrays=as_arrays,
-                                          max_after_nms=max_after_nms)
+                                          max_after_nms=max_after_nms, _sinks=_sinks)
     else:
         eval_res = compute_query2ctx_info_svmr_only(model, eval_dataset, opt, context_info,
                                                     max_before_nms=opt.max_before_nms, max_n_videos=max_after_nms,
-                                                    tasks=tasks, ops=ops, as_arrays=as_arrays, max_after_nms=max_after_nms)
+                                                    tasks=tasks, ops=ops, as_arrays=as_arrays, max_after_nms=max_after_nms,
+                                                    _sinks=_sinks)
     eval_res["video2idx"] = eval_dataset.video2idx
     return eval_res
 
@@ -1573,10 +1604,26 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
     use_desc_type=True.  opt.nms_on_full_lists=True runs NMS on the untruncated lists instead (not the reference).
     opt.nms_on_device=True (not a reference option; host NMS is the default): the after-NMS lists come from xml_nms_moments on
     the device-resident records (compute_query2ctx_info) instead of post_processing_*_nms on the fetched arrays -- the same
-    lists, entry for entry."""
+    lists, entry for entry.
+    opt.eval_on_device=True (not a reference option; the host evaluator is the default): both metric sets come from
+    xml_eval_moments on the device-resident records -- the sinks' records cut to max_after_nms, and K11's kept records (or,
+    without opt.nms_on_device, the host's after-NMS lists sent back as records) -- against a DeviceGroundTruth built once;
+    one small copy of counters per metric set.  The same numbers as evaluate.eval_retrieval, key for key.
+    opt.metrics_only=True (needs eval_on_device, and nms_on_device when opt.nms_thd != -1): additionally no record buffer is
+    fetched at all; returns (None, metrics, None, metrics_after_nms)."""
     import time
     from . import evaluate, postproc
     from .results import to_lists
+    eval_on_device = bool(getattr(opt, "eval_on_device", False))
+    metrics_only = bool(getattr(opt, "metrics_only", False))
+    with_nms = getattr(opt, "nms_thd", -1) != -1
+    if metrics_only and not eval_on_device:
+        raise ValueError("opt.metrics_only needs opt.eval_on_device")
+    if metrics_only and with_nms and not getattr(opt, "nms_on_device", False):
+        raise ValueError("opt.metrics_only with opt.nms_thd != -1 needs opt.nms_on_device")
+    if eval_on_device and ops is not hip_ops:
+        raise ValueError("opt.eval_on_device needs the HIP ops")
+    sinks_kw = dict(_sinks="only" if metrics_only else "also") if eval_on_device else {}
     t = [time.perf_counter()]
 
     def lap(name):
@@ -1584,20 +1631,44 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
         if timings is not None:
             timings[name] = timings.get(name, 0.0) + t[-1] - t[-2]
     if ctx_info is None:
-        raw = get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=ops, as_arrays=True)
+        raw = get_eval_res(model, eval_dataset, opt, tasks, max_after_nms, ops=ops, as_arrays=True, **sinks_kw)
     elif "VCMR" in tasks or "VR" in tasks:
         raw = compute_query2ctx_info(model, eval_dataset, opt, ctx_info, max_before_nms=opt.max_before_nms,
                                      max_n_videos=opt.max_vcmr_video, tasks=tasks, ops=ops, as_arrays=True,
-                                     max_after_nms=max_after_nms)
+                                     max_after_nms=max_after_nms, **sinks_kw)
         raw["video2idx"] = eval_dataset.video2idx
     else:
         raw = compute_query2ctx_info_svmr_only(model, eval_dataset, opt, ctx_info, max_before_nms=opt.max_before_nms,
                                                max_n_videos=max_after_nms, tasks=tasks, ops=ops, as_arrays=True,
-                                               max_after_nms=max_after_nms)
+                                               max_after_nms=max_after_nms, **sinks_kw)
         raw["video2idx"] = eval_dataset.video2idx
+    sinks = raw.pop("_sinks", None)
     # opt.nms_on_device: the kept lists were made on the device, next to the raw ones
     dev_nms = {k[:-4]: raw.pop(k) for k in [k for k in raw if k.endswith("_nms")]}
     lap("search")
+    match_number = not getattr(opt, "debug", False)
+    use_desc_type = getattr(opt, "dset_name", "tvr") == "tvr"
+    dev_gt = None
+    if sinks is not None and ground_truth is not None and sinks["raw"]:
+        n_rows = max(s.n for s, _ in sinks["raw"].values())
+        dev_gt = evaluate.DeviceGroundTruth(ground_truth, eval_dataset.video2idx, sinks["desc_ids"][:n_rows], opt.device,
+                                            use_desc_type=use_desc_type or with_nms, match_number=match_number)
+    if metrics_only:
+        lap("top_n")
+        metrics = metrics_nms = None
+        if dev_gt is not None:
+            metrics = evaluate.eval_retrieval_device(
+                {k: s.eval_raw(max_after_nms) + (sc,) for k, (s, sc) in sinks["raw"].items()}, dev_gt,
+                use_desc_type=use_desc_type)
+        lap("eval")
+        if with_nms:
+            lap("nms")
+            if dev_gt is not None:
+                metrics_nms = evaluate.eval_retrieval_device({k: s.eval_kept() for k, s in sinks["kept"].items()}, dev_gt)
+            lap("eval_nms")
+        if not as_arrays:
+            lap("lists")
+        return None, metrics, None, metrics_nms
     full = None
     if getattr(opt, "nms_on_full_lists", False):
         full = {k: (v if k == "video2idx" else v.copy()) for k, v in raw.items()}
@@ -1605,11 +1676,14 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
     if full is not None:
         raw = full
     lap("top_n")
-    use_desc_type = getattr(opt, "dset_name", "tvr") == "tvr"
     metrics = None
-    if ground_truth is not None:
+    if dev_gt is not None:
+        metrics = evaluate.eval_retrieval_device(
+            {k: s.eval_raw(max_after_nms) + (sc,) for k, (s, sc) in sinks["raw"].items()}, dev_gt,
+            use_desc_type=use_desc_type)
+    elif ground_truth is not None:
         metrics = evaluate.eval_retrieval(submission, ground_truth, iou_thds=(0.5, 0.7), verbose=False,
-                                          match_number=not getattr(opt, "debug", False), use_desc_type=use_desc_type)
+                                          match_number=match_number, use_desc_type=use_desc_type)
     lap("eval")
     sub_nms = metrics_nms = None
     if getattr(opt, "nms_thd", -1) != -1:
@@ -1621,9 +1695,18 @@ def eval_epoch(model, eval_dataset, opt, tasks=("SVMR",), max_after_nms=100, gro
                 sub_nms[k] = fn(raw[k], nms_thd=opt.nms_thd, max_before_nms=opt.max_before_nms,
                                 max_after_nms=max_after_nms)         # (arrays in, new arrays out: nothing to deep-copy)
         lap("nms")
-        if ground_truth is not None:
+        if dev_gt is not None:
+            on_dev = {}
+            for k in ("SVMR", "VCMR"):
+                if k in sinks["kept"]:
+                    on_dev[k] = sinks["kept"][k].eval_kept()
+                elif k in sub_nms:      # host NMS: its lists go back as records (f32 seconds, so scale = 1.0)
+                    rec, cnt = evaluate.records_from_results(sub_nms[k])
+                    on_dev[k] = (torch.from_numpy(rec).to(opt.device), torch.from_numpy(cnt).to(opt.device))
+            metrics_nms = evaluate.eval_retrieval_device(on_dev, dev_gt)
+        elif ground_truth is not None:
             metrics_nms = evaluate.eval_retrieval(sub_nms, ground_truth, iou_thds=(0.5, 0.7), verbose=False,
-                                                  match_number=not getattr(opt, "debug", False))
+                                                  match_number=match_number)
         lap("eval_nms")
     if not as_arrays:
         submission = to_lists(submission)

@@ -979,6 +979,65 @@ def nms_moments(records, count, by_video, thd, scale=1.0, max_before=None, max_a
     return out, out_index, out_count
 
 
+EVAL_TASKS = {"VCMR": 0, "SVMR": 1, "VR": 2}
+
+
+def eval_moments(rec, count, task, gt, scale=1.0, max_pred=100, iou_thds=(0.5, 0.7), topks=(1, 5, 10, 100),
+                 first_hit=None, hits=None, rows=None):
+    """K12: the recall counters of K10 / K11 records on the device (xml_eval_moments; the semantics of
+    evaluate.eval_by_task_type on the array path).
+    rec (Nq, n, 4) int32 = xml_moment rows (row stride >= n records: a view of a wider buffer is fine), count (Nq,) int32 valid
+    prefix per row or None (whole rows); task "VCMR" | "SVMR" | "VR"; gt: the ground truth of the same rows in the same order --
+    an evaluate.DeviceGroundTruth, or anything with gt_vid (Nq,) int32, gt_ts (Nq, n_ts, 2) f32, n_gt (Nq,) int32 and
+    desc_type (Nq,) int32 or None.  scale: float64 factor on st / ed (clip_length for SVMR records in clip units).
+    -> (first_hit (Nq, n_thd) int32, hits (4, n_thd, n_k) int32, rows (4,) int32) on the device; n_thd is 1 for "VR".
+    first_hit / hits / rows: destinations to use instead of new tensors."""
+    if not isinstance(rec, torch.Tensor) or not rec.is_cuda:
+        raise _lib.XmlHipError("rec: tensor must live on the GPU; the HIP path has no CPU fallback")
+    if rec.dtype != torch.int32 or rec.dim() != 3 or rec.shape[2] != 4 or rec.stride(2) != 1 or rec.stride(1) != 4 \
+            or rec.stride(0) % 4 != 0:
+        raise _lib.XmlHipError("rec: expected (Nq, n, 4) int32 xml_moment rows, got %s %s strides %s"
+                               % (rec.dtype, tuple(rec.shape), tuple(rec.stride())))
+    if task not in EVAL_TASKS:
+        raise ValueError("task: expected one of %s, got %r" % (sorted(EVAL_TASKS), task))
+    nq, n = rec.shape[0], rec.shape[1]
+    if count is not None:
+        _req(count, "count", torch.int32)
+        assert count.numel() == nq
+    _req(gt.gt_vid, "gt.gt_vid", torch.int32)
+    _req(gt.gt_ts, "gt.gt_ts", torch.float32)
+    _req(gt.n_gt, "gt.n_gt", torch.int32)
+    if gt.desc_type is not None:
+        _req(gt.desc_type, "gt.desc_type", torch.int32)
+        assert gt.desc_type.numel() == nq
+    assert gt.gt_vid.numel() == nq and gt.n_gt.numel() == nq and gt.gt_ts.dim() == 3 and gt.gt_ts.shape[0] == nq \
+        and gt.gt_ts.shape[2] == 2, "the ground truth holds one row per record row"
+    n_ts = gt.gt_ts.shape[1]
+    n_thd = 1 if task == "VR" else len(iou_thds)
+    thd = (ctypes.c_float * max(len(iou_thds), 1))(*[float(x) for x in iou_thds])
+    ks = (ctypes.c_int32 * len(topks))(*[int(k) for k in topks])
+    dev = rec.device
+    if first_hit is None:
+        first_hit = torch.empty((nq, n_thd), dtype=torch.int32, device=dev)
+    if hits is None:
+        hits = torch.empty((4, n_thd, len(topks)), dtype=torch.int32, device=dev)
+    if rows is None:
+        rows = torch.empty((4,), dtype=torch.int32, device=dev)
+    for t, name, numel in ((first_hit, "first_hit", nq * n_thd), (hits, "hits", 4 * n_thd * len(topks)), (rows, "rows", 4)):
+        _req(t, name, torch.int32)
+        assert t.numel() == numel, "%s: expected %d elements, got %d" % (name, numel, t.numel())
+    if nq == 0:                     # (the entry leaves its outputs untouched: no row, no hit)
+        hits.zero_()
+        rows.zero_()
+        return first_hit, hits, rows
+    check(_lib.load().xml_eval_moments(_p(rec), rec.stride(0) // 4, _p(count), nq, n, EVAL_TASKS[task], float(scale),
+                                       int(max_pred), _p(gt.gt_vid), _p(gt.gt_ts), n_ts, _p(gt.n_gt), _p(gt.desc_type),
+                                       ctypes.cast(thd, ctypes.c_void_p), len(iou_thds) if task != "VR" else 1,
+                                       ctypes.cast(ks, ctypes.c_void_p), len(topks), _p(first_hit), _p(hits), _p(rows),
+                                       _stream()), "xml_eval_moments")
+    return first_hit, hits, rows
+
+
 # ---- exact-rank mode (bf16 K6 as a filter in front of f32 scores; include/xmlhip.h "Exact-rank mode") --------------------
 def round_bf16_rows_err(y):
     """y (..., d) f32 L2-normalised rows -> (yb bf16 = rne(y), err (...) f32 = ||y - yb||_2 per row)."""
