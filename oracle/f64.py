@@ -12,6 +12,9 @@ for the exact value W; `bf16_round` for the staged reference S).  Boundaries mod
 projected Q / K / V, the normalised probabilities P (they reach the P.V MFMA through an LDS patch in the storage type), the
 attention context, K1's ReLU output + position rows (`pre_ln=True`: only the LayerNorm-epilogue GEMM stores the
 pre-LayerNorm value in the storage type; the unfused path keeps it in f32).
+
+The training nodes (autograd.py) have autograd references at the end of this module (`train_*`): there `staged` applies the
+stage to the forward value AND / OR to the gradient crossing the same point, as the bf16 backward kernels store gradients too.
 """
 import math
 
@@ -148,3 +151,135 @@ def q2c_scores(q, c, mask):
     """get_video_level_scores behind the normalisation: per-clip cosines (Nq, L, Nv) masked, and their max over clips."""
     s = mask_logits(torch.einsum("md,nld->mln", d(q), d(c)), d(mask).t().unsqueeze(0))
     return torch.max(s, dim=1)[0], s
+
+
+# ---- training ops: staged float64 AUTOGRAD references (tests/test_gpu_train_bf16.py) ----------------------------------------
+# The bf16 training nodes of tvretrieval_amd/autograd.py store activations AND gradients in bf16.  `staged` is the
+# straight-through form of `stage` for autograd: the forward value and / or the gradient crossing the boundary is put through
+# `stage`; with stage = ident the node is not even recorded, so the reference IS plain float64 autograd (the exact value W).
+# Each reference below is plain torch autograd in the dtype of its leaves (float64 for W and S; float32 gives the float32
+# reference R of numerics_regimes.check_bf16_rounding) and names the stores it models.
+class _Staged(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, fwd, bwd):
+        ctx.bwd = bwd
+        return x.clone() if fwd is None else fwd(x).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g if ctx.bwd is None else ctx.bwd(g).to(g.dtype)), None, None
+
+
+def staged(x, stage=ident, fwd=True, bwd=True):
+    """x with `stage` applied to its value (fwd) and to the gradient that flows back through this point (bwd)."""
+    if stage is ident or not (fwd or bwd):
+        return x
+    return _Staged.apply(x, stage if fwd else None, stage if bwd else None)
+
+
+def operand(w):
+    """an f32 master parameter as the bf16 GEMM operand the kernels read (ops.pack_weights / BertAdam.refresh_shadows round
+    it to nearest); its gradient stays f32 and goes to the master unchanged.  Part of the OPERANDS: applied for W and S alike."""
+    return _Staged.apply(w, bf16_round, None)
+
+
+def train_linear(x, w, b, relu, stage=ident):
+    """LinearFn.  bf16 stores: y (ops.linear's epilogue, behind the ReLU) and dX (ops.linear on W^T: LinearFn.backward; the
+    zero-padded reduction columns of n % 8 add exact zeros).  relu_bwd passes dY or 0: no rounding.  dW / db: f32 sums
+    (gemm_tn, or transposes + split-K; colsum) of products of the bf16 values -- no boundary."""
+    y = F.linear(staged(x, stage, fwd=False), operand(w), b)
+    return staged(y.clamp_min(0) if relu else y, stage, bwd=False)
+
+
+def train_layernorm(a, b, g, beta, stage=ident):
+    """LayerNormFn without dropout sites.  bf16 stores: y (xml_add_layernorm) and dx (layernorm_bwd_kernel's st8 in dy's type;
+    ONE dx serves a and b, ops.convert widens it exactly where `a` is f32).  Statistics, dgamma, dbeta: f32."""
+    x = a if b is None else a + b
+    y = F.layer_norm(staged(x, stage, fwd=False), (x.shape[-1],), g, beta, O.LN_EPS)
+    return staged(y, stage, bwd=False)
+
+
+def train_qkv(x, ws, bs, stage=ident, residual=None):
+    """QkvFn / QkvResFn: one GEMM on the row-stacked weights.  bf16 stores: y, and dX --
+    residual None: dX = rne(dY W);  "epilogue": the residual gradient is the addend of the dX GEMM, dX = rne(dY W + dres), one
+    store;  "fallback" (dres in another dtype): rne(dY W) + dres in torch.  -> y, or (y, x as the residual operand)."""
+    w = torch.cat([operand(w_) for w_ in ws], 0)
+    bias = torch.cat(list(bs), 0)
+    if residual == "fallback":
+        return staged(F.linear(staged(x, stage, fwd=False), w, bias), stage, bwd=False), x
+    xs = staged(x, stage, fwd=False)
+    y = staged(F.linear(xs, w, bias), stage, bwd=False)
+    return y if residual is None else (y, xs)
+
+
+def train_attention(q, k, v, q_mask, k_mask, n_heads, stage=ident):
+    """AttentionCoreFn / AttentionKvFn / AttentionQkvFn, p_drop = 0, fused (attention_train.hip) and unfused chain alike.
+    bf16 stores: P where it feeds P V and P^T dO (LDS patch / attn_softmax's P, P^T; the softmax backward itself uses the f32
+    P), the context O, dS = P (dP - delta) / sqrt(dh) (LDS / attn_softmax's dS, dS^T: the gradient of the RAW Q K^T), and
+    dQ, dK, dV.  S and dP stay f32 (accumulators / out_f32 GEMMs)."""
+    n, lq, hsz = q.shape
+    lk = k.shape[1]
+    dh = hsz // n_heads
+    km = k_mask.to(q.dtype)
+    att = km.unsqueeze(1) if q_mask is None else torch.einsum("bm,bn->bmn", q_mask.to(q.dtype), km)
+    sp = lambda t, l: staged(t, stage, fwd=False).view(n, l, n_heads, dh).permute(0, 2, 1, 3)      # noqa: E731
+    raw = staged(torch.matmul(sp(q, lq), sp(k, lk).transpose(-1, -2)), stage, fwd=False)
+    probs = torch.softmax(raw / math.sqrt(dh) + (1 - att.unsqueeze(1)) * O.ATT_NEG, dim=-1)
+    ctx = torch.matmul(staged(probs, stage, bwd=False), sp(v, lk))
+    return staged(ctx.permute(0, 2, 1, 3).contiguous().view(n, lq, hsz), stage, bwd=False)
+
+
+def train_modular_pool(enc, mask, wm, stage=ident):
+    """ModularPoolFn.  bf16 stores: the pooled rows and denc; the softmax over tokens and dwm (f32 master, read as f32) are f32."""
+    e = staged(enc, stage, fwd=False)
+    sc = torch.softmax(O.mask_logits(e @ wm.t(), mask.to(e.dtype).unsqueeze(2)), dim=1)
+    return staged(torch.einsum("blm,bld->mbd", sc, e), stage, bwd=False)
+
+
+def train_video_level_scores(qs, fs, masks, stage=ident):
+    """VideoLevelScoresFn.  bf16 stores: the normalised rows qn / cn (ops.l2norm_rows) and dquery / dfeat.  l2norm_bwd
+    differentiates the normalisation of the UNROUNDED row (straight through the store of qn / cn); the cosines, their max and
+    d(qn), d(cn) are f32 (scores f32; loss_tail.hip keeps the gradient of the normalised row in registers, the separate
+    launches in f32 tensors)."""
+    tot = 0
+    for q, c, m in zip(qs, fs, masks):
+        qn = staged(F.normalize(staged(q, stage, fwd=False), dim=-1), stage, bwd=False)
+        cn = staged(F.normalize(staged(c, stage, fwd=False), dim=-1), stage, bwd=False)
+        s = O.mask_logits(torch.einsum("md,nld->mln", qn, cn), m.to(qn.dtype).t().unsqueeze(0))
+        tot = tot + torch.max(s, dim=1)[0]
+    return tot / len(qs)
+
+
+def train_pair_sim(q, f2, stage=ident):
+    """PairSimFn: sim f32; bf16 stores: dq and df2."""
+    return torch.einsum("bd,bld->bl", staged(q, stage, fwd=False), staged(f2, stage, fwd=False))
+
+
+def train_span_loss(sims, filters, mask, st_ed, merged, ks):
+    """SpanLossFn (f32 in the bf16 model too: PairSimFn's output is f32): no bf16 boundary."""
+    n_sim = len(sims)
+    mask = mask.to(sims[0].dtype)
+    conv = lambda s, w: F.conv1d(s.unsqueeze(1), w, padding=ks // 2).squeeze(1)     # noqa: E731
+    if merged:
+        s = (sims[0] + sims[1]) / 2
+        lst, led = O.mask_logits(conv(s, filters[0]), mask), O.mask_logits(conv(s, filters[1]), mask)
+    else:
+        lst = sum(O.mask_logits(conv(sims[i], filters[i]), mask) for i in range(n_sim)) / n_sim
+        led = sum(O.mask_logits(conv(sims[i], filters[n_sim + i]), mask) for i in range(n_sim)) / n_sim
+    return F.cross_entropy(lst, st_ed[:, 0]) + F.cross_entropy(led, st_ed[:, 1])
+
+
+def train_rank_loss(scores, ranks_ctx, ranks_q, margin, lse):
+    """RankLossFn (f32 scores from VideoLevelScoresFn): no bf16 boundary."""
+    n = scores.shape[0]
+    ar = torch.arange(n)
+    pos = scores[ar, ar]
+    masked = scores.detach().clone()
+    masked[ar, ar] = 999
+
+    def neg(sc, scm, r):
+        return sc[ar, torch.sort(scm, descending=True, dim=1)[1][ar, r.long()]]
+
+    def rl(p, ng):
+        return torch.log1p(torch.exp(ng - p)).sum() / n if lse else torch.clamp(margin + ng - p, min=0).sum() / n
+    return torch.stack([rl(pos, neg(scores, masked, ranks_ctx)), rl(pos, neg(scores.t(), masked.t(), ranks_q))])

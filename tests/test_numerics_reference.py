@@ -4,6 +4,8 @@ without a GPU.
 * each generator achieves the figure it promises;
 * the float32 reference is finite in every regime and passes the new checks itself (as f32, and rounded to bf16 by torch),
   the 1 % cap on rounding-boundary elements included;
+* the staged float64 AUTOGRAD references of the training nodes (oracle/f64.py, tests/train_bf16_cases.py): identity stage ==
+  plain float64 autograd bit for bit, staged != exact, one bf16 store stays within half a bf16 ulp of W (<= 2^-8 |W|) plus one f32 rounding;
 * sensitivity: deliberately wrong stand-ins are rejected by the check meant for them while the existing `close(...)`
   limits of test_gpu_kernels.py accept them on that suite's operands."""
 import math
@@ -13,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 import numerics_regimes as NR
+import train_bf16_cases as TC
 from oracle import f64
 from oracle import xml_oracle as O
 from test_gpu_kernels import _att_weights, _ragged_mask, close, rnd
@@ -222,3 +225,103 @@ def test_one_pass_variance_is_rejected_at_mean_1e3_and_accepted_at_zero_mean():
     bad = _layernorm_one_pass(case["a"] + case["b"], case["g"], case["beta"])
     with pytest.raises(AssertionError, match="float32 reference"):
         NR.check_f32("layernorm one pass", "offset1e3", bad, case["W"], case["R"], 8)
+
+
+# ---- staged float64 autograd references of the training nodes -----------------------------------------------------------
+def _plain(case, ls):
+    """the node of `case` as plain torch ops on float64 leaves (weights rounded to bf16 beforehand): no oracle/f64 staging."""
+    cfg = case.cfg
+    sp = lambda t, h: t.view(t.shape[0], t.shape[1], cfg["heads"], h // cfg["heads"]).permute(0, 2, 1, 3)     # noqa: E731
+    if case.op == "LinearFn":
+        y = F.linear(*ls)
+        return y.clamp_min(0) if cfg["relu"] else y
+    if case.op == "LayerNormFn":
+        a, b, g, beta = ls
+        x = a if b is None else a + b
+        return F.layer_norm(x, (x.shape[-1],), g, beta, O.LN_EPS)
+    if case.op in ("QkvFn", "QkvResFn"):
+        y = F.linear(ls[0], torch.cat(ls[1::2], 0), torch.cat(ls[2::2], 0))
+        return (y, ls[0]) if cfg["residual"] else y
+    if case.op.startswith("Attention"):
+        h = ls[0].shape[-1] // {"core": 1, "kv": 1, "qkv": 3}[cfg["form"]]
+        q, k, v = {"core": lambda: ls, "kv": lambda: (ls[0], ls[1][..., :h], ls[1][..., h:]),
+                   "qkv": lambda: (ls[0][..., :h], ls[0][..., h:2 * h], ls[0][..., 2 * h:])}[cfg["form"]]()
+        km, qm = cfg["k_mask"].double(), cfg["q_mask"]
+        att = km.unsqueeze(1) if qm is None else torch.einsum("bm,bn->bmn", qm.double(), km)
+        s = torch.matmul(sp(q, h), sp(k, h).transpose(-1, -2)) / math.sqrt(h // cfg["heads"]) + (1 - att.unsqueeze(1)) * O.ATT_NEG
+        o = torch.matmul(torch.softmax(s, dim=-1), sp(v, h))
+        return o.permute(0, 2, 1, 3).contiguous().view(q.shape)
+    if case.op == "ModularPoolFn":
+        enc, wm = ls
+        sc = torch.softmax(O.mask_logits(enc @ wm.t(), cfg["mask"].double().unsqueeze(2)), dim=1)
+        return torch.einsum("blm,bld->mbd", sc, enc)
+    if case.op == "VideoLevelScoresFn":
+        n_mod, tot = cfg["n_mod"], 0
+        for i in range(n_mod):
+            s = torch.einsum("md,nld->mln", F.normalize(ls[i], dim=-1), F.normalize(ls[n_mod + i], dim=-1))
+            tot = tot + torch.max(O.mask_logits(s, cfg["masks"][i].double().t().unsqueeze(0)), dim=1)[0]
+        return tot / n_mod
+    assert case.op == "PairSimFn"
+    return torch.einsum("bd,bld->bl", *ls)
+
+
+@pytest.mark.parametrize("case", TC.all_cases(), ids=repr)
+def test_training_node_references(case):
+    refs = case.refs()
+    (Wo, Wg), (So, Sg), (Ro, Rg) = refs["W"], refs["S"], refs["R"]
+    for t in Wo + [g for g in Wg if g is not None]:
+        assert t.dtype == torch.float64 and bool(torch.isfinite(t).all())
+    assert [g is None for g in Wg] == [not n for n in case.needs] == [g is None for g in Sg]
+    if case.op in ("SpanLossFn", "RankLossFn"):      # f32 nodes: nothing is staged
+        assert all(torch.equal(a, b) for a, b in zip(Wo, So)) and all(torch.equal(a, b) for a, b in zip(Wg, Sg))
+        for w, r in zip(Wo + Wg, Ro + Rg):
+            assert float((r.double() - w).abs().max()) <= 1e-5 * float(w.abs().max())
+        return
+    # identity stage == plain float64 autograd on the same operands, bit for bit
+    is_w = lambda i: case.leaves[i] is not None and case.leaves[i].dtype == F32 and case.leaves[i].dim() == 2 and \
+        case.op in ("LinearFn", "QkvFn", "QkvResFn")                                                          # noqa: E731
+    ls = [None if t is None else (f64.bf16_round(t) if is_w(i) else t.double()).requires_grad_(ng)
+          for i, (t, ng) in enumerate(zip(case.leaves, case.needs))]
+    outs = _plain(case, ls)
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    torch.autograd.backward(outs, [g.double() for g in case.gouts])
+    for a, b in zip(Wo, outs):
+        assert torch.equal(a, b.detach())
+    for a, l in zip(Wg, ls):
+        assert a is None or torch.equal(a, l.grad)
+    # the staged form differs from the exact one, by bf16 roundings and not by more
+    diff = max(float((s - w).abs().max() / w.abs().max()) for s, w in zip(So + Sg, Wo + Wg) if w is not None)
+    assert 0 < diff < 2e-2, diff
+    # One bf16 store: S = rne(W), i.e. within HALF A bf16 ULP of W -- per element at most 2^-8 |W| (8 significand bits: the
+    # spacing in [2^e, 2^(e+1)) is 2^(e-7)) and exactly on the grid.  (2^-9 |W| cannot hold for a correct rounding: W = 0.3993
+    # lies 8.3e-4 = 2.07e-3 |W| from its nearest bf16 neighbour 0.3984.)  f32 outputs in front of every boundary are untouched.
+    # (bf16_round goes through float32 like the kernels' stores: a double rounding may add one f32 rounding of W)
+    half_ulp = lambda w: 0.5 * NR.bf16_ulp(w) + 2.0 ** -24 * w.abs()      # noqa: E731
+    if not case.chain:
+        for i, (s, w) in enumerate(zip(So, Wo)):
+            if case.out_is_bf16(i):
+                assert bool(((s - w).abs() <= half_ulp(w)).all()) and bool(((s - w).abs() <= (2.0 ** -8 + 2.0 ** -24) * w.abs()).all())
+                assert torch.equal(s, f64.bf16_round(s))
+            else:
+                assert torch.equal(s, w)
+        for i, (s, w) in enumerate(zip(Sg, Wg)):
+            if w is None:
+                continue
+            if case.grad_is_bf16(i):                      # one store: half a bf16 ulp
+                assert bool(((s - w).abs() <= half_ulp(w)).all()) and bool(((s - w).abs() <= (2.0 ** -8 + 2.0 ** -24) * w.abs()).all())
+                assert torch.equal(s, f64.bf16_round(s))
+
+
+def test_staged_is_straight_through():
+    x = torch.randn(64, dtype=torch.float64, requires_grad=True)
+    g = torch.randn(64, dtype=torch.float64)
+    assert f64.staged(x, f64.ident) is x
+    for fwd, bwd in ((True, True), (True, False), (False, True)):
+        x.grad = None
+        y = f64.staged(x, f64.bf16_round, fwd, bwd)
+        y.backward(g)
+        assert torch.equal(y.detach(), f64.bf16_round(x.detach()) if fwd else x.detach())
+        assert torch.equal(x.grad, f64.bf16_round(g) if bwd else g)
+    w = torch.randn(8, 8, requires_grad=True)
+    f64.operand(w).sum().backward()
+    assert torch.equal(f64.operand(w).detach(), w.detach().to(BF16).float()) and torch.equal(w.grad, torch.ones(8, 8))
