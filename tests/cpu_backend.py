@@ -1,6 +1,9 @@
 """TEST INFRASTRUCTURE: CPU stand-ins (built on the oracle's formulation) for tvretrieval_amd.ops and for the model,
 so that the host-side orchestration (corpus sharding, two-phase all-gather merge) can be exercised with world_size-2
-`gloo` process groups on a machine without a GPU.  Never imported by the product."""
+`gloo` process groups on a machine without a GPU.  Never imported by the product.
+CpuOps follows the backend contract stated at the top of tvretrieval_amd/inference.py: the names of OPS_CONTRACT with the
+parameter names of tvretrieval_amd.ops (tests/test_backend_contract.py).  Restricted search (allow=) is not implemented;
+vid_len / pair_vid only let the kernels skip entries that are exactly zero, so they are ignored."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -9,6 +12,8 @@ from oracle import xml_oracle as O
 
 
 class CpuOps(object):
+    F16S = object()         # no split-f16 model on this backend: never a model's compute_dtype, never a tensor's dtype
+
     @staticmethod
     def l2norm_rows(x):
         return F.normalize(x.float(), dim=-1)
@@ -23,7 +28,9 @@ class CpuOps(object):
         return out
 
     @staticmethod
-    def q2c_scores_fused(qn, cn, masks, out=None):
+    def q2c_scores_fused(qn, cn, masks, out=None, normalize_q=False):
+        if normalize_q:
+            qn = [CpuOps.l2norm_rows(q) for q in qn]
         acc = None
         for m in range(len(qn)):
             s = CpuOps.q2c_scores(qn[m], cn[m], masks[m])
@@ -31,7 +38,9 @@ class CpuOps(object):
         return acc
 
     @staticmethod
-    def topk_rows(scores, k, alpha=0.0, idx_in=None):
+    def topk_rows(scores, k, alpha=0.0, idx_in=None, allow=None, col0=0, return_count=False):
+        if allow is not None or col0 or return_count:
+            raise NotImplementedError("CpuOps.topk_rows: allow=")
         n = scores.shape[1]
         pay = idx_in.long() if idx_in is not None else torch.arange(n).repeat(scores.shape[0], 1)
         order = torch.argsort(pay, dim=1, stable=True)
@@ -50,8 +59,20 @@ class CpuOps(object):
         return yb, (y.double() - yb.double()).norm(dim=-1).float()
 
     @staticmethod
-    def pack_q2c_corpus(feat1n, mask=None, plan=None, normalize=False):
+    def pack_q2c_corpus(feat1n, mask=None, plan=None, normalize=False, out=None):
         return F.normalize(feat1n.float(), dim=-1) if normalize else feat1n
+
+    @staticmethod
+    def q2c_pack_plan(masks):
+        return None
+
+    @staticmethod
+    def q2c_tiled_ok(lpad, hidden, dtype):
+        return False
+
+    @staticmethod
+    def q2c_tiled_numel(rows, hidden, dtype):
+        return 0
 
     @staticmethod
     def q2c_rescore(qn, cn, masks, pair_vid):
@@ -82,7 +103,9 @@ class CpuOps(object):
         return fail, eps, t_k - eps, fail.sum().reshape(1).int()
 
     @staticmethod
-    def select_ge_rows(scores, thr, cap=None):
+    def select_ge_rows(scores, thr, cap=None, allow=None, col0=0):
+        if allow is not None or col0:
+            raise NotImplementedError("CpuOps.select_ge_rows: allow=")
         take = scores >= thr[:, None]
         cnt = take.sum(1).int()
         if cap is None:
@@ -94,7 +117,10 @@ class CpuOps(object):
         return idx, cnt
 
     @staticmethod
-    def convse_rerank(q_lin, feat2, masks, pair_vid, conv_w, l_ref, merged, ksize, softmax=True, zero_skipped=True):
+    def convse_rerank(q_lin, feat2, masks, pair_vid, conv_w, l_ref, merged, ksize, softmax=True, zero_skipped=True,
+                      pair_w=None, band=None, vid_len=None):
+        if band is not None:
+            raise NotImplementedError("CpuOps.convse_rerank: candidate summaries (band=)")
         n_mod = len(q_lin)
         n_conv = 1 if merged else n_mod
         wst = conv_w[:n_conv * ksize].view(n_conv, 1, 1, ksize)
@@ -126,7 +152,9 @@ class CpuOps(object):
         return st, ed
 
     @staticmethod
-    def moment_topk(st, ed, w, l_ref, min_l, max_l, n_out):
+    def moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=None, pair_vid=None, vid_len=None):
+        if summ is not None:
+            raise NotImplementedError("CpuOps.moment_topk: candidate summaries (summ=)")
         nq, kp, _ = st.shape
         st, ed = st[..., :l_ref], ed[..., :l_ref]
         if w is None:
@@ -157,13 +185,14 @@ class CpuModel(object):
                 setattr(self, m + "_query_linear",
                         (lambda mm: (lambda x: F.linear(x, w[mm + "_query_linear.weight"], w[mm + "_query_linear.bias"])))(m))
 
-    def encode_query(self, qf, qm):
+    def encode_query(self, qf, qm, n_valid_tokens=None):
         with torch.no_grad():
             return self.o.encode_query(qf, qm)
 
-    def encode_context(self, vf, vm, sf, sm):
+    def encode_context(self, vf, vm, sf, sm, outs=(None, None, None, None)):
         with torch.no_grad():
-            return self.o.encode_context(vf, vm, sf, sm)
+            enc = self.o.encode_context(vf, vm, sf, sm)
+        return tuple(e if o is None else o.copy_(e) for e, o in zip(enc, outs))
 
     def _conv_weights(self):
         w = self.o.w

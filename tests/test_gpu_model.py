@@ -377,7 +377,7 @@ def test_video_with_one_empty_modality_matches_the_reference_lists():
     assert seen >= nq, "video 1 never reached a list"
 
 
-def test_ragged_corpus_buckets_give_identical_lists(monkeypatch):
+def test_ragged_corpus_buckets_give_identical_lists():
     """TVR-like clip counts: the index built with length buckets and the one built without return the same top-100 /
     top-200 lists, bit for bit (bf16, the headline dtype)."""
     from tvretrieval_amd import inference as inf
@@ -392,8 +392,7 @@ def test_ragged_corpus_buckets_give_identical_lists(monkeypatch):
                for b in range(0, nv, 100)]
     with torch.no_grad():
         bucketed = inf.build_corpus_index(m, batches, l_ref=l)
-        monkeypatch.setenv("XML_Q2C_NO_BUCKETS", "1")
-        flat = inf.build_corpus_index(m, batches, l_ref=l)
+        flat = inf.build_corpus_index(m, batches, l_ref=l, length_buckets=False)
         assert bucketed.feat1n["video"].plan is not None and flat.feat1n["video"].plan is None
         a = inf.vcmr_search(m, bucketed, qf.to(DEV), qm.to(DEV))
         b = inf.vcmr_search(m, flat, qf.to(DEV), qm.to(DEV))
@@ -970,6 +969,53 @@ def test_preallocated_index_equals_list_and_cat_index():
     for mod in a.modalities:
         assert torch.equal(a.feat1n_rows(mod), b.feat1n_rows(mod))
         assert torch.equal(a.feat2[mod], b.feat2[mod]) and torch.equal(a.mask[mod], b.mask[mod])
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_known_size_storage_and_direct_encode_equal_the_list_index(dtype):
+    """The three ways to build an index -- l_ref only (batches collected), l_ref + n_videos (rows written into tensors
+    allocated from the first batch), storage=IndexStorage (memory handed in) -- hold the same bits and answer a search
+    alike, at the smallest shape where K6's tile image and the encode straight into index rows are both taken (hidden 256,
+    128 clips).  Batches of 10: 0, 2 and 3 are padded to 128 (direct encode once the destinations exist), batch 1 to its own
+    maximum (a copy between direct batches).  (a) ragged lengths: the length-bucketed image; (b) every video full length:
+    no plan, all_valid, and a storage's tile buffer is the image's destination."""
+    from tvretrieval_amd import inference as inf
+    nv, l = 37, 128
+    m, cfg = _synthetic_model("video_sub", 256, 96, 64, 64, l, dtype, seed=3)
+    lens_a = np.random.default_rng(8).integers(5, l + 1, nv); lens_a[3] = l
+    assert lens_a[10:20].max() < l
+    qf, qm = _feats(9, np.random.default_rng(9).integers(5, 31, 9), 64, 3)
+    for lens, n_tiles in ((lens_a, 10), (np.full(nv, l), None)):
+        vf, vm = _feats(nv, lens, 96, 1)
+        sf, sm = _feats(nv, lens, 64, 2)
+
+        def batches():
+            for b in range(0, nv, 10):
+                lb = int(lens[b:b + 10].max()) if b == 10 else l
+                yield tuple(t[b:b + 10, :lb].contiguous().to(DEV) for t in (vf, vm, sf, sm))
+        with torch.no_grad():
+            storage = inf.IndexStorage(m, nv, l)
+            built = [inf.build_corpus_index(m, batches(), l_ref=l),
+                     inf.build_corpus_index(m, batches(), l_ref=l, n_videos=nv),
+                     inf.build_corpus_index(m, batches(), storage=storage)]
+            outs = [inf.vcmr_search(m, idx, qf.to(DEV), qm.to(DEV)) for idx in built]
+        a = built[0]
+        for b, out in zip(built[1:], outs[1:]):
+            assert torch.equal(a.vlen, b.vlen) and a.ragged == b.ragged == (n_tiles is not None)
+            for mod in a.modalities:
+                ta, tb = a.feat1n[mod], b.feat1n[mod]
+                assert torch.equal(a.feat1n_rows(mod), b.feat1n_rows(mod)), mod
+                assert torch.equal(a.feat2[mod], b.feat2[mod]) and torch.equal(a.mask[mod], b.mask[mod]), mod
+                assert ta.all_valid == tb.all_valid == (n_tiles is None)
+                assert (ta.mask_bits is None and tb.mask_bits is None) or torch.equal(ta.mask_bits, tb.mask_bits)
+                assert (ta.plan is None) == (tb.plan is None) == (n_tiles is None)
+                if n_tiles is not None:
+                    assert ta.plan.n_tiles == tb.plan.n_tiles == n_tiles
+            for k in ("q2c", "top_indices", "flat_scores", "flat_indices"):
+                assert torch.equal(outs[0][k], out[k]), k
+        if n_tiles is None:          # the tile image is written in place, not copied
+            for mod in a.modalities:
+                assert built[2].feat1n[mod].data.data_ptr() == storage.tiles[mod].data_ptr()
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -338,10 +338,9 @@ def _owner_pass(model, index, qvec, ex, k, n_out, q2c_alpha, min_pred_l, max_pre
             qv = {m: v[o_lo:o_hi] for m, v in qv_c.items()}
             top_w, top_gid = own_w.contiguous(), own_gid.contiguous()
             vl = inf.ragged_lengths(index, ops, replicated=True)
-            rk = dict(pair_vid=top_gid, vid_len=vl) if vl is not None else {}
             st, ed = inf.stage_span_probs(model, index, qv, top_gid, ops, replicated=True, vid_len=vl)
             _mark("convse_k7")
-            fs, fi = ops.moment_topk(st, ed, top_w, index.l_ref, min_pred_l, max_pred_l, n_out, **rk)
+            fs, fi = ops.moment_topk(st, ed, top_w, index.l_ref, min_pred_l, max_pred_l, n_out, pair_vid=top_gid, vid_len=vl)
             _mark("moment_k9")
         else:   # more ranks than queries in this chunk
             top_w, top_gid = own_w[:0], own_gid[:0]
@@ -389,11 +388,11 @@ def video_owner_local_moments(model, index, qvec, top_w, top_gid, n_out, min_pre
     own = (top_gid >= lo) & (top_gid < hi)
     pair_local = torch.where(own, top_gid - lo, torch.full_like(top_gid, -1)).contiguous()
     vl = inf.ragged_lengths(index, ops)
-    rk = dict(pair_vid=pair_local, vid_len=vl) if vl is not None else {}
     st, ed = inf.stage_span_probs(model, index, qvec, pair_local, ops, zero_skipped=False, vid_len=vl)   # K9 skips w == 0 pairs
     _mark("convse_k7")
     w_local = torch.where(own, top_w, torch.zeros_like(top_w)).contiguous()   # w == 0 marks slots owned elsewhere:
-    loc_fs, loc_fi = ops.moment_topk(st, ed, w_local, index.l_ref, min_pred_l, max_pred_l, n_out, **rk)     # skipped
+    loc_fs, loc_fi = ops.moment_topk(st, ed, w_local, index.l_ref, min_pred_l, max_pred_l, n_out,          # skipped
+                                     pair_vid=pair_local, vid_len=vl)
     _mark("moment_k9")
     return loc_fs, loc_fi
 

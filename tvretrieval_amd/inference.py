@@ -11,11 +11,34 @@ What changed by design (outputs are the same lists):
   * the (Nq, Nv, L) st/ed tensors are never built: ConvSE runs only on the top-k (and GT) videos per query;
   * the (Nq, k, L, L) product + full sort is replaced by a banded top-n kernel.
 Everything on the device goes through tvretrieval_amd.ops (HIP); numpy only formats the result lists.
+
+The `ops` argument of the functions here and in tvretrieval_amd.dist is the kernel backend.  tvretrieval_amd.ops is its
+definition; a backend is any object with the names of OPS_CONTRACT, each taking the parameter names tvretrieval_amd.ops
+gives it (tests/test_backend_contract.py holds the CPU stand-in of the gloo tests to that).  Nothing here asks a backend what
+it can do: every keyword is passed, None / False being each callee's default, and a stand-in may raise NotImplementedError
+for a non-default value it does not implement.  What OPS_CONTRACT lists is what index build, plain and f32 exact-rank search
+and the sharded drivers call:
+  l2norm_rows(x)                                          round_bf16_rows_err(y)
+  q2c_pack_plan(masks)                                    q2c_tiled_ok(lpad, hidden, dtype)
+  q2c_tiled_numel(rows, hidden, dtype)                    pack_q2c_corpus(feat1n, mask, plan, normalize=, out=)
+  q2c_scores_fused(qn, cn, masks, normalize_q=)           q2c_rescore(qn, cn, masks, pair_vid)
+  topk_rows(scores, k, alpha=, idx_in=, allow=)           select_ge_rows(scores, thr, cap, allow=)
+  exact_certificate(filter_scores, top_val, eq, ec, slack, alpha, outside)
+  convse_rerank(q_lin, feat2, masks, pair_vid, conv_w, l_ref, merged, ksize, softmax=, zero_skipped=, pair_w=, band=, vid_len=)
+  moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=, pair_vid=, vid_len=)
+  F16S                                                    the dtype sentinel of split-f16 models and rows
+The split-f16 exact mode (split_f16_rows, SplitRows, F16_UNIT_LOG2), explain_moments (span_evidence), the device-side result
+records (moments_decode, nms_moments) and vcmr_search_host (ingest_rows) call further entries of tvretrieval_amd.ops; a
+backend without them serves every search that does not ask for those.
 """
 import numpy as np
 import torch
 
 from . import ops as hip_ops
+
+OPS_CONTRACT = ("l2norm_rows", "round_bf16_rows_err", "q2c_pack_plan", "q2c_tiled_ok", "q2c_tiled_numel", "pack_q2c_corpus",
+                "q2c_scores_fused", "q2c_rescore", "topk_rows", "select_ge_rows", "exact_certificate", "convse_rerank",
+                "moment_topk", "F16S")
 
 
 def _round_up(x, m):
@@ -135,7 +158,7 @@ def _exact_filter_operands(f1_raw, mask, plan, ops, mode="f32", filter_dtype=Non
 
 def exact_mode_of(model, ops=hip_ops):
     """which exact-rank pipeline an index built from this model gets"""
-    return "f16s" if getattr(model, "compute_dtype", None) is getattr(ops, "F16S", object()) else "f32"
+    return "f16s" if getattr(model, "compute_dtype", None) is ops.F16S else "f32"
 
 
 def index_lpad(l_ref, model, ops=hip_ops):
@@ -145,10 +168,9 @@ def index_lpad(l_ref, model, ops=hip_ops):
     a tile, so the padding rows of SHORT videos cost no MFMA work) instead of 112 on the slow per-modality kernels."""
     lp = _round_up(int(l_ref), 16)
     dt = getattr(model, "compute_dtype", torch.float32)
-    if dt is getattr(ops, "F16S", object()):
+    if dt is ops.F16S:
         dt = torch.float16            # (its K6 operand is the f16 hi plane)
-    if 64 < lp < 128 and hasattr(ops, "q2c_tiled_ok") and model is not None and \
-            ops.q2c_tiled_ok(128, model.config.hidden_size, dt):
+    if 64 < lp < 128 and model is not None and ops.q2c_tiled_ok(128, model.config.hidden_size, dt):
         return 128
     return lp
 
@@ -187,7 +209,7 @@ class IndexStorage(object):
         self.f2 = {m: torch.zeros((self.n_videos, self.lpad, h), dtype=dt, device=dev) for m in mods}
         self.mk = {m: torch.zeros((self.n_videos, self.lpad), dtype=torch.float32, device=dev) for m in mods}
         self.tiles = {}
-        if tiles and hasattr(ops, "q2c_tiled_numel") and self.lpad == 128 and dt in (torch.float32, torch.bfloat16):
+        if tiles and self.lpad == 128 and dt in (torch.float32, torch.bfloat16):
             n = ops.q2c_tiled_numel(self.n_videos * self.lpad, h, dt)
             if n:
                 self.tiles = {m: torch.zeros(n, dtype=dt, device=dev) for m in mods}
@@ -197,140 +219,106 @@ class IndexStorage(object):
 
 
 def build_corpus_index(model, context_batches, ops=hip_ops, keep_raw=False, video_offset=0, n_total=None,
-                        l_ref=None, n_videos=None, exact_filter=False, storage=None):
+                        l_ref=None, n_videos=None, exact_filter=False, storage=None, length_buckets=True):
     """Encode context batches and assemble the resident index.
 
     context_batches: iterable of (video_feat, video_mask, sub_feat, sub_mask) device tensors (unused modality:
-    None).  Each batch is encoded at its own padded length and zero-filled beyond it when concatenated, exactly
+    None).  Each batch is encoded at its own padded length and zero-filled beyond it in the index, exactly
     like cat_tensor (xml/inference.py:71-87), so rows >= a batch's max length are 0 and rows between a video's
     length and its batch max hold the encoder's outputs at padded positions (both observable through the 5-tap
     ConvSE).
+    l_ref + n_videos (a resident engine knows its corpus) or storage=IndexStorage: the index tensors exist before the loop
+    (allocated from the first batch's dtype and width, or handed in) and every encoded batch is written into its rows -- no
+    growing list of per-batch outputs, no concatenation pass, the per-batch activations are recycled by the allocator; a
+    batch of full padded length is encoded STRAIGHT into its rows (the last layer of each branch writes there).  Otherwise
+    the encoded batches are collected, n_videos / l_ref (the batch maximum) follow from them, and the same rows are filled.
     exact_filter=True (f32 model): exact-rank mode -- feat1n becomes the bf16 filter image, index.exact the f32 operands
-    (ExactFilter); vcmr_search then returns the f32 path's lists at close to the bf16 path's speed."""
+    (ExactFilter); vcmr_search then returns the f32 path's lists at close to the bf16 path's speed.
+    length_buckets=False: a ragged corpus keeps the plain two-videos-per-tile K6 image (A/B against the bucketed one)."""
     mods = [n for n, u in (("video", model.use_video), ("sub", model.use_sub)) if u]
-    if storage is not None:
+    dst = None                    # (feat1, feat2, mask): per-modality (n_videos, lpad, H) x2 and (n_videos, lpad) f32
+    if storage is not None:       # (zero-filled by IndexStorage; used for ONE build)
         assert l_ref is None or int(l_ref) == storage.l_ref
         assert n_videos is None or int(n_videos) == storage.n_videos
         l_ref, n_videos = storage.l_ref, storage.n_videos
-    if n_videos is not None and l_ref is not None:
-        return _build_corpus_index_prealloc(model, context_batches, ops, keep_raw, video_offset, n_total, int(l_ref),
-                                            int(n_videos), mods, exact_filter, storage)
-    parts = {m: dict(f1=[], f2=[], mk=[]) for m in mods}
+        dst = dict(storage.f1), dict(storage.f2), dict(storage.mk)
+    known = n_videos is not None and l_ref is not None
+    lpad = index_lpad(l_ref, model, ops) if known else None
+    collected, r = [], 0
     for video_feat, video_mask, sub_feat, sub_mask in context_batches:
-        v1, v2, s1, s2 = model.encode_context(video_feat, video_mask, sub_feat, sub_mask)
-        if "video" in parts:
-            parts["video"]["f1"].append(v1), parts["video"]["f2"].append(v2), parts["video"]["mk"].append(video_mask.float())
-        if "sub" in parts:
-            parts["sub"]["f1"].append(s1), parts["sub"]["f2"].append(s2), parts["sub"]["mk"].append(sub_mask.float())
-    batch_max = max(t.shape[1] for t in parts[mods[0]]["f2"])
-    l_ref = batch_max if l_ref is None else int(l_ref)
-    assert l_ref >= batch_max
-    lpad = index_lpad(l_ref, model, ops)
-
-    def cat(tensors):
-        n = sum(t.shape[0] for t in tensors)
-        out = tensors[0].new_zeros((n, lpad) + tuple(tensors[0].shape[2:]))
-        r = 0
-        for t in tensors:
-            out[r:r + t.shape[0], :t.shape[1]] = t
-            r += t.shape[0]
-        return out
-
-    feat1n, feat2, mask, raw, ex_f32, ex_ec = {}, {}, {}, {}, {}, {}
-    for m in mods:
-        mask[m] = cat(parts[m]["mk"])
-    # ragged corpora: one length-bucketed layout shared by the modalities (2 / 4 / 8 videos per K6 tile)
-    plan = ops.q2c_pack_plan([mask[m] for m in mods]) if (hasattr(ops, "q2c_pack_plan") and lpad == 128) else None
-    for m in mods:
-        f1 = cat(parts[m]["f1"])
-        feat2[m] = cat(parts[m]["f2"])
-        if exact_filter:
-            feat1n[m], ex_f32[m], ex_ec[m] = _exact_filter_operands(f1, mask[m], plan, ops, exact_mode_of(model, ops))
-            if exact_mode_of(model, ops) == "f16s":
-                feat2[m] = ops.split_f16_rows(feat2[m])
-        elif hasattr(ops, "pack_q2c_corpus"):    # HIP backend: normalised + slice-major tiles for the persistent K6 kernel
-            feat1n[m] = ops.pack_q2c_corpus(f1, mask[m], plan, normalize=True)
-        else:
-            feat1n[m] = ops.l2norm_rows(f1)
-        if keep_raw:
-            raw[m] = f1
-    idx = CorpusIndex(mods, feat1n, feat2, mask, l_ref, video_offset, n_total)
-    if getattr(ops, "RAGGED_ROWS", False):
-        idx.set_valid_lengths()
-    idx.raw_feat1 = raw
-    if exact_filter:
-        idx.exact = _make_exact_filter(ex_f32, ex_ec, exact_mode_of(model, ops))
-    return idx
-
-
-def _make_exact_filter(ex_f32, ex_ec, mode):
-    # f16 filter: rounding errors 8x smaller than bf16's -> the certificate holds with half the candidates
-    return ExactFilter(ex_f32, ex_ec, n_candidates=128 if (mode == "f16s" and EXACT_F16S_FILTER == "f16") else 256, mode=mode)
-
-
-def _build_corpus_index_prealloc(model, context_batches, ops, keep_raw, video_offset, n_total, l_ref, n_videos, mods,
-                                 exact_filter=False, storage=None):
-    """build_corpus_index when the number of videos and the corpus-wide length are known up front (a resident engine knows
-    its corpus): the three index tensors per modality are allocated once and every encoded batch is written into its
-    rows -- no growing list of per-batch outputs, no concatenation pass, and the per-batch activations are recycled by the
-    allocator instead of each batch mapping fresh memory.  Same contents as the list + cat path (zero rows beyond a
-    batch's own padded length)."""
-    lpad = index_lpad(l_ref, model, ops)
-    f1, f2, mk = {}, {}, {}
-    if storage is not None:       # (zero-filled by IndexStorage; used for ONE build)
-        f1, f2, mk = dict(storage.f1), dict(storage.f2), dict(storage.mk)
-    r = 0
-    for video_feat, video_mask, sub_feat, sub_mask in context_batches:
-        # batches of full padded length are encoded STRAIGHT into their rows of the index tensors (the last layer of each
-        # branch writes there): no per-batch copies.  The first batch, shorter batches and non-HIP backends go through copies.
+        feats = dict(video=video_feat, sub=sub_feat)
         outs = [None, None, None, None]
-        direct = bool(f1) and getattr(ops, "ENCODE_INTO_INDEX", False)
+        direct = dst is not None and all(feats[m] is not None and feats[m].shape[1] == lpad
+                                         and r + feats[m].shape[0] <= n_videos for m in mods)
         if direct:
-            for i, (m, feat) in enumerate((("video", video_feat), ("sub", sub_feat))):
-                b = feat.shape[0] if feat is not None else 0
-                if m in mods and feat is not None and feat.shape[1] == lpad and r + b <= n_videos:
-                    outs[2 * i], outs[2 * i + 1] = f1[m][r:r + b], f2[m][r:r + b]
-                elif m in mods:
-                    direct = False
-        if direct:
-            v1, v2, s1, s2 = model.encode_context(video_feat, video_mask, sub_feat, sub_mask, outs=tuple(outs))
-        else:
-            v1, v2, s1, s2 = model.encode_context(video_feat, video_mask, sub_feat, sub_mask)
-        for m, a1, a2, am in (("video", v1, v2, video_mask), ("sub", s1, s2, sub_mask)):
-            if m not in mods:
-                continue
-            if m not in f1:
-                f1[m] = a1.new_zeros((n_videos, lpad, a1.shape[2]))
-                f2[m] = a2.new_zeros((n_videos, lpad, a2.shape[2]))
-                mk[m] = torch.zeros((n_videos, lpad), dtype=torch.float32, device=a1.device)
-            b, lb = a1.shape[0], a1.shape[1]
-            assert r + b <= n_videos and lb <= l_ref
-            if not direct:
-                f1[m][r:r + b, :lb] = a1
-                f2[m][r:r + b, :lb] = a2
-            mk[m][r:r + b, :lb] = am.float()
-        r += v1.shape[0] if v1 is not None else s1.shape[0]
+            for i, m in enumerate(("video", "sub")):
+                if m in mods:
+                    b = feats[m].shape[0]
+                    outs[2 * i], outs[2 * i + 1] = dst[0][m][r:r + b], dst[1][m][r:r + b]
+        v1, v2, s1, s2 = model.encode_context(video_feat, video_mask, sub_feat, sub_mask, outs=tuple(outs))
+        enc = {m: e for m, e in (("video", (v1, v2, video_mask)), ("sub", (s1, s2, sub_mask))) if m in mods}
+        if not known:
+            collected.append(enc)
+            continue
+        if dst is None:
+            dst = _alloc_index_rows(enc, n_videos, lpad)
+        r = _fill_index_rows(dst, r, enc, l_ref, copy=not direct)
+    if not known:
+        batch_max = max(enc[mods[0]][1].shape[1] for enc in collected)
+        l_ref = batch_max if l_ref is None else int(l_ref)
+        assert l_ref >= batch_max
+        n_videos = sum(enc[mods[0]][1].shape[0] for enc in collected)
+        dst = _alloc_index_rows(collected[0], n_videos, index_lpad(l_ref, model, ops))
+        for enc in collected:
+            r = _fill_index_rows(dst, r, enc, l_ref)
+        del collected          # (the per-batch outputs are not held through the packing passes)
     assert r == n_videos, "n_videos=%d but the batches held %d" % (n_videos, r)
-    plan = ops.q2c_pack_plan([mk[m] for m in mods]) if (hasattr(ops, "q2c_pack_plan") and lpad == 128) else None
-    feat1n, raw, ex_f32, ex_ec = {}, {}, {}, {}
+    return _finish_index(model, ops, mods, dst, int(l_ref), video_offset, n_total, keep_raw, exact_filter, length_buckets,
+                         storage.tiles if storage is not None else {})
+
+
+def _alloc_index_rows(enc, n_videos, lpad):
+    """Zero-filled index tensors for n_videos videos, dtype / width / device of the encoded batch enc."""
+    f1 = {m: a1.new_zeros((n_videos, lpad, a1.shape[2])) for m, (a1, _, _) in enc.items()}
+    f2 = {m: a2.new_zeros((n_videos, lpad, a2.shape[2])) for m, (_, a2, _) in enc.items()}
+    mk = {m: torch.zeros((n_videos, lpad), dtype=torch.float32, device=a1.device) for m, (a1, _, _) in enc.items()}
+    return f1, f2, mk
+
+
+def _fill_index_rows(dst, r, enc, l_ref, copy=True):
+    """One encoded batch, enc[m] = (feat1, feat2, mask), into rows r : r + b, columns : lb of the index tensors; returns
+    r + b.  copy=False: the encoder already wrote feat1 / feat2 there."""
+    f1, f2, mk = dst
+    for m, (a1, a2, am) in enc.items():
+        b, lb = a1.shape[0], a1.shape[1]
+        assert r + b <= mk[m].shape[0] and lb <= l_ref
+        if copy:
+            f1[m][r:r + b, :lb] = a1
+            f2[m][r:r + b, :lb] = a2
+        mk[m][r:r + b, :lb] = am.float()
+    return r + b
+
+
+def _finish_index(model, ops, mods, dst, l_ref, video_offset, n_total, keep_raw, exact_filter, length_buckets, tile_bufs):
+    """Filled index tensors -> CorpusIndex: K6's resident operand (and the exact-rank ones), valid lengths."""
+    f1, f2, mk = dst
+    # ragged corpora: one length-bucketed layout shared by the modalities (2 / 4 / 8 videos per K6 tile)
+    plan = ops.q2c_pack_plan([mk[m] for m in mods]) if (length_buckets and mk[mods[0]].shape[1] == 128) else None
+    mode = exact_mode_of(model, ops)
+    feat1n, ex_f32, ex_ec = {}, {}, {}
     for m in mods:
         if exact_filter:
-            feat1n[m], ex_f32[m], ex_ec[m] = _exact_filter_operands(f1[m], mk[m], plan, ops, exact_mode_of(model, ops))
-            if exact_mode_of(model, ops) == "f16s":
+            feat1n[m], ex_f32[m], ex_ec[m] = _exact_filter_operands(f1[m], mk[m], plan, ops, mode)
+            if mode == "f16s":
                 f2[m] = ops.split_f16_rows(f2[m])
-        else:
-            tile_buf = storage.tiles.get(m) if (storage is not None and plan is None) else None
-            kw = dict(out=tile_buf) if tile_buf is not None else {}
-            feat1n[m] = ops.pack_q2c_corpus(f1[m], mk[m], plan, normalize=True, **kw) if hasattr(ops, "pack_q2c_corpus") \
-                else ops.l2norm_rows(f1[m])
-        if keep_raw:
-            raw[m] = f1[m]
-    idx = CorpusIndex(mods, feat1n, f2, mk, l_ref, video_offset, n_total)
-    if getattr(ops, "RAGGED_ROWS", False):
-        idx.set_valid_lengths()
-    idx.raw_feat1 = raw
-    if exact_filter:
-        idx.exact = _make_exact_filter(ex_f32, ex_ec, exact_mode_of(model, ops))
+        else:       # normalised, in slice-major tiles where the persistent K6 kernel takes them (a storage's buffer: no plan)
+            feat1n[m] = ops.pack_q2c_corpus(f1[m], mk[m], plan, normalize=True,
+                                            out=tile_bufs.get(m) if plan is None else None)
+    idx = CorpusIndex(mods, feat1n, f2, mk, l_ref, video_offset, n_total).set_valid_lengths()
+    idx.raw_feat1 = dict(f1) if keep_raw else {}
+    if exact_filter:        # f16 filter: rounding errors 8x smaller than bf16's -> the certificate holds with half the candidates
+        idx.exact = ExactFilter(ex_f32, ex_ec, n_candidates=128 if (mode == "f16s" and EXACT_F16S_FILTER == "f16") else 256,
+                                mode=mode)
     return idx
 
 
@@ -370,7 +358,7 @@ def compute_context_info(model, eval_dataset, opt, ops=hip_ops):
 def stage_query_vectors(model, query_feat, query_mask, n_valid_tokens=None):
     """encode_query -> per-modality modular query vectors, in index.modalities order.
     n_valid_tokens: see XML.encode_query (host-known token count: no read-back in the packed encoder)."""
-    vq, sq = model.encode_query(query_feat, query_mask, **(dict(n_valid_tokens=n_valid_tokens) if n_valid_tokens is not None else {}))
+    vq, sq = model.encode_query(query_feat, query_mask, n_valid_tokens=n_valid_tokens)
     out = {}
     if model.use_video:
         out["video"] = vq
@@ -379,25 +367,21 @@ def stage_query_vectors(model, query_feat, query_mask, n_valid_tokens=None):
     return out
 
 
-import os as _os
 # Measured in round 4 (profiles/r04_notes.md) and NOT the default: handing K9 its selection threshold from K7 takes K9 from
 # 0.65 to 0.45-0.53 ms at the TVR shape, but the extra epilogue work costs K7 as much or more (+0.2 ms with one maximum per
 # group of 16 rows, +0.45 ms with the 8 largest rows of a pair), and at the as-trained shape the weaker bound makes K9 slower.
-RAGGED_ROWS = _os.environ.get("XML_RAGGED_ROWS", "1") == "1"     # K7 / K9 skip the zero tails of short videos (A/B: 0)
-K7_SUMMARIES = _os.environ.get("XML_K7_SUMMARIES", "0") == "1"   # vcmr_search: K7 emits per-pair candidate summaries for K9 (False: K9 makes its own first pass; A/B)
+K7_SUMMARIES = False   # vcmr_search: K7 emits per-pair candidate summaries for K9 (False: K9 makes its own first pass); a tool may set it
 K6_TIMER = None   # bench.py: callable returning (start, end) torch.cuda.Event pair recorded around each K6 launch
 
 
 def _k6(index, qn, ops, normalize_q=False):
     """One fused K6 launch over the local corpus (both modalities), bracketed by the bench's HIP events."""
     mods = index.modalities
-    if normalize_q and not getattr(ops, "Q2C_NORMALIZE_Q", False):
-        qn, normalize_q = [ops.l2norm_rows(q) for q in qn], False
-    kw = dict(normalize_q=True) if normalize_q else {}
     ev = K6_TIMER() if K6_TIMER is not None else None
     if ev:
         ev[0].record()
-    q2c = ops.q2c_scores_fused(qn, [index.feat1n[m] for m in mods], [index.mask[m] for m in mods], **kw)
+    q2c = ops.q2c_scores_fused(qn, [index.feat1n[m] for m in mods], [index.mask[m] for m in mods],
+                               normalize_q=normalize_q)
     if ev:
         ev[1].record()
     return q2c
@@ -439,10 +423,9 @@ def pack_video_allow(allowed):
         bits[:, :nv] = a
         words = (bits.reshape(r, nw, 32).astype(np.uint32) << np.arange(32, dtype=np.uint32)).sum(-1, dtype=np.uint32)
         return np.ascontiguousarray(words).view(np.int32)
-    bits = torch.zeros((r, nw * 32), dtype=torch.int64, device=a.device)
+    bits = torch.zeros((r, nw * 32), dtype=torch.bool, device=a.device)
     bits[:, :nv] = a
-    words = (bits.reshape(r, nw, 32) << torch.arange(32, device=a.device)).sum(-1)           # 0 .. 2^32 - 1
-    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
+    return hip_ops._pack_bits32(bits)
 
 
 def _check_video_allow(video_allow, index, nq):
@@ -465,10 +448,9 @@ def _allow_rows(video_allow, rows):
 
 def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None):
     """Exact-rank replacement of K6 + K8: dispatches on index.exact.mode (round-3 f32 re-score / split-f16 pipeline)."""
-    kw = dict(video_allow=video_allow) if video_allow is not None else {}
     if index.exact.mode == "f16s":
-        return stage_exact_topk_f16s(index, qvec, k, alpha, ops, defer_check, **kw)
-    return stage_exact_topk_f32(index, qvec, k, alpha, ops, **kw)
+        return stage_exact_topk_f16s(index, qvec, k, alpha, ops, defer_check, video_allow)
+    return stage_exact_topk_f32(index, qvec, k, alpha, ops, video_allow)
 
 
 def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None):
@@ -493,8 +475,6 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
         raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
                          "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
     masks = [index.mask[m] for m in mods]
-    akw = (lambda rows=None: dict(allow=_allow_rows(video_allow, rows) if rows is not None else video_allow)) \
-        if video_allow is not None else (lambda rows=None: {})
     q_sr, q_hi, eq = [], [], []
     for m in mods:
         q = qvec[m].contiguous()
@@ -510,7 +490,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
     nq, hidden = q_hi[0].shape
     filt = _k6(index, q_hi, ops)
     m_c = min(ex.n_candidates, index.n_videos)
-    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, **akw())
+    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
     rows_c = [ex.feat1n_f32[m] for m in mods]                    # SplitRows (Nv, lpad, H)
     cand_r = ops.q2c_rescore(q_sr, rows_c, masks, cand_i)
     top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
@@ -530,7 +510,8 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
         is_fail = fail.index_select(0, order) != 0
         inf_ = torch.full((), float("inf"), device=fail.device)
         thr = torch.where(is_fail, thr_all.index_select(0, order), inf_).contiguous()      # passing slots select nothing
-        cand2, cnt2 = ops.select_ge_rows(filt.index_select(0, order).contiguous(), thr, c_cap, **akw(order))
+        cand2, cnt2 = ops.select_ge_rows(filt.index_select(0, order).contiguous(), thr, c_cap,
+                                         allow=_allow_rows(video_allow, order))
         q_sub = [sr[order] for sr in q_sr]
         q_sub = [ops.SplitRows(sr.data.contiguous(), sr.inv.contiguous()) for sr in q_sub]
         full = ops.q2c_rescore(q_sub, rows_c, masks, cand2)
@@ -557,7 +538,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
                     qs = [ops.SplitRows(sr.data.index_select(0, rows).contiguous(), sr.inv.index_select(0, rows).contiguous())
                           for sr in q_sr]
                     allv = ops.q2c_rescore(qs, rows_c, masks, every.repeat(rows.numel(), 1).contiguous())
-                    fw, fi = ops.topk_rows(allv, k, alpha=alpha, **akw(rows))
+                    fw, fi = ops.topk_rows(allv, k, alpha=alpha, allow=_allow_rows(video_allow, rows))
                     top_w.index_copy_(0, rows, fw)
                     top_i.index_copy_(0, rows, fi)
                 info["n_full_rows"] = int(bad.numel())
@@ -579,8 +560,6 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
     ex = index.exact
     mods = index.modalities
-    akw = (lambda rows=None: dict(allow=_allow_rows(video_allow, rows) if rows is not None else video_allow)) \
-        if video_allow is not None else (lambda rows=None: {})
     if k > min(ex.n_candidates, index.n_videos):
         raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
                          "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
@@ -594,7 +573,7 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
         qb.append(b), eq.append(e)
     filt = _k6(index, qb, ops)
     m_c = min(ex.n_candidates, index.n_videos)
-    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, **akw())
+    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
     f32rows = [ex.feat1n_f32[m] for m in mods]
     cand_r = ops.q2c_rescore(qn, f32rows, masks, cand_i)
     top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
@@ -609,17 +588,17 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
         # score reaches T_k - eps can still enter: usually a few dozen more than M.  Re-score exactly those.
         thr = thr_all.index_select(0, rows).contiguous()
         frows = filt.index_select(0, rows).contiguous()
-        cap = int(ops.select_ge_rows(frows, thr, **akw(rows)).max())
+        cap = int(ops.select_ge_rows(frows, thr, allow=_allow_rows(video_allow, rows)).max())
         if video_allow is not None:
             cap = max(cap, k)          # (rows with fewer than k allowed videos: the list is filled up with id -1 = -inf)
         if cap <= EXACT_TIER2_CAP:
-            cand2, _ = ops.select_ge_rows(frows, thr, cap, **akw(rows))
+            cand2, _ = ops.select_ge_rows(frows, thr, cap, allow=_allow_rows(video_allow, rows))
             full = ops.q2c_rescore(qsub, f32rows, masks, cand2)                       # (-inf where a row has fewer candidates)
             fw, fi = ops.topk_rows(full, k, alpha=alpha, idx_in=cand2)
         else:   # scores so close together that the filter cannot separate them: the f32 K6 row itself
             n_full = nf
             full = ops.q2c_scores_fused(qsub, f32rows, masks)
-            fw, fi = ops.topk_rows(full, k, alpha=alpha, **akw(rows))
+            fw, fi = ops.topk_rows(full, k, alpha=alpha, allow=_allow_rows(video_allow, rows))
         top_w.index_copy_(0, rows, fw)
         top_i.index_copy_(0, rows, fi)
     info = dict(n_fail=nf, n_full_rows=n_full, fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s,
@@ -628,9 +607,8 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
 
 
 def ragged_lengths(index, ops=hip_ops, replicated=False):
-    """The valid-length array K7 / K9 take for a ragged corpus (None: full rows -- every video full length, a backend
-    without the entry, or RAGGED_ROWS switched off)."""
-    if not (RAGGED_ROWS and getattr(ops, "RAGGED_ROWS", False) and index.ragged):
+    """The valid-length array K7 / K9 take for a ragged corpus (None: every video has the full length -- full rows)."""
+    if not index.ragged:
         return None
     return index.vlen_all if replicated else index.vlen
 
@@ -687,15 +665,12 @@ def stage_span_probs(model, index, qvec, pair_vid, ops=hip_ops, zero_skipped=Tru
         q_lin = query_linears(model, index, qvec)
     merged = bool(model.config.merge_two_stream and len(mods) == 2)
     feat2, mask = (index.feat2_all, index.mask_all) if replicated else (index.feat2, index.mask)
-    if getattr(feat2[mods[0]], "dtype", None) is getattr(ops, "F16S", object()):
+    if feat2[mods[0]].dtype is ops.F16S:
         q_lin = [ops.split_f16_rows(q.float().contiguous()) for q in q_lin]      # per-row scales: q' is not normalised
     # band = (min_l, max_l) [+ pair_w]: K7 also returns the per-pair candidate summaries K9 starts from (st, ed, summ)
-    kw = dict(pair_w=pair_w, band=band) if (band is not None and hasattr(ops, "MOMENT_SUMM")) else {}
-    if vid_len is not None:
-        kw["vid_len"] = vid_len
     return ops.convse_rerank(q_lin, [feat2[m] for m in mods], [mask[m] for m in mods], pair_vid,
                              model._conv_weights(), index.l_ref, merged, model.config.conv_kernel_size, softmax=True,
-                             zero_skipped=zero_skipped, **kw)
+                             zero_skipped=zero_skipped, pair_w=pair_w, band=band, vid_len=vid_len)
 
 
 def pad_moment_tail(flat_scores, flat_indices, k_videos, l_ref, min_pred_l=None, max_pred_l=None):
@@ -744,22 +719,21 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
     holds only its allowed videos (indices in this index's numbering); a query with a < K of them ends in K - a empty slots
     (top_i -1, top_w 0, or -inf when alpha == 0), which yield no moments.  K6 still scores every video."""
     exact = None
-    akw = {}
     if video_allow is not None:
         if external_top is not None:
             raise ValueError("video_allow and external_top exclude each other: a caller's video lists replace the ranking "
                              "the mask restricts (filter the lists instead)")
-        akw = dict(video_allow=_check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0]))
+        _check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0])
     if external_top is None and index.exact is not None:
         q2c = None          # (the f32 (Nq, Nv) matrix is never formed; exact["q2c_filter"] is the bf16 pass's)
         # defer_exact_check (split-f16 exact mode): no host read-back inside the pass; out["exact"]["overflow_dev"] (device
         # bool, None when every video is a candidate) says whether the on-device second tier's capacity was exceeded
         top_w, top_i, exact = stage_exact_topk(index, qvec, min(max_vcmr_video, index.n_videos), q2c_alpha, ops,
-                                               **(dict(defer_check=True) if defer_exact_check else {}), **akw)
+                                               bool(defer_exact_check), video_allow)
     elif external_top is None:
         q2c = stage_q2c(index, qvec, ops)
         k = min(max_vcmr_video, index.n_videos)
-        top_w, top_i = ops.topk_rows(q2c, k, alpha=q2c_alpha, **(dict(allow=akw["video_allow"]) if akw else {}))
+        top_w, top_i = ops.topk_rows(q2c, k, alpha=q2c_alpha, allow=video_allow)
     else:   # external video-retrieval results replace K6/K8 (xml/inference.py:349-355): (meta idx int32, exp(alpha*s))
         q2c = None
         top_i, top_w = external_top
@@ -770,16 +744,16 @@ def stage_moments(model, index, qvec, top_w, top_i, min_pred_l=2, max_pred_l=16,
                   pad_tail=False, q_lin=None):
     """K7 + K9 on the selected (query, video) pairs -> (flat_scores (Nq, n) f32 desc, flat_indices (Nq, n) int32).
     q_lin: the query linears' outputs when the caller already has them (fork_query_linears)."""
-    if hasattr(ops, "MOMENT_SUMM") and K7_SUMMARIES:
+    if K7_SUMMARIES:
         # K7 hands K9 the 8 largest row maxima of every pair (taken while the rows were in its registers): K9 reads the
         # 1 GB of span probabilities once instead of twice
         st, ed, summ = stage_span_probs(model, index, qvec, top_i, ops, pair_w=top_w.contiguous(), band=(min_pred_l, max_pred_l))
         fs, fi = ops.moment_topk(st, ed, top_w, index.l_ref, min_pred_l, max_pred_l, max_before_nms, summ=summ)
     else:
         vl = ragged_lengths(index, ops)
-        rk = dict(pair_vid=top_i, vid_len=vl) if vl is not None else {}
         st, ed = stage_span_probs(model, index, qvec, top_i, ops, vid_len=vl, q_lin=q_lin)
-        fs, fi = ops.moment_topk(st, ed, top_w, index.l_ref, min_pred_l, max_pred_l, max_before_nms, **rk)
+        fs, fi = ops.moment_topk(st, ed, top_w, index.l_ref, min_pred_l, max_pred_l, max_before_nms, pair_vid=top_i,
+                                 vid_len=vl)
     if pad_tail:
         pad_moment_tail(fs, fi, top_i.shape[1], index.l_ref, min_pred_l, max_pred_l)
     return fs, fi
@@ -813,9 +787,9 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
                          "rows in the empty video slots of a restricted list")
     qvec = stage_query_vectors(model, query_feat, query_mask, n_valid_tokens)
-    forked = fork_query_linears(model, index, qvec, ops) if not (hasattr(ops, "MOMENT_SUMM") and K7_SUMMARIES) else None
+    forked = fork_query_linears(model, index, qvec, ops) if not K7_SUMMARIES else None
     q2c, top_w, top_i, exact = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, external_top,
-                                                defer_exact_check, **(dict(video_allow=video_allow) if video_allow is not None else {}))
+                                                defer_exact_check, video_allow)
     q_lin = None
     if forked is not None:
         q_lin, lin_done = forked
@@ -870,8 +844,6 @@ def explain_moments(model, index, query_feat, query_mask, pair_q, pair_vid, ops=
       q2c (P,)      video-level score of the pair: its entry of stage_q2c's matrix, or the re-scored f32-grade value on an
                     exact-rank index (with_q2c=False: None -- on a plain index the score costs a K6 pass over the corpus)
     Corpus shards (tvretrieval_amd.dist) are not handled: every pair_vid must lie in [0, index.n_videos)."""
-    if not hasattr(ops, "span_evidence"):
-        raise NotImplementedError("explain_moments needs a backend with span_evidence (the HIP ops)")
     mods = index.modalities
     dev = index.device
     pq, pv = _as_pairs(pair_q, "pair_q", dev), _as_pairs(pair_vid, "pair_vid", dev)
@@ -903,7 +875,7 @@ def explain_moments(model, index, query_feat, query_mask, pair_q, pair_vid, ops=
                            q2c=torch.zeros((0,), dtype=torch.float32, device=dev) if with_q2c else None))
     with torch.no_grad():
         q_lin = query_linears(model, index, qvec)
-        split = getattr(index.feat2[mods[0]], "dtype", None) is getattr(ops, "F16S", object())
+        split = index.feat2[mods[0]].dtype is ops.F16S
         if split:
             q_lin = [ops.split_f16_rows(q.float().contiguous()) for q in q_lin]      # per-row scales, as stage_span_probs
         merged = bool(model.config.merge_two_stream and n_mod == 2)
@@ -1127,10 +1099,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
             done = evt()
             done.record(main)                            # the staging set is free once the query encoder has read it
             freed[c & 1] = done
-            akw = {}
-            if video_allow is not None:
-                akw = dict(video_allow=video_allow if video_allow.shape[0] == 1 else video_allow[b:e])
-            _, tw, ti, _ = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, **akw)
+            allow = video_allow if (video_allow is None or video_allow.shape[0] == 1) else video_allow[b:e]
+            _, tw, ti, _ = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, video_allow=allow)
             qvecs.append(qvec), tws.append(tw), tis.append(ti)
         one = len(bounds) == 1
         qvec = {m: (qvecs[0][m] if one else torch.cat([q[m] for q in qvecs])) for m in qvecs[0]}

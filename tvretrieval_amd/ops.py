@@ -7,8 +7,6 @@ GPU tensor is missing -- there is no eager/CPU fallback.
 import collections
 import ctypes
 
-import os
-
 import numpy as np
 
 import torch
@@ -171,9 +169,6 @@ def check_count(v, what):
     if v < 0:
         check(v, what)
     return v
-
-
-ENCODE_INTO_INDEX = True      # attention_block(out=...) exists: inference.build_corpus_index encodes into the index tensors
 
 
 def _req_w(w, name, x):
@@ -488,16 +483,19 @@ class PackPlan(object):
         """(nv, 128) binary f32 mask -> (2 * n_tiles, 4) int32: the masks of every wave tile's 128 packed columns."""
         flat = torch.cat([(mask != 0).reshape(-1), torch.zeros(1, dtype=torch.bool, device=mask.device)])
         rm = self.row_map.long()
-        v = flat[torch.where(rm >= 0, rm, torch.full_like(rm, flat.numel() - 1))]
-        w = (v.view(-1, 4, 32).to(torch.int64) << torch.arange(32, device=mask.device, dtype=torch.int64)).sum(-1)
-        return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
+        return _pack_bits32(flat[torch.where(rm >= 0, rm, torch.full_like(rm, flat.numel() - 1))].view(-1, 128))
+
+
+def _pack_bits32(bits):
+    """(..., 32 k) bool or 0/1 tensor -> (..., k) int32 words: bit j of word w is element 32 w + j."""
+    w = bits.reshape(bits.shape[:-1] + (-1, 32)).to(torch.int64) << torch.arange(32, device=bits.device, dtype=torch.int64)
+    w = w.sum(-1)                                                  # 0 .. 2^32 - 1
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
 
 
 def q2c_pack_plan(masks):
     """PackPlan for the corpus with these per-modality (Nv, 128) clip masks, or None when packing does not apply
-    (non-binary masks, full-length corpus, fewer than 5 % of the clip rows to save, XML_Q2C_NO_BUCKETS=1 for A/B runs)."""
-    if os.environ.get("XML_Q2C_NO_BUCKETS") or os.environ.get("XML_Q2C_KEEP_MASKS") or os.environ.get("XML_Q2C_ROW_MAJOR"):
-        return None
+    (non-binary masks, full-length corpus, fewer than 5 % of the clip rows to save)."""
     for m in masks:
         if m.shape[1] != 128 or not bool(((m == 0) | (m == 1)).all()):
             return None
@@ -512,91 +510,79 @@ def q2c_tiled_ok(lpad, hidden, dtype):
     return dtype in _DT and bool(_lib.load().xml_q2c_tiled_ok(int(lpad), int(hidden), dt_of(dtype)))
 
 
-def q2c_tile_rows(x):
-    """(..., H) contiguous rows -> TiledRows (K6 operand layout)."""
-    _req(x, "x")
-    hidden = x.shape[-1]
-    rows = x.numel() // hidden
-    nbytes = _lib.load().xml_q2c_tiled_bytes(rows, hidden, dt_of(x))
-    data = torch.empty(nbytes // x.element_size(), dtype=x.dtype, device=x.device)
-    check(_lib.load().xml_q2c_tile_rows(_p(x), _p(data), rows, hidden, dt_of(x), _stream()), "xml_q2c_tile_rows")
-    return TiledRows(data, rows, hidden, x.shape)
-
-
 def q2c_tiled_numel(rows, hidden, dtype):
     """Elements of the K6 tile image of (rows, hidden) rows of `dtype`, 0 when the tiled kernel does not take the shape."""
-    if not q2c_tiled_ok(128, hidden, dtype) or os.environ.get("XML_Q2C_ROW_MAJOR"):
+    if not q2c_tiled_ok(128, hidden, dtype):
         return 0
     return int(_lib.load().xml_q2c_tiled_bytes(rows, hidden, _DT[dtype])) // torch.empty(0, dtype=dtype).element_size()
 
 
-def pack_q2c_corpus(feat1n, mask=None, plan=None, normalize=False, out=None):
-    """Resident form of the similarity operand: slice-major tiles when the persistent kernel takes it, else as is.
-    mask (Nv, Lpad): if every entry is 1 (full-length videos) the tiles are marked all_valid and K6 skips the masks.
-    plan (q2c_pack_plan over ALL modalities' masks): the length-bucketed image instead.
-    normalize: feat1n holds the UN-normalised clip features; F.normalize runs inside the tiling pass
-    (xml_q2c_tile_rows_l2norm: bitwise the values of l2norm_rows followed by the tiling, one pass over the index less)."""
+def _tile(x, rows_dst, row_map=None, normalize=False, out=None, rows_src=None):
+    """The K6 tile image of rows_dst rows (rounded up to whole 256-row tiles) made from the (..., H) rows of x: destination
+    row i holds source row row_map[i] (-1: a zero row), or row i without a map; normalize: F.normalize inside the pass.
+    out: caller-owned flat buffer of exactly the image's size.  rows_src: x is the head of a longer contiguous buffer."""
     lib = _lib.load()
-    fused = normalize and lib.xml_q2c_tile_rows_l2norm_ok(feat1n.shape[2], dt_of(feat1n)) \
-        and q2c_tiled_ok(feat1n.shape[1], feat1n.shape[2], feat1n.dtype) and not os.environ.get("XML_Q2C_ROW_MAJOR")
-    if normalize and not fused:
-        feat1n = l2norm_rows(feat1n)
-    if plan is not None and q2c_tiled_ok(feat1n.shape[1], feat1n.shape[2], feat1n.dtype):
-        _req(feat1n, "feat1n")
-        nv, lpad, hidden = feat1n.shape
-        rows_packed = plan.n_tiles * 256
-        data = torch.empty(rows_packed * hidden, dtype=feat1n.dtype, device=feat1n.device)
-        if fused:
-            check(lib.xml_q2c_tile_rows_l2norm(_p(feat1n), _p(plan.row_map), _p(data), nv * lpad, rows_packed, hidden,
-                                               dt_of(feat1n), _stream()), "xml_q2c_tile_rows_l2norm")
-        else:
-            check(lib.xml_q2c_tile_rows_gather(_p(feat1n), _p(plan.row_map), _p(data), rows_packed, hidden,
-                                               dt_of(feat1n), _stream()), "xml_q2c_tile_rows_gather")
-        t = TiledRows(data, nv * lpad, hidden, feat1n.shape)
-        t.plan = plan
-        t.mask_bits = plan.mask_bits(mask)
-        return t
-    if q2c_tiled_ok(feat1n.shape[1], feat1n.shape[2], feat1n.dtype) and not os.environ.get("XML_Q2C_ROW_MAJOR"):
-        if fused:
-            hidden = feat1n.shape[-1]
-            rows = feat1n.numel() // hidden
-            nbytes = lib.xml_q2c_tiled_bytes(rows, hidden, dt_of(feat1n))
-            if out is not None:            # caller-owned tile buffer (inference.IndexStorage)
-                _req(out, "out", feat1n.dtype)
-                assert out.numel() == nbytes // feat1n.element_size()
-                data = out
-            else:
-                data = torch.empty(nbytes // feat1n.element_size(), dtype=feat1n.dtype, device=feat1n.device)
-            check(lib.xml_q2c_tile_rows_l2norm(_p(feat1n), None, _p(data), rows, nbytes // (hidden * feat1n.element_size()),
-                                               hidden, dt_of(feat1n), _stream()), "xml_q2c_tile_rows_l2norm")
-            t = TiledRows(data, rows, hidden, feat1n.shape)
-        else:
-            t = q2c_tile_rows(feat1n)         # (XML_Q2C_ROW_MAJOR=1: keep rows, for A/B measurements)
-        keep = os.environ.get("XML_Q2C_KEEP_MASKS")      # 1: float masks (4-slot kernel), for A/B measurements
-        t.all_valid = mask is not None and bool((mask == 1).all()) and not keep
-        if mask is not None and not t.all_valid and not keep and mask.shape[1] == 128 \
-                and bool(((mask == 0) | (mask == 1)).all()):
-            w = (mask.view(-1, 4, 32) != 0).to(torch.int64) << torch.arange(32, device=mask.device, dtype=torch.int64)
-            w = w.sum(-1)
-            t.mask_bits = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()
-        return t
-    return feat1n
+    hidden, dt = x.shape[-1], dt_of(x)
+    rows = x.numel() // hidden if rows_src is None else rows_src
+    n = lib.xml_q2c_tiled_bytes(rows_dst, hidden, dt) // x.element_size()
+    if out is None:
+        out = torch.empty(n, dtype=x.dtype, device=x.device)
+    else:
+        _req(out, "out", x.dtype)
+        assert out.numel() == n
+    if normalize:
+        check(lib.xml_q2c_tile_rows_l2norm(_p(x), _p(row_map), _p(out), rows, n // hidden, hidden, dt, _stream()),
+              "xml_q2c_tile_rows_l2norm")
+    elif row_map is not None:
+        check(lib.xml_q2c_tile_rows_gather(_p(x), _p(row_map), _p(out), n // hidden, hidden, dt, _stream()),
+              "xml_q2c_tile_rows_gather")
+    else:
+        assert rows_dst == rows
+        check(lib.xml_q2c_tile_rows(_p(x), _p(out), rows, hidden, dt, _stream()), "xml_q2c_tile_rows")
+    return TiledRows(out, rows, hidden, x.shape)
+
+
+def q2c_tile_rows(x):
+    """(..., H) contiguous rows -> TiledRows (K6 operand layout)."""
+    _req(x, "x")
+    return _tile(x, x.numel() // x.shape[-1])
 
 
 def q2c_tile_rows_l2norm(x):
     """F.normalize(x, dim=-1) + the K6 tile layout in ONE pass (xml_q2c_tile_rows_l2norm; bitwise l2norm_rows then
     q2c_tile_rows), or None when the fused pass does not take the shape."""
     _req(x, "x")
-    lib = _lib.load()
-    hidden = x.shape[-1]
-    if not lib.xml_q2c_tile_rows_l2norm_ok(hidden, dt_of(x)):
+    if not _lib.load().xml_q2c_tile_rows_l2norm_ok(x.shape[-1], dt_of(x)):
         return None
-    rows = x.numel() // hidden
-    nbytes = lib.xml_q2c_tiled_bytes(rows, hidden, dt_of(x))
-    data = torch.empty(nbytes // x.element_size(), dtype=x.dtype, device=x.device)
-    check(lib.xml_q2c_tile_rows_l2norm(_p(x), None, _p(data), rows, nbytes // (hidden * x.element_size()), hidden, dt_of(x),
-                                       _stream()), "xml_q2c_tile_rows_l2norm")
-    return TiledRows(data, rows, hidden, x.shape)
+    return _tile(x, x.numel() // x.shape[-1], normalize=True)
+
+
+def pack_q2c_corpus(feat1n, mask=None, plan=None, normalize=False, out=None):
+    """Resident form of the similarity operand: slice-major tiles when the persistent kernel takes it, else as is.
+    mask (Nv, Lpad): if every entry is 1 (full-length videos) the tiles are marked all_valid and K6 skips the masks;
+    binary masks are packed into bit words, any other mask (or None) stays the float mask K6 is handed per call.
+    plan (q2c_pack_plan over ALL modalities' masks): the length-bucketed image instead.
+    normalize: feat1n holds the UN-normalised clip features; F.normalize runs inside the tiling pass
+    (xml_q2c_tile_rows_l2norm: bitwise the values of l2norm_rows followed by the tiling, one pass over the index less).
+    out: caller-owned buffer for the plain (plan-less) tile image (inference.IndexStorage.tiles)."""
+    nv, lpad, hidden = feat1n.shape
+    tiled = q2c_tiled_ok(lpad, hidden, feat1n.dtype)
+    fused = normalize and tiled and bool(_lib.load().xml_q2c_tile_rows_l2norm_ok(hidden, dt_of(feat1n)))
+    if normalize and not fused:
+        feat1n = l2norm_rows(feat1n)
+    if not tiled:
+        return feat1n
+    _req(feat1n, "feat1n")
+    if plan is not None:
+        t = _tile(feat1n, plan.n_tiles * 256, plan.row_map, fused)
+        t.plan = plan
+        t.mask_bits = plan.mask_bits(mask)
+        return t
+    t = _tile(feat1n, nv * lpad, None, fused, out)
+    t.all_valid = mask is not None and bool((mask == 1).all())
+    if mask is not None and not t.all_valid and bool(((mask == 0) | (mask == 1)).all()):
+        t.mask_bits = _pack_bits32(mask != 0)
+    return t
 
 
 _pair_maps = {}
@@ -623,11 +609,8 @@ def q2c_tile_rows_l2norm_pair(q0, q1):
         m, j = i // r, i % r
         rmap = torch.where(j < nq, m * nq + j, torch.full_like(i, -1)).contiguous()
         _pair_maps[key] = rmap
-    es = q0.element_size()
-    half = lib.xml_q2c_tiled_bytes(nq, hidden, dt_of(q0)) // es
-    data = torch.empty(2 * half, dtype=q0.dtype, device=q0.device)
-    check(lib.xml_q2c_tile_rows_l2norm(_p(q0), _p(rmap), _p(data), 2 * nq, 2 * r, hidden, dt_of(q0), _stream()),
-          "xml_q2c_tile_rows_l2norm")
+    half = lib.xml_q2c_tiled_bytes(nq, hidden, dt_of(q0)) // q0.element_size()
+    data = _tile(q0, 2 * r, rmap, True, rows_src=2 * nq).data
     return [TiledRows(data[:half], nq, hidden, q0.shape), TiledRows(data[half:], nq, hidden, q0.shape)]
 
 
@@ -763,8 +746,6 @@ def merge_shard_topk(recv_score, recv_id, k, alpha=0.0):
     return vals, idx
 
 
-Q2C_NORMALIZE_Q = True  # q2c_scores_fused(normalize_q=True) exists
-RAGGED_ROWS = True     # convse_rerank(vid_len=) / moment_topk(pair_vid=, vid_len=) exist (xml_convse_rerank_ex, xml_moment_topk_ex)
 MOMENT_SUMM = 8        # XML_MOMENT_SUMM
 
 
@@ -881,7 +862,7 @@ def moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=None, pair_vid=None,
     """K9/K10.  st, ed (Nq, K, Lpad) f32 probabilities; w (Nq, K) f32 or None.
     summ (Nq, K, 8) f32: the candidate summaries convse_rerank(..., band=(min_l, max_l), pair_w=w) returned for THESE rows.
     pair_vid (Nq, K) int32 + vid_len (Nv,) int32: the rows came from convse_rerank(..., vid_len=vid_len) -- entries beyond a
-    video's valid length were not written and are not read.
+    video's valid length were not written and are not read.  vid_len=None (full rows): pair_vid is not looked at.
     Returns (scores (Nq, n_out) f32 desc, flat (Nq, n_out) int32 = (r*l_ref + i)*l_ref + j, -1 = empty)."""
     _req(st, "st", torch.float32); _req(ed, "ed", torch.float32)
     if w is not None:
@@ -890,8 +871,9 @@ def moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=None, pair_vid=None,
     if summ is not None:
         _req(summ, "summ", torch.float32)
         assert tuple(summ.shape) == (nq, kpairs, MOMENT_SUMM)
-    assert (pair_vid is None) == (vid_len is None)
-    if vid_len is not None:
+    if vid_len is None:
+        pair_vid = None
+    else:
         _req(pair_vid, "pair_vid", torch.int32); _req(vid_len, "vid_len", torch.int32)
         assert tuple(pair_vid.shape) == (nq, kpairs)
     sc = torch.empty((nq, n_out), dtype=torch.float32, device=st.device)
