@@ -487,6 +487,37 @@ int xml_ingest_rows(const void* src, int src_dt, const int64_t* row_start, void*
                     int lmax, int d, int max_len, float eps, int normalize, xml_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training batches from a device-resident feature store: one stream (video, subtitle or query tokens) of a training batch
+ * in ONE launch, from rows that stay on the device in the store's dtype.  The host sends n example ids per step.
+ *   replaces StartEndDataset.__getitem__ (xml/start_end_dataset.py:94-145: truncate to max_len, l2_normalize_np_array,
+ *   the temporal endpoint feature of lines 127-142), start_end_collate / pad_sequences_1d (xml/start_end_dataset.py:346-359)
+ *   and the host-to-device copy of prepare_batch_inputs (xml/start_end_dataset.py:362-370).
+ *   src (rows_total, d) XML_F32 or XML_F16, resident; row_start (n_items + 1) int64 DEVICE: item j = rows
+ *   [row_start[j], row_start[j + 1]); ids (n) int32 DEVICE: batch position i takes example ids[i];
+ *   item_of (n_examples) int32 DEVICE: example -> item, or NULL: ids are item ids
+ *   dst (n, lmax, d + 2 * tef) XML_F32 or XML_BF16 (the f32 result rounded to nearest even); mask (n, lmax) f32 or NULL;
+ *   len_out (n) int32 or NULL
+ * Batch position i, item = item_of ? item_of[ids[i]] : ids[i], len = min(rows of the item, max_len, lmax):
+ *   rows l < len: store row row_start[item] + l as f32, divided by (||x||_2 + eps) when normalize; with tef = 1 columns d and
+ *   d + 1 hold (float)l / (float)len and that plus (float)(1.0 / (double)len) -- bit for bit torch's arange(0, L, 1.0) / L and
+ *   tef_st + 1.0 / L on the CPU; they are not normalised.  Rows l >= len are zero in every column.  mask[i, l] = l < len.
+ *   An id outside [0, n_examples) or an item outside [0, n_items) gives len = 0 (zero rows, zero mask): no out-of-range read.
+ * A row's bits do not depend on its batch position, on n, on lmax or on the other examples of the batch.
+ * XML_ERR_BAD_ARG: null src / row_start / ids / dst; n, lmax, d, max_len, n_items <= 0; n_examples <= 0 with item_of; dtypes
+ * outside the lists above; tef or normalize not 0 / 1; eps NaN.  XML_ERR_UNSUPPORTED: d > 4096.
+ * No workspace, no allocation, no host synchronisation; capturable; re-entrant per stream.
+ * --------------------------------------------------------------------------------------------- */
+int xml_gather_feature_rows(const void* src, int src_dt, const int64_t* row_start, int64_t n_items, const int32_t* ids, int n,
+                            const int32_t* item_of, int64_t n_examples, void* dst, int dst_dt, float* mask, int32_t* len_out,
+                            int lmax, int d, int max_len, float eps, int normalize, int tef, xml_stream_t stream);
+
+/* dst[i, :] = src[ids[i], :] for an (n_rows, w) int64 table, zeros for an id outside [0, n_rows): the (N, 2) start / end label
+ * table -> the batch's st_ed_indices (torch.stack of get_st_ed_label's results, xml/start_end_dataset.py:147-162,356-358).
+ * src, ids (int32), dst on the device.  XML_ERR_BAD_ARG: null pointers, w, n, n_rows <= 0.  XML_ERR_UNSUPPORTED: w > 4096. */
+int xml_gather_index_rows(const int64_t* src, int w, int64_t n_rows, const int32_t* ids, int n, int64_t* dst,
+                          xml_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * K10: the index tail of compute_query2ctx_info as a device epilogue -- one 16-byte record per list entry, so a query batch
  * leaves the device in ONE copy and the host never loops over queries or list entries.
  *   replaces np.unravel_index(flat, (max_n_videos, max_ctx_l, max_ctx_l)), sorted_q2c_indices[i, local],

@@ -482,6 +482,57 @@ def gen_ingest_case(ns, name, seed, n, dims, max_l, bsz):
     print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
+def gen_train_collate_case(ns, name, seed):
+    """Training collate: what the reference's StartEndDataset.__getitem__ (xml/start_end_dataset.py:94-145), start_end_collate
+    and prepare_batch_inputs (346-370) hand to the model.  The dataset object is made with __new__ (its __init__ opens h5
+    files) and the three handlers are plain dicts of arrays.  9 examples over 5 videos of 7, 1, 44, 40 and 23 clips with
+    max_ctx_len 40 (one video truncated, one with a single clip), descriptions of 1-9 tokens with max_desc_len 6, `ts` values
+    that hit both clamps of get_st_ed_label, two examples on one video in a batch, a full batch of 6 and a tail of 3.
+    Stored: the raw arrays + lengths, the example table, and per (mode, normalisation) each batch's tensors."""
+    from baselines.crossmodal_moment_localization import start_end_dataset as sed
+    rng = np.random.default_rng(seed)
+    vlens, dims, max_ctx_len, max_desc_len, clip_length, bsz = [7, 1, 44, 40, 23], (48, 32, 32), 40, 6, 1.5, 6
+    vids = ["vid_%d" % i for i in range(len(vlens))]
+    qlens = [4, 1, 9, 6, 3, 7, 2, 5, 8]
+    ex_vid = [0, 1, 2, 0, 4, 1, 3, 0, 1]
+    #      inside      one clip    end beyond the cut   start in the last clip   ...
+    ts = [[1.6, 6.1], [0.0, 1.2], [30.0, 64.5], [9.1, 10.4], [0.0, 34.5], [0.7, 1.4], [58.6, 59.9], [3.0, 4.5], [0.2, 0.9]]
+    data = [dict(desc_id=100 + i, desc="query %d" % i, vid_name=vids[ex_vid[i]], duration=float(vlens[ex_vid[i]] * clip_length),
+                 ts=ts[i]) for i in range(len(qlens))]
+    raw = dict(video={v: (rng.standard_normal((l, dims[0])) * rng.uniform(0.05, 3.0)).astype(np.float32)
+                      for v, l in zip(vids, vlens)},
+               sub={v: (rng.standard_normal((l, dims[1])) * rng.uniform(0.05, 3.0)).astype(np.float32)
+                    for v, l in zip(vids, vlens)},
+               desc={str(e["desc_id"]): rng.standard_normal((l, dims[2])).astype(np.float32) for e, l in zip(data, qlens)})
+    raw["video"][vids[0]][2] = 0.0                              # an all-zero clip: x / (0 + eps) stays 0
+    out = dict(examples=np.array(json.dumps(data)), vlens=np.array(vlens, dtype=np.int64), qlens=np.array(qlens, dtype=np.int64),
+               dims=np.array(dims, dtype=np.int64), max_ctx_len=np.int64(max_ctx_len), max_desc_len=np.int64(max_desc_len),
+               clip_length=np.float64(clip_length), bsz=np.int64(bsz))
+    out["raw/video"] = np.concatenate([raw["video"][v] for v in vids], 0)
+    out["raw/sub"] = np.concatenate([raw["sub"][v] for v in vids], 0)
+    out["raw/desc"] = np.concatenate([raw["desc"][str(e["desc_id"])] for e in data], 0)
+    cases = [("video_sub", True), ("video_sub", False), ("video_sub_tef", True), ("video_tef", False), ("sub", True)]
+    out["cases"] = np.array(json.dumps(cases))
+    for mode, norm in cases:
+        ds = sed.StartEndDataset.__new__(sed.StartEndDataset)
+        ds.dset_name, ds.data, ds.ctx_mode = "tvr", data, mode
+        ds.max_desc_len, ds.max_ctx_len, ds.clip_length = max_desc_len, max_ctx_len, clip_length
+        ds.use_video, ds.use_sub, ds.use_tef = "video" in mode, "sub" in mode, "tef" in mode
+        ds.vid_feat_h5, ds.sub_bert_h5, ds.desc_bert_h5 = raw["video"], raw["sub"], raw["desc"]
+        ds.normalize_vfeat = ds.normalize_tfeat = norm
+        for b in range(0, len(data), bsz):
+            _, batched = sed.start_end_collate([ds[i] for i in range(b, min(b + bsz, len(data)))])
+            inputs = sed.prepare_batch_inputs(batched, torch.device("cpu"))
+            for k, v in inputs.items():
+                used = dict(tef=ds.use_tef, video=ds.use_video, sub=ds.use_sub).get(k.split("_")[0], True)
+                if not used:
+                    continue                                    # (2, 2) placeholders of an unused stream
+                out["%s/%s/batch%d/%s" % (mode, "norm" if norm else "raw", b // bsz, k)] = v.numpy()
+    path = os.path.join(OUT_DIR, name + ".npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 def gen_visualization_case(ns, name, cfg, seed, n, len_lo, len_hi, lq_lo, lq_hi):
     """XML.get_visualization_data (xml/model_xml.py:253-289) on a batch of n (query, video) examples: the modular
     attention weights and the per-clip evidence behind the span logits.  The reference returns a list of per-example dicts
@@ -550,7 +601,7 @@ def main():
     if only:      # regenerate a subset: python tools/make_golden.py train_step
         g = globals()
         for fn in ("gen_model_case", "gen_pipeline_case", "gen_external_vr_case", "gen_eval_case", "gen_train_case",
-                   "gen_ingest_case", "gen_visualization_case"):
+                   "gen_ingest_case", "gen_train_collate_case", "gen_visualization_case"):
             orig = g[fn]
             g[fn] = (lambda o: lambda ns, name, *a, **k: o(ns, name, *a, **k) if only in name else None)(orig)
     ap = argparse.ArgumentParser()
@@ -592,6 +643,7 @@ def main():
                              cross_att=False, merge_two_stream=False, ranking_loss_type="lse", use_hard_negative=True,
                              hard_pool_size=3), 32, bsz=7, len_lo=5, len_hi=19)
     gen_ingest_case(ns, "ingest_collate", 51, n=11, dims=(48, 32), max_l=40, bsz=4)
+    gen_train_collate_case(ns, "train_collate", 52)
     # staged: two steps without the span loss, then three with it (t_total 10, warmup 0.1: the late tensors see multiplier
     # 0 at THEIR step 0 while the early ones are already decaying)
     gen_train_case(ns, "train_step_staged_video_sub_h128",

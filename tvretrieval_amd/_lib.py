@@ -132,6 +132,9 @@ SIGNATURES = {
     "xml_conv1d_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "xml_ingest_rows": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
                                 c_void_p]),
+    "xml_gather_feature_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int,
+                                        c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p]),
+    "xml_gather_index_rows": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "xml_moments_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int,
                                    c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "xml_nms_moments": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int,

@@ -316,6 +316,57 @@ def ingest_rows(src, row_start, n, lmax, max_len, normalize=True, eps=1e-5, out_
     return out, mask
 
 
+def gather_feature_rows(src, row_start, ids, lmax, max_len, item_of=None, normalize=True, eps=1e-5, tef=False,
+                        out_dtype=torch.float32, out=None, mask_out=None, len_out=None, want_len=True):
+    """One stream of a training batch from a device-resident ragged store (xml_gather_feature_rows): src (rows, d) f32 / f16,
+    row_start (n_items + 1,) int64, ids (n,) int32 example ids, item_of (n_examples,) int32 example -> item or None (ids are
+    item ids) -> (features (n, lmax, d + 2 * tef) [x / (||x|| + eps) per row, the temporal endpoint columns, zero padding],
+    mask (n, lmax) f32, lengths (n,) int32 or None with want_len=False).  out / mask_out / len_out: existing tensors to write
+    into."""
+    _req(src, "src"); _req(row_start, "row_start", torch.int64); _req(ids, "ids", torch.int32)
+    if src.dtype not in (torch.float32, torch.float16) or src.dim() != 2:
+        raise _lib.XmlHipError("src: expected (rows, d) float32 or float16")
+    n, d = int(ids.numel()), int(src.shape[1])
+    dd = d + (2 if tef else 0)
+    if item_of is not None:
+        _req(item_of, "item_of", torch.int32)
+    for t, name, shape, dtype in ((out, "out", (n, int(lmax), dd), None), (mask_out, "mask_out", (n, int(lmax)), torch.float32),
+                                  (len_out, "len_out", (n,), torch.int32)):
+        if t is not None:
+            _req(t, name, dtype)
+            if tuple(t.shape) != shape:
+                raise _lib.XmlHipError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+    if out is None:
+        out = torch.empty((n, int(lmax), dd), dtype=out_dtype, device=src.device)
+    if mask_out is None:
+        mask_out = torch.empty((n, int(lmax)), dtype=torch.float32, device=src.device)
+    if len_out is None and want_len:
+        len_out = torch.empty((n,), dtype=torch.int32, device=src.device)
+    check(_lib.load().xml_gather_feature_rows(
+        _p(src), dt_of(src), _p(row_start), row_start.numel() - 1, _p(ids), n, _p(item_of),
+        0 if item_of is None else item_of.numel(), _p(out), dt_of(out), _p(mask_out), _p(len_out), int(lmax), d, int(max_len),
+        float(eps), int(bool(normalize)), int(bool(tef)), _stream()), "xml_gather_feature_rows")
+    return out, mask_out, len_out
+
+
+def gather_index_rows(table, ids, out=None):
+    """out[i, :] = table[ids[i], :] for an (n_rows, w) int64 table and int32 ids, zeros for an id out of range
+    (xml_gather_index_rows): the (N, 2) start / end labels -> the batch's st_ed_indices."""
+    _req(table, "table", torch.int64); _req(ids, "ids", torch.int32)
+    if table.dim() != 2:
+        raise _lib.XmlHipError("table: expected (n_rows, w)")
+    n, w = int(ids.numel()), int(table.shape[1])
+    if out is None:
+        out = torch.empty((n, w), dtype=torch.int64, device=table.device)
+    else:
+        _req(out, "out", torch.int64)
+        if tuple(out.shape) != (n, w):
+            raise _lib.XmlHipError("out: expected shape %s, got %s" % ((n, w), tuple(out.shape)))
+    check(_lib.load().xml_gather_index_rows(_p(table), w, int(table.shape[0]), _p(ids), n, _p(out), _stream()),
+          "xml_gather_index_rows")
+    return out
+
+
 def add_layernorm(a, b, g, beta, out_dtype=None):
     _req(a, "a"); _req(g, "g", torch.float32); _req(beta, "beta", torch.float32)
     out_dtype = out_dtype or (b.dtype if b is not None else a.dtype)
