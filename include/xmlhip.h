@@ -540,6 +540,45 @@ int xml_moments_decode(const int32_t* flat, const float* score, const int32_t* t
                        const int32_t* meta2vid, int nq, int n, int64_t ld_in, int k, int l_ref, float clip_length,
                        int seconds, xml_moment* out, int64_t ld_out, int32_t* out_count, xml_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Videos longer than max_ctx_l: indexed in parts, ranked by the best part.
+ * A video of n > W = max_ctx_l clips is stored as 1 + ceil((n - W) / (W - O)) overlapping PARTS of W clips (offsets 0, S, 2S,
+ * ... while offset + W < n, S = W - O, and one last part at n - W), adjacent index rows in offset order; a video of n <= W
+ * clips is one part.  Each part is encoded, stored and scored exactly as a stand-alone video of its clips, so every heavy
+ * kernel runs unchanged on the rows.  With O >= max_pred_l every candidate moment of the video lies inside some part.
+ *
+ *   xml_group_best_allow: the fold between K6 and K8.  scores (rows, n_parts) f32, row stride ld; part_video (n_parts) int32
+ *     = source video of each index row; group_start (n_videos + 1) int32 = CSR over the index rows (video v owns rows
+ *     group_start[v] .. group_start[v + 1] - 1); video_allow NULL or (allow_rows = 1 | rows, allow_ld >= ceil(n_videos / 32))
+ *     words over SOURCE videos in xml_topk_rows_allowed's bit layout; out_bits (rows, out_ld >= ceil(n_parts / 32)) words in
+ *     the same layout over INDEX ROWS: bit p is set iff p is the best part of its video for that row and the video is allowed;
+ *     the padding bits of the last word are 0 (words beyond ceil(n_parts / 32) are not written).  Handing out_bits to
+ *     xml_topk_rows_allowed gives a list in which every video appears at most once, by its best part.
+ *     Best part of a video: the running best starts as (its first row, -inf) and a later row replaces it when its score is
+ *     strictly greater -- the maximum, ties to the lowest row; a NaN never wins; a video whose scores are all -inf / NaN is
+ *     represented by its first row.
+ *   xml_best_part_rows: the same question for ONE named video per row (SVMR, ground-truth videos): video (rows) int32 source
+ *     ids -> out (rows) int32 = index row of that video's best part, -1 for an id outside [0, n_videos).
+ *   Both: at most one pass over the scores (the score of a video's only part decides nothing and is not read), no workspace, no allocation, no host synchronisation, capturable.
+ *     XML_ERR_BAD_ARG before any launch: null scores / tables / outputs, rows < 0, n_parts or n_videos <= 0, n_videos > n_parts,
+ *     ld < n_parts (xml_best_part_rows: ld < n_videos), out_ld or allow_ld too small, allow_rows not 1 or rows.  rows == 0:
+ *     returns 0 and launches nothing.
+ *   xml_moments_decode_parts: xml_moments_decode on an index of parts.  part_offset (index rows) int32 = first clip of each
+ *     row in its source video (not NULL); it is added to st_idx and ed_idx as integers, before the float conversion, in both
+ *     the seconds and the clip-unit form -- a record is what xml_moments_decode emits for those clip indices in an unsplit
+ *     video, with the same roundings.  meta2vid maps the index row to the caller's id of the SOURCE video.  Everything else,
+ *     the INT32_MAX guard included, is xml_moments_decode (which runs the same kernel without offsets).
+ * --------------------------------------------------------------------------------------------- */
+int xml_group_best_allow(const float* scores, int64_t ld, int rows, int n_parts, const int32_t* part_video,
+                         const int32_t* group_start, int n_videos, const uint32_t* video_allow, int64_t allow_ld,
+                         int allow_rows, uint32_t* out_bits, int64_t out_ld, xml_stream_t stream);
+int xml_best_part_rows(const float* scores, int64_t ld, int rows, const int32_t* group_start, int n_videos,
+                       const int32_t* video, int32_t* out, xml_stream_t stream);
+int xml_moments_decode_parts(const int32_t* flat, const float* score, const int32_t* top_idx, const int32_t* row_vid,
+                             const int32_t* meta2vid, const int32_t* part_offset, int nq, int n, int64_t ld_in, int k,
+                             int l_ref, float clip_length, int seconds, xml_moment* out, int64_t ld_out, int32_t* out_count,
+                             xml_stream_t stream);
+
 /* K11: greedy temporal NMS of K10's records ON THE DEVICE -- the semantics of xml_nms_vcmr_host / xml_nms_svmr_host (below) on
  * device-resident xml_moment rows, one more launch behind xml_moments_decode; the host entries stay the default path.
  *   in   (nq, n) xml_moment, row stride ld_in >= n records, 16-byte aligned; row q holds count[q] valid records as a prefix

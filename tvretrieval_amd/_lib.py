@@ -137,6 +137,12 @@ SIGNATURES = {
     "xml_gather_index_rows": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "xml_moments_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int,
                                    c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    # ---- long videos indexed in parts (parts.hip, decode.hip) ----
+    "xml_group_best_allow": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int,
+                                     c_void_p, c_int64, c_void_p]),
+    "xml_best_part_rows": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "xml_moments_decode_parts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64,
+                                         c_int, c_int, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "xml_nms_moments": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int,
                                 c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "xml_eval_moments": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,

@@ -12,8 +12,9 @@ namespace {
 // one workgroup per query row; n <= 1024 entries walked 256 at a time
 __global__ __launch_bounds__(256) void moments_decode_kernel(
     const int32_t* __restrict__ flat, const float* __restrict__ score, const int32_t* __restrict__ top_idx,
-    const int32_t* __restrict__ row_vid, const int32_t* __restrict__ meta2vid, int n, int64_t ld_in, int k, int l_ref,
-    float clip, int seconds, xml_moment* __restrict__ out, int64_t ld_out, int32_t* __restrict__ out_count) {
+    const int32_t* __restrict__ row_vid, const int32_t* __restrict__ meta2vid, const int32_t* __restrict__ part_offset,
+    int n, int64_t ld_in, int k, int l_ref, float clip, int seconds, xml_moment* __restrict__ out, int64_t ld_out,
+    int32_t* __restrict__ out_count) {
   const int q = blockIdx.x, tid = threadIdx.x;
   const int ll = l_ref * l_ref;
   int valid = 0;
@@ -25,8 +26,13 @@ __global__ __launch_bounds__(256) void moments_decode_kernel(
       const int32_t f = flat[(int64_t)q * ld_in + i];
       if (f >= 0) {
         const int r = f / ll, rem = f - r * ll;
-        const int si = rem / l_ref, ei = rem - si * l_ref;
+        int si = rem / l_ref, ei = rem - si * l_ref;
         int meta = top_idx ? top_idx[(int64_t)q * k + r] : (row_vid ? row_vid[q] : r);
+        if (part_offset && meta >= 0) {      // index row of a PART: clip indices of the whole video (integers, before the
+          const int off = part_offset[meta]; //  float conversion: the record of an unsplit video, with the same roundings)
+          si += off;
+          ei += off;
+        }
         m.vid = (meta2vid && meta >= 0) ? meta2vid[meta] : meta;
         if (seconds) {     // numpy float32 arithmetic: one rounding per operation.  hipcc contracts a * b + c into an fma
 #pragma clang fp contract(off)   // by default (-ffp-contract=fast, and HIP's __fmul_rn / __fadd_rn are plain operators)
@@ -59,9 +65,10 @@ __global__ __launch_bounds__(256) void moments_decode_kernel(
 
 }  // namespace
 
-extern "C" int xml_moments_decode(const int32_t* flat, const float* score, const int32_t* top_idx, const int32_t* row_vid,
-                                  const int32_t* meta2vid, int nq, int n, int64_t ld_in, int k, int l_ref, float clip_length,
-                                  int seconds, xml_moment* out, int64_t ld_out, int32_t* out_count, xml_stream_t stream) {
+static int moments_decode(const int32_t* flat, const float* score, const int32_t* top_idx, const int32_t* row_vid,
+                          const int32_t* meta2vid, const int32_t* part_offset, int nq, int n, int64_t ld_in, int k, int l_ref,
+                          float clip_length, int seconds, xml_moment* out, int64_t ld_out, int32_t* out_count,
+                          xml_stream_t stream) {
   XML_ENTER();
   static_assert(sizeof(xml_moment) == 16, "xml_moment is a 16-byte record");
   if (!score || !out || nq <= 0 || n <= 0 || ld_in < n || ld_out < n) return XML_ERR_BAD_ARG;
@@ -70,7 +77,25 @@ extern "C" int xml_moments_decode(const int32_t* flat, const float* score, const
   if (((uintptr_t)out & 15) != 0) return XML_ERR_BAD_ARG;
   if (flat && (int64_t)l_ref * l_ref * (top_idx ? k : 1) > INT32_MAX) return XML_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(moments_decode_kernel, dim3(nq), dim3(256), 0, (hipStream_t)stream, flat, score, top_idx, row_vid,
-                     meta2vid, n, ld_in, k, l_ref, clip_length, seconds, out, ld_out, out_count);
+                     meta2vid, part_offset, n, ld_in, k, l_ref, clip_length, seconds, out, ld_out, out_count);
   XML_CHECK_LAUNCH();
   return XML_OK;
+}
+
+extern "C" int xml_moments_decode(const int32_t* flat, const float* score, const int32_t* top_idx, const int32_t* row_vid,
+                                  const int32_t* meta2vid, int nq, int n, int64_t ld_in, int k, int l_ref, float clip_length,
+                                  int seconds, xml_moment* out, int64_t ld_out, int32_t* out_count, xml_stream_t stream) {
+  return moments_decode(flat, score, top_idx, row_vid, meta2vid, nullptr, nq, n, ld_in, k, l_ref, clip_length, seconds, out,
+                        ld_out, out_count, stream);
+}
+
+// K10 on an index of parts (parts.hip): part_offset (index rows) int32 = first clip of each row in its source video, added to
+// st_idx / ed_idx; meta2vid then maps the index row to the SOURCE video's id.  flat == NULL (the VR list) has no clips to shift.
+extern "C" int xml_moments_decode_parts(const int32_t* flat, const float* score, const int32_t* top_idx,
+                                        const int32_t* row_vid, const int32_t* meta2vid, const int32_t* part_offset, int nq,
+                                        int n, int64_t ld_in, int k, int l_ref, float clip_length, int seconds,
+                                        xml_moment* out, int64_t ld_out, int32_t* out_count, xml_stream_t stream) {
+  if (!part_offset) return XML_ERR_BAD_ARG;
+  return moments_decode(flat, score, top_idx, row_vid, meta2vid, part_offset, nq, n, ld_in, k, l_ref, clip_length, seconds,
+                        out, ld_out, out_count, stream);
 }

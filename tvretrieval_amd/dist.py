@@ -120,6 +120,9 @@ def check_shards(index, group=None):
     """Collective validation of the shard layout, once per index: every rank learns every rank's shard size, and an empty
     shard raises on ALL ranks.  (Raised only where the shard is empty, the error would leave the other ranks waiting in
     the next collective: a hang instead of a failure.)"""
+    if getattr(index, "parts", None) is not None:
+        raise ValueError("a parts index (build_corpus_index(parts=)) cannot be a corpus shard: the sharded drivers merge "
+                         "per-shard video lists and know nothing of parts that fold into one video")
     if getattr(index, "_shards_checked", False):
         return
     world = dist.get_world_size(group) if dist.is_initialized() else 1

@@ -28,8 +28,9 @@ and the sharded drivers call:
   moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=, pair_vid=, vid_len=)
   F16S                                                    the dtype sentinel of split-f16 models and rows
 The split-f16 exact mode (split_f16_rows, SplitRows, F16_UNIT_LOG2), explain_moments (span_evidence), the device-side result
-records (moments_decode, nms_moments) and vcmr_search_host (ingest_rows) call further entries of tvretrieval_amd.ops; a
-backend without them serves every search that does not ask for those.
+records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and searches on an index of parts (group_best_allow,
+best_part_rows, moments_decode(part_offset=)) call further entries of tvretrieval_amd.ops; a backend without them serves
+every search that does not ask for those.
 """
 import numpy as np
 import torch
@@ -72,6 +73,10 @@ class CorpusIndex(object):
         # fetches the clip rows nor writes the (exactly zero) probabilities beyond it, K9 does not read them
         self.vlen = self.vlen_all = None
         self.ragged = False
+        # long videos indexed in parts (build_corpus_index(parts=)): the device ingest.PartTable; rows
+        # of the index are then PARTS (n_videos keeps meaning index rows) and n_source_videos the videos they fold back into
+        self.parts = None
+        self.n_source_videos = self.n_videos
 
     def set_valid_lengths(self):
         """Per-video valid length from the masks (one small device pass + one host read at build time)."""
@@ -219,7 +224,7 @@ class IndexStorage(object):
 
 
 def build_corpus_index(model, context_batches, ops=hip_ops, keep_raw=False, video_offset=0, n_total=None,
-                        l_ref=None, n_videos=None, exact_filter=False, storage=None, length_buckets=True):
+                        l_ref=None, n_videos=None, exact_filter=False, storage=None, length_buckets=True, parts=None):
     """Encode context batches and assemble the resident index.
 
     context_batches: iterable of (video_feat, video_mask, sub_feat, sub_mask) device tensors (unused modality:
@@ -234,7 +239,20 @@ def build_corpus_index(model, context_batches, ops=hip_ops, keep_raw=False, vide
     the encoded batches are collected, n_videos / l_ref (the batch maximum) follow from them, and the same rows are filled.
     exact_filter=True (f32 model): exact-rank mode -- feat1n becomes the bf16 filter image, index.exact the f32 operands
     (ExactFilter); vcmr_search then returns the f32 path's lists at close to the bf16 path's speed.
-    length_buckets=False: a ragged corpus keeps the plain two-videos-per-tile K6 image (A/B against the bucketed one)."""
+    length_buckets=False: a ragged corpus keeps the plain two-videos-per-tile K6 image (A/B against the bucketed one).
+    parts (ingest.PartTable, host or device): the batches hold the PARTS of videos longer than max_ctx_l, in the table's row
+    order (ingest.ContextFeeder(parts=)); every part is encoded and stored as a stand-alone video.  The index gets
+    index.parts (the table on the device) and index.n_source_videos; index.n_videos stays the number of index rows.  Searches
+    then rank a video by its best part and report moments in whole-video time (vcmr_search)."""
+    if parts is not None:
+        if exact_filter:
+            raise ValueError("build_corpus_index: parts= and exact_filter=True exclude each other -- exact-rank mode never "
+                             "forms the f32 (Nq, rows) score matrix that the best part of a video is taken from")
+        if video_offset or (n_total is not None and int(n_total) != parts.n_parts):
+            raise ValueError("build_corpus_index: a parts index is not a corpus shard (video_offset / n_total)")
+        if n_videos is not None and int(n_videos) != parts.n_parts:
+            raise ValueError("build_corpus_index: n_videos = %d, but the part table has %d index rows (n_videos counts rows)"
+                             % (n_videos, parts.n_parts))
     mods = [n for n, u in (("video", model.use_video), ("sub", model.use_sub)) if u]
     dst = None                    # (feat1, feat2, mask): per-modality (n_videos, lpad, H) x2 and (n_videos, lpad) f32
     if storage is not None:       # (zero-filled by IndexStorage; used for ONE build)
@@ -273,8 +291,17 @@ def build_corpus_index(model, context_batches, ops=hip_ops, keep_raw=False, vide
             r = _fill_index_rows(dst, r, enc, l_ref)
         del collected          # (the per-batch outputs are not held through the packing passes)
     assert r == n_videos, "n_videos=%d but the batches held %d" % (n_videos, r)
-    return _finish_index(model, ops, mods, dst, int(l_ref), video_offset, n_total, keep_raw, exact_filter, length_buckets,
-                         storage.tiles if storage is not None else {})
+    if parts is not None and r != parts.n_parts:
+        raise ValueError("build_corpus_index: the batches held %d rows, the part table has %d parts" % (r, parts.n_parts))
+    index = _finish_index(model, ops, mods, dst, int(l_ref), video_offset, n_total, keep_raw, exact_filter, length_buckets,
+                          storage.tiles if storage is not None else {})
+    if parts is not None:
+        if index.l_ref > parts.max_ctx_len:
+            raise ValueError("build_corpus_index: rows of %d clips, but the part table was planned for max_ctx_len = %d"
+                             % (index.l_ref, parts.max_ctx_len))
+        index.parts = parts.to(index.device)
+        index.n_source_videos = parts.n_videos
+    return index
 
 
 def _alloc_index_rows(enc, n_videos, lpad):
@@ -429,14 +456,44 @@ def pack_video_allow(allowed):
 
 
 def _check_video_allow(video_allow, index, nq):
-    """video_allow of a search over index for nq queries: int32 words on the index's device, 1 or nq rows."""
-    nw = (index.n_videos + 31) // 32
+    """video_allow of a search over index for nq queries: int32 words on the index's device, 1 or nq rows.  On a parts index
+    the bits number SOURCE videos."""
+    nv = index.n_source_videos if index.parts is not None else index.n_videos
+    nw = (nv + 31) // 32
     if not torch.is_tensor(video_allow) or video_allow.dtype != torch.int32 or video_allow.dim() != 2:
         raise ValueError("video_allow must be a 2-D int32 tensor of bit words (pack_video_allow)")
     if video_allow.shape[1] < nw or video_allow.shape[0] not in (1, nq):
         raise ValueError("video_allow must be (1 | %d, >= %d) words for %d videos and %d queries, got %s"
-                         % (nq, nw, index.n_videos, nq, tuple(video_allow.shape)))
+                         % (nq, nw, nv, nq, tuple(video_allow.shape)))
     return video_allow
+
+
+def _parts_meta2vid(index, meta2vid):
+    """K10's table of a parts index, index row -> the caller's id of the source video (PartTable.meta2vid), composed once per
+    ids tensor and kept on the index: the same tensor, unchanged since (same object, same version), is served from there."""
+    if meta2vid is None or not torch.is_tensor(meta2vid):
+        return index.parts.meta2vid(meta2vid)
+    kept = index.__dict__.get("_parts_meta2vid")
+    if kept is None or kept[0] is not meta2vid or kept[1] != meta2vid._version:
+        kept = (meta2vid, meta2vid._version, index.parts.meta2vid(meta2vid))
+        index._parts_meta2vid = kept
+    return kept[2]
+
+
+def _check_parts_search(index, max_pred_l, external_top=None, pad_tail=False):
+    """What a search on a parts index cannot do, each with its reason."""
+    if external_top is not None:
+        raise ValueError("external_top on a parts index: a caller's lists name index rows and would bypass the fold that lets "
+                         "only the best part of a video compete (rank the source videos with the index instead)")
+    if index.exact is not None:
+        raise ValueError("a parts index cannot be an exact-rank index (exact_filter=True): no f32 score matrix exists to "
+                         "take the best part of a video from")
+    if int(max_pred_l) > index.parts.overlap:
+        raise ValueError("max_pred_l = %d exceeds the part overlap of %d clips: a moment of that length need not lie inside "
+                         "one part (plan_parts(overlap=) must be >= max_pred_l)" % (max_pred_l, index.parts.overlap))
+    if pad_tail:
+        raise ValueError("pad_tail=True on a parts index: the reference-shaped tail would have to invent rows in the video "
+                         "slots that stay empty once every video is counted once")
 
 
 def _allow_rows(video_allow, rows):
@@ -717,13 +774,23 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
     top_i (Nq, K) int32, exact-rank info or None).  Per query independent of the rest of the batch.
     video_allow (pack_video_allow's words, 1 or Nq rows, on the device): every query's list is the list of the corpus that
     holds only its allowed videos (indices in this index's numbering); a query with a < K of them ends in K - a empty slots
-    (top_i -1, top_w 0, or -inf when alpha == 0), which yield no moments.  K6 still scores every video."""
+    (top_i -1, top_w 0, or -inf when alpha == 0), which yield no moments.  K6 still scores every video.
+    A parts index: K6, then ops.group_best_allow (each video's best part AND the caller's mask over source videos), then K8 under
+    those bits -- top_i are index rows, one per video; slots beyond the number of allowed videos are empty."""
     exact = None
     if video_allow is not None:
         if external_top is not None:
             raise ValueError("video_allow and external_top exclude each other: a caller's video lists replace the ranking "
                              "the mask restricts (filter the lists instead)")
         _check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0])
+    if index.parts is not None:
+        # long videos in parts: K6 scores every part, the fold keeps each video's best part (and the caller's mask, which
+        # numbers source videos), K8 ranks those -- the restricted search over the index rows, one row per video
+        _check_parts_search(index, 0, external_top)
+        q2c = stage_q2c(index, qvec, ops)
+        best = ops.group_best_allow(q2c, index.parts, video_allow)
+        top_w, top_i = ops.topk_rows(q2c, min(max_vcmr_video, index.n_videos), alpha=q2c_alpha, allow=best)
+        return q2c, top_w, top_i, None
     if external_top is None and index.exact is not None:
         q2c = None          # (the f32 (Nq, Nv) matrix is never formed; exact["q2c_filter"] is the bf16 pass's)
         # defer_exact_check (split-f16 exact mode): no host read-back inside the pass; out["exact"]["overflow_dev"] (device
@@ -782,10 +849,22 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     record_count (K10 of flat_scores / flat_indices: (Nq, n, 4) int32 xml_moment rows in seconds, (Nq,) int32) and nms_records
     (Nq, max_after_nms, 4) / nms_index (Nq, max_after_nms) positions in `records` / nms_count (Nq,) = filter_vcmr_by_nms of
     them; with svmr_video also svmr_records / svmr_record_count (clip units) and svmr_nms_records / svmr_nms_index /
-    svmr_nms_count = post_processing_svmr_nms on the spans scaled by clip_length in float64."""
+    svmr_nms_count = post_processing_svmr_nms on the spans scaled by clip_length in float64.
+    A parts index (build_corpus_index(parts=): videos longer than max_ctx_l stored as overlapping parts): a video is ranked by
+    its best part, and the result is by definition the restricted search over the index rows that allows exactly each query's
+    best parts (ANDed with video_allow, whose bits then number SOURCE videos).  top_indices / flat_indices stay in index rows
+    (K7, K9 and explain_moments need them); out["top_videos"] (Nq, K) int32 names the source videos; records carry the source
+    video's id (meta2vid: source video -> id) and whole-video times (the part's clip offset is added in K10); svmr_video names
+    source videos, out["svmr_rows"] the index rows that stood for them.  Refused with a ValueError: external_top, pad_tail=True,
+    an exact-rank index, max_pred_l > parts.overlap (such a moment need not lie inside one part)."""
     if video_allow is not None and pad_tail:
         raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
                          "rows in the empty video slots of a restricted list")
+    parts = index.parts
+    pkw = {}
+    if parts is not None:
+        _check_parts_search(index, max_pred_l, external_top, pad_tail)
+        meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=parts.part_offset)
     qvec = stage_query_vectors(model, query_feat, query_mask, n_valid_tokens)
     forked = fork_query_linears(model, index, qvec, ops) if not K7_SUMMARIES else None
     q2c, top_w, top_i, exact = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, external_top,
@@ -798,13 +877,19 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     out = dict(q2c=q2c, top_scores=top_w, top_indices=top_i, flat_scores=fs, flat_indices=fi)
     if exact is not None:
         out["exact"] = exact
+    if parts is not None:       # (index plumbing: the source video of every listed row, -1 in the empty slots)
+        out["top_videos"] = torch.where(top_i >= 0, parts.part_video[top_i.clamp_min(0).long()], top_i)
     if nms_thd is not None:
         rec, cnt = ops.moments_decode(fs, flat=fi, top_idx=top_i, meta2vid=meta2vid, l_ref=index.l_ref,
-                                      clip_length=clip_length, seconds=True)
+                                      clip_length=clip_length, seconds=True, **pkw)
         nrec, nidx, ncnt = ops.nms_moments(rec, cnt, True, nms_thd, max_before=max_before_nms, max_after=max_after_nms)
         out.update(records=rec, record_count=cnt, nms_records=nrec, nms_index=nidx, nms_count=ncnt)
     if svmr_video is not None:
-        pv = svmr_video.to(torch.int32).reshape(-1, 1).contiguous()
+        pv = svmr_video.to(torch.int32).reshape(-1).contiguous()
+        if parts is not None:       # a SOURCE video per query: its best part for that query stands for it (-1: unknown id)
+            pv = ops.best_part_rows(q2c, parts, pv)
+            out["svmr_rows"] = pv
+        pv = pv.reshape(-1, 1)
         st1, ed1 = stage_span_probs(model, index, qvec, pv, ops, q_lin=q_lin)
         ss, sf = ops.moment_topk(st1, ed1, None, index.l_ref, min_pred_l, max_pred_l, max_before_nms)
         if pad_tail:
@@ -812,7 +897,7 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         out.update(svmr_scores=ss, svmr_flat=sf, svmr_st=st1[:, 0], svmr_ed=ed1[:, 0])
         if nms_thd is not None:
             rec, cnt = ops.moments_decode(ss, flat=sf, row_vid=pv.reshape(-1), meta2vid=meta2vid, l_ref=index.l_ref,
-                                          seconds=False)
+                                          seconds=False, **pkw)
             nrec, nidx, ncnt = ops.nms_moments(rec, cnt, False, nms_thd, scale=clip_length, max_before=max_before_nms,
                                                max_after=max_after_nms)
             out.update(svmr_records=rec, svmr_record_count=cnt, svmr_nms_records=nrec, svmr_nms_index=nidx,
@@ -1013,6 +1098,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     dev = next(model.parameters()).device
     ragged = row_start is not None
     nq = (row_start.numel() - 1) if ragged else query_feat.shape[0]
+    if index.parts is not None:
+        _check_parts_search(index, max_pred_l, None, pad_tail)
     if video_allow is not None:
         if pad_tail:
             raise ValueError("video_allow and pad_tail=True exclude each other (see vcmr_search)")
@@ -1044,7 +1131,10 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
         buffers.last_done.synchronize()                  # (the pass before the previous one: normally long finished)
     main = torch.cuda.current_stream(dev)
     side = buffers.copy_stream
-    if meta2vid is None:
+    pkw = {}
+    if index.parts is not None:      # records name source videos, in whole-video time (see vcmr_search)
+        meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=index.parts.part_offset)
+    elif meta2vid is None:
         meta2vid = torch.arange(index.n_videos, dtype=torch.int32, device=dev)
     copied, freed = [None, None], buffers.freed
     ev_h2d = []
@@ -1110,7 +1200,7 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
         t1, t2, t2b, t3 = evt(), evt(), evt(), torch.cuda.Event(enable_timing=timings is not None)
         t1.record(main)
         ops.moments_decode(fs, flat=fi, top_idx=top_i, meta2vid=meta2vid, l_ref=index.l_ref, clip_length=clip_length,
-                           seconds=True, out=buffers.rec_dev, out_count=buffers.cnt_dev)
+                           seconds=True, out=buffers.rec_dev, out_count=buffers.cnt_dev, **pkw)
         t2.record(main)
         rec_src, cnt_src, t_out = buffers.rec_dev, buffers.cnt_dev, t2
         if nms_thd is not None:
@@ -1160,6 +1250,10 @@ class GraphedVcmrSearch(object):
             raise ValueError("GraphedVcmrSearch: video_allow_rows must be None, 1 or nq = %d, got %r" % (nq, video_allow_rows))
         if "video_allow" in search_kwargs:
             raise ValueError("GraphedVcmrSearch: pass video_allow_rows= here and the mask itself to every call")
+        if getattr(index, "parts", None) is not None:
+            raise ValueError("GraphedVcmrSearch: a parts index (build_corpus_index(parts=)) is not captured yet -- the fold and "
+                             "K10 with offsets need no host round trip, but the captured pass has not been verified; use "
+                             "vcmr_search or vcmr_search_host")
         if index.exact is not None and index.exact.mode != "f16s":
             raise ValueError("the f32 exact-rank mode reads its certificate on the host (the fallback's launch shape "
                              "depends on it): not capturable -- build the index from an ops.F16S model")

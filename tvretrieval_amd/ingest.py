@@ -84,6 +84,116 @@ class FeatureStore(object):
 _TORCH_DT = {"float16": torch.float16, "float32": torch.float32}
 
 
+class PartTable(object):
+    """Which index rows make up which video, for corpora with videos longer than max_ctx_len.
+    A long video is stored as several overlapping PARTS, each an ordinary index row of <= max_ctx_len clips; the parts of a
+    video are adjacent rows, in offset order.
+      part_video  (n_parts,)      int32  source video of each index row
+      part_offset (n_parts,)      int32  first clip of the row in its source video
+      part_len    (n_parts,)      int32  clips of the row
+      group_start (n_videos + 1,) int32  CSR over the index rows: video v owns rows group_start[v] : group_start[v + 1]
+    plan_parts() makes the host table (numpy arrays); .to(device) returns the copy with int32 tensors on that device, which is
+    what build_corpus_index(parts=) keeps on the index and the device ops take."""
+
+    def __init__(self, part_video, part_offset, part_len, group_start, max_ctx_len, overlap):
+        on_device = torch.is_tensor(part_video)
+        if on_device:
+            pv, po, pl, gs = (t.detach().cpu().numpy() for t in (part_video, part_offset, part_len, group_start))
+        else:
+            pv, po, pl, gs = (np.asarray(a) for a in (part_video, part_offset, part_len, group_start))
+        self.max_ctx_len, self.overlap = int(max_ctx_len), int(overlap)
+        if self.max_ctx_len < 1 or not 0 <= self.overlap < self.max_ctx_len:
+            raise ValueError("PartTable: 0 <= overlap < max_ctx_len is required, got overlap %d, max_ctx_len %d"
+                             % (self.overlap, self.max_ctx_len))
+        for a, name in ((pv, "part_video"), (po, "part_offset"), (pl, "part_len"), (gs, "group_start")):
+            if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("PartTable: %s must be a 1-D integer array" % name)
+        n_parts, n_videos = len(pv), len(gs) - 1
+        if n_videos < 1 or len(po) != n_parts or len(pl) != n_parts:
+            raise ValueError("PartTable: part_video / part_offset / part_len must have one entry per part and group_start "
+                             "n_videos + 1 >= 2 entries; got %d / %d / %d / %d" % (len(pv), len(po), len(pl), len(gs)))
+        if gs[0] != 0 or gs[-1] != n_parts or (np.diff(gs) < 1).any():
+            raise ValueError("PartTable: group_start must rise strictly from 0 to n_parts = %d (every video has a part)"
+                             % n_parts)
+        if not np.array_equal(pv, np.repeat(np.arange(n_videos), np.diff(gs))):
+            raise ValueError("PartTable: the parts of a video must be adjacent index rows, videos in order: part_video must "
+                             "equal the video of each row's group_start range")
+        if (pl < 1).any() or (pl > self.max_ctx_len).any() or (po < 0).any():
+            raise ValueError("PartTable: every part needs 1 <= part_len <= max_ctx_len = %d and part_offset >= 0"
+                             % self.max_ctx_len)
+        first = gs[:-1]
+        inner = np.ones(n_parts, dtype=bool)
+        inner[first] = False
+        if (po[first] != 0).any() or (np.diff(po)[inner[1:]] < 1).any():
+            raise ValueError("PartTable: the parts of a video must start at offset 0 and follow in rising offset order")
+        if on_device:
+            self.part_video, self.part_offset, self.part_len, self.group_start = (
+                t.to(torch.int32).contiguous() for t in (part_video, part_offset, part_len, group_start))
+        else:
+            self.part_video, self.part_offset, self.part_len, self.group_start = (
+                np.ascontiguousarray(a, dtype=np.int32) for a in (pv, po, pl, gs))
+        self.n_parts, self.n_videos = int(n_parts), int(n_videos)
+
+    @property
+    def device(self):
+        return self.part_video.device if torch.is_tensor(self.part_video) else None
+
+    def n_clips(self):
+        """(n_videos,) clips of each source video = end of its last part (host array)."""
+        po, pl, gs = (np.asarray(t.cpu() if torch.is_tensor(t) else t) for t in (self.part_offset, self.part_len, self.group_start))
+        last = gs[1:] - 1
+        return (po[last] + pl[last]).astype(np.int32)
+
+    def to(self, device):
+        """The table with int32 tensors on `device` (already validated: the copy is not checked again)."""
+        t = object.__new__(PartTable)
+        t.__dict__.update(self.__dict__)
+        t.part_video, t.part_offset, t.part_len, t.group_start = (
+            torch.as_tensor(a, dtype=torch.int32).to(device).contiguous()
+            for a in (self.part_video, self.part_offset, self.part_len, self.group_start))
+        return t
+
+    def meta2vid(self, video_ids=None):
+        """K10's table for an index of parts: index row -> the caller's id of its source video.  video_ids (n_videos,)
+        int32, source video -> id (None: the source-video number itself); array or tensor on the table's side."""
+        if video_ids is None:
+            return self.part_video
+        if torch.is_tensor(self.part_video):
+            ids = torch.as_tensor(video_ids, dtype=torch.int32).to(self.part_video.device)
+            if ids.dim() != 1 or ids.numel() != self.n_videos:
+                raise ValueError("PartTable.meta2vid: %d ids for %d source videos" % (ids.numel(), self.n_videos))
+            return ids.index_select(0, self.part_video.long()).contiguous()
+        ids = np.asarray(video_ids.cpu() if torch.is_tensor(video_ids) else video_ids, dtype=np.int32)
+        if ids.ndim != 1 or len(ids) != self.n_videos:
+            raise ValueError("PartTable.meta2vid: %d ids for %d source videos" % (ids.size, self.n_videos))
+        return np.ascontiguousarray(ids[self.part_video])
+
+
+def plan_parts(n_clips, max_ctx_len, overlap=16):
+    """The part plan of a corpus: n_clips (n_videos,) clips per video -> PartTable (host).
+    W = max_ctx_len, O = overlap, S = W - O.  A video of n <= W clips is one part (0, n); a video of n > W clips gets parts of
+    W clips at offsets 0, S, 2S, ... for every offset with offset + W < n, and one last part at n - W: 1 + ceil((n - W) / S)
+    parts.  Every window of <= O clips of the video (K9's candidates: at most max_pred_l <= O clips) lies inside a part."""
+    w, o = int(max_ctx_len), int(overlap)
+    if w < 1 or not 0 <= o < w:
+        raise ValueError("plan_parts: 0 <= overlap < max_ctx_len is required, got overlap %d, max_ctx_len %d" % (o, w))
+    n = np.asarray(n_clips)
+    if n.ndim != 1 or n.size < 1 or not np.issubdtype(n.dtype, np.integer) or (n < 1).any():
+        raise ValueError("plan_parts: n_clips must be a non-empty 1-D integer array of clip counts >= 1")
+    n = n.astype(np.int64)
+    s = w - o
+    count = np.where(n > w, 1 + (np.maximum(n - w, 0) + s - 1) // s, 1)
+    gs = np.concatenate([[0], np.cumsum(count)])
+    if gs[-1] > np.iinfo(np.int32).max:
+        raise ValueError("plan_parts: %d parts do not fit int32 row numbers" % gs[-1])
+    pv = np.repeat(np.arange(len(n)), count)
+    j = np.arange(gs[-1]) - gs[:-1][pv]                       # number of the part inside its video
+    nv = n[pv]
+    po = np.where(j == count[pv] - 1, np.maximum(nv - w, 0), j * s)
+    pl = np.minimum(nv, w)
+    return PartTable(pv.astype(np.int32), po.astype(np.int32), pl.astype(np.int32), gs.astype(np.int32), w, o)
+
+
 class ContextFeeder(object):
     """Raw clip rows leave the host in the STORE's dtype (f16 on disk: half the PCIe bytes of the reference's f32 batches)
     and back to back -- runs of videos that are adjacent in the store are ONE copy from the memory map into the pinned
@@ -94,12 +204,31 @@ class ContextFeeder(object):
 
     def __init__(self, video_names, video_store=None, sub_store=None, max_ctx_len=100, batch_size=200,
                  normalize_vfeat=True, normalize_tfeat=True, device="cuda:0", ops=hip_ops, feature_dtype=torch.float32,
-                 host_threads=8):
+                 host_threads=8, parts=None):
         """feature_dtype=torch.bfloat16 (bf16 models only): the normalised features are handed over in bf16 -- the encoder's
-        input LayerNorm reads half the bytes (the C ABI takes f32 or the compute dtype); the reference's contract is f32."""
+        input LayerNorm reads half the bytes (the C ABI takes f32 or the compute dtype); the reference's contract is f32.
+        parts (PartTable of plan_parts over these videos' clip counts, host): nothing is cut off -- the feeder iterates batches
+        of PARTS, each the rows [offset, offset + len) of its video in the store; rows that two parts share are copied twice."""
         self.feature_dtype = feature_dtype
         self.names, self.vs, self.ss = list(video_names), video_store, sub_store
         self.max_ctx_len, self.bsz = int(max_ctx_len), int(batch_size)
+        self.parts = parts
+        if parts is not None:
+            if torch.is_tensor(parts.part_video):
+                raise ValueError("ContextFeeder: parts must be the host table (plan_parts), not its device copy")
+            if parts.n_videos != len(self.names) or parts.max_ctx_len != self.max_ctx_len:
+                raise ValueError("ContextFeeder: the part table covers %d videos at max_ctx_len %d, the feeder %d at %d"
+                                 % (parts.n_videos, parts.max_ctx_len, len(self.names), self.max_ctx_len))
+            counts = parts.n_clips()
+            for tag, store in (("video", video_store), ("sub", sub_store)):
+                if store is None:
+                    continue
+                have = np.array([store.index[n][1] for n in self.names], dtype=np.int64)
+                if (have != counts).any():
+                    i = int(np.nonzero(have != counts)[0][0])
+                    raise ValueError("ContextFeeder: the part table was planned for %d clips of %r, the %s store holds %d "
+                                     "(with parts, the video and subtitle stores must hold the same clip count per video)"
+                                     % (counts[i], self.names[i], tag, have[i]))
         self.norm = dict(video=normalize_vfeat, sub=normalize_tfeat)
         self.device, self.ops = torch.device(device), ops
         self._stage = {}
@@ -108,25 +237,32 @@ class ContextFeeder(object):
         self.host_threads = max(1, int(host_threads))
         self.stats = dict(rows=0, h2d_bytes=0, gather_s=0.0)
 
+    def _n_items(self):
+        return len(self.names) if self.parts is None else self.parts.n_parts
+
     def __len__(self):
-        return (len(self.names) + self.bsz - 1) // self.bsz
+        return (self._n_items() + self.bsz - 1) // self.bsz
 
     def _staging(self, key, rows, store):
         buf = self._stage.get(key)
         if buf is None or buf.shape[0] < rows:
-            cap = max(rows, min(self.bsz, len(self.names)) * self.max_ctx_len)
+            cap = max(rows, min(self.bsz, self._n_items()) * self.max_ctx_len)
             buf = torch.empty((cap, store.dim), dtype=_TORCH_DT[store.dtype])
             if self.device.type == "cuda":
                 buf = buf.pin_memory()
             self._stage[key] = buf
         return buf
 
-    def _gather(self, store, names, slot, tag):
-        """-> (pinned (rows, D) buffer in the store dtype holding the batch's truncated videos back to back, rows,
-        row_start (n + 1) int64, lmax)"""
+    def _gather(self, store, items, slot, tag):
+        """items: the batch's video names, or with a part table its range of index rows -> (pinned (rows, D) buffer in the
+        store dtype holding the batch's truncated videos (or parts) back to back, rows, row_start (n + 1) int64, lmax)"""
         import time
         t0 = time.perf_counter()
-        idx = [store.index[n] for n in names]
+        if self.parts is None:
+            idx = [store.index[n] for n in items]
+        else:       # a part is the sub-range [first + offset, + len) of its video's rows
+            pt = self.parts
+            idx = [[store.index[self.names[pt.part_video[p]]][0] + int(pt.part_offset[p]), int(pt.part_len[p])] for p in items]
         lens = np.minimum(np.array([i[1] for i in idx], dtype=np.int64), self.max_ctx_len)
         start = np.concatenate([[0], np.cumsum(lens)])
         rows = int(start[-1])
@@ -163,8 +299,8 @@ class ContextFeeder(object):
     def __iter__(self):
         cuda = self.device.type == "cuda"
         copy_stream = torch.cuda.Stream(self.device) if cuda else None
-        for bi, b in enumerate(range(0, len(self.names), self.bsz)):
-            names = self.names[b:b + self.bsz]
+        for bi, b in enumerate(range(0, self._n_items(), self.bsz)):
+            names = self.names[b:b + self.bsz] if self.parts is None else range(b, min(b + self.bsz, self.parts.n_parts))
             out = []
             for tag, store in (("video", self.vs), ("sub", self.ss)):
                 if store is None:

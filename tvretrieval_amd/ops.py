@@ -934,13 +934,77 @@ def moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=None, pair_vid=None,
     return sc, fl
 
 
+def _parts_args(scores, parts, what):
+    """Validate a device part table (ingest.PartTable.to(device)) against a (rows, n_parts) score matrix."""
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise _lib.XmlHipError("%s: scores must be a tensor on the GPU; the HIP path has no CPU fallback" % what)
+    if scores.dtype != torch.float32:
+        raise _lib.XmlHipError("%s: scores: expected dtype torch.float32, got %s" % (what, scores.dtype))
+    if scores.dim() != 2 or (scores.shape[1] > 1 and scores.stride(1) != 1):
+        raise ValueError("%s: scores must be a (rows, n_parts) f32 matrix with unit column stride, got %s strides %s"
+                         % (what, tuple(scores.shape), tuple(scores.stride())))
+    for name in ("part_video", "group_start"):
+        t = getattr(parts, name, None)
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError("%s: parts.%s must be a contiguous 1-D int32 tensor (ingest.PartTable.to(device))" % (what, name))
+        if t.device != scores.device:
+            raise ValueError("%s: parts.%s is on %s, the scores are on %s" % (what, name, t.device, scores.device))
+    n_parts, n_videos = int(parts.part_video.numel()), int(parts.group_start.numel()) - 1
+    if n_videos < 1 or n_parts < n_videos:
+        raise ValueError("%s: a part table of %d videos in %d parts" % (what, n_videos, n_parts))
+    if scores.shape[1] != n_parts:
+        raise ValueError("%s: scores have %d columns, the part table has %d index rows" % (what, scores.shape[1], n_parts))
+    if scores.shape[0] and scores.stride(0) < n_parts:
+        raise ValueError("%s: score row stride %d < %d columns" % (what, scores.stride(0), n_parts))
+    return n_parts, n_videos
+
+
+def group_best_allow(scores, parts, video_allow=None):
+    """The fold of a parts index between K6 and K8 (xml_group_best_allow).  scores (rows, n_parts) f32 (row stride >= n_parts);
+    parts: device part table (part_video (n_parts,) / group_start (n_videos + 1,) int32); video_allow None or
+    (1 | rows, >= ceil(n_videos / 32)) int32 words over SOURCE videos (inference.pack_video_allow).
+    -> (rows, ceil(n_parts / 32)) int32 words over index rows: bit p set iff p is its video's best part for that row (maximum,
+    ties to the lowest row, NaN never wins) and the video is allowed -- topk_rows(scores, k, allow=) of it ranks videos."""
+    n_parts, n_videos = _parts_args(scores, parts, "group_best_allow")
+    rows = scores.shape[0]
+    allow_ld = allow_rows = 0
+    if video_allow is not None:
+        video_allow, _ = _allow_args(video_allow, 0, rows, n_videos, scores.device, "group_best_allow")
+        allow_ld, allow_rows = video_allow.stride(0), video_allow.shape[0]
+    out = torch.empty((rows, (n_parts + 31) // 32), dtype=torch.int32, device=scores.device)
+    check(_lib.load().xml_group_best_allow(_p(scores), scores.stride(0) if rows else n_parts, rows, n_parts,
+                                           _p(parts.part_video), _p(parts.group_start), n_videos, _p(video_allow), allow_ld,
+                                           allow_rows, _p(out), out.stride(0), _stream()), "xml_group_best_allow")
+    return out
+
+
+def best_part_rows(scores, parts, video):
+    """scores (rows, n_parts) f32, video (rows,) int32 SOURCE video per row -> (rows,) int32 index row of that video's best
+    part (group_best_allow's rule), -1 for an id outside [0, n_videos)  (xml_best_part_rows)."""
+    n_parts, n_videos = _parts_args(scores, parts, "best_part_rows")
+    rows = scores.shape[0]
+    if not torch.is_tensor(video) or video.dtype != torch.int32 or video.dim() != 1 or video.numel() != rows:
+        raise ValueError("best_part_rows: video must be a (%d,) int32 tensor of source-video ids, got %s %s"
+                         % (rows, getattr(video, "dtype", type(video).__name__), tuple(getattr(video, "shape", ()))))
+    if video.device != scores.device:
+        raise ValueError("best_part_rows: video is on %s, the scores are on %s" % (video.device, scores.device))
+    video = video.contiguous()
+    out = torch.empty((rows,), dtype=torch.int32, device=scores.device)
+    check(_lib.load().xml_best_part_rows(_p(scores), scores.stride(0) if rows else n_parts, rows, _p(parts.group_start),
+                                         n_videos, _p(video), _p(out), _stream()), "xml_best_part_rows")
+    return out
+
+
 def moments_decode(scores, flat=None, top_idx=None, row_vid=None, meta2vid=None, l_ref=0, clip_length=1.5, seconds=True,
-                   n=None, out=None, out_count=None):
+                   n=None, out=None, out_count=None, part_offset=None):
     """K10.  (flat (Nq, n) int32, scores (Nq, n) f32) -> records (Nq, n, 4) int32 = xml_moment {vid i32, st f32, ed f32,
     score f32} (view the host copy as results.MOMENT_DTYPE) and count (Nq,) int32.
     top_idx (Nq, K) int32: video of local rank r; row_vid (Nq,) int32: the one video of each query (SVMR); meta2vid (Nv,)
     int32: meta index -> video2idx value.  flat=None: the VR list of top_idx[:, :n] / scores[:, :n].
-    out / out_count: write into these rows of a larger result buffer ((Nq, >= n, 4) int32 / (Nq,) int32 views)."""
+    out / out_count: write into these rows of a larger result buffer ((Nq, >= n, 4) int32 / (Nq,) int32 views).
+    part_offset (index rows,) int32 (a parts index: PartTable.part_offset on the device): the row's first clip in its source
+    video is added to st_idx / ed_idx before the float conversion (xml_moments_decode_parts); meta2vid should then be
+    PartTable.meta2vid(...), index row -> source video id."""
     _req(scores, "scores", torch.float32)
     nq = scores.shape[0]
     n = scores.shape[1] if n is None else int(n)
@@ -960,6 +1024,16 @@ def moments_decode(scores, flat=None, top_idx=None, row_vid=None, meta2vid=None,
         out_count = torch.empty((nq,), dtype=torch.int32, device=scores.device)
     assert out.dtype == torch.int32 and out.shape[0] == nq and out.shape[2] == 4 and out.stride(2) == 1 and out.stride(1) == 4
     assert out_count.dtype == torch.int32 and out_count.is_contiguous() and out_count.numel() == nq
+    if part_offset is not None:
+        _req(part_offset, "part_offset", torch.int32)
+        if part_offset.dim() != 1 or (meta2vid is not None and meta2vid.numel() != part_offset.numel()):
+            raise ValueError("moments_decode: part_offset must be (index rows,) int32, one entry per entry of meta2vid; got %s"
+                             % (tuple(part_offset.shape),))
+        check(_lib.load().xml_moments_decode_parts(_p(flat), _p(scores), _p(top_idx), _p(row_vid), _p(meta2vid),
+                                                   _p(part_offset), nq, n, scores.stride(0), k, int(l_ref),
+                                                   float(clip_length), 1 if seconds else 0, _p(out), out.stride(0) // 4,
+                                                   _p(out_count), _stream()), "xml_moments_decode_parts")
+        return out, out_count
     check(_lib.load().xml_moments_decode(_p(flat), _p(scores), _p(top_idx), _p(row_vid), _p(meta2vid), nq, n,
                                          scores.stride(0), k, int(l_ref), float(clip_length), 1 if seconds else 0,
                                          _p(out), out.stride(0) // 4, _p(out_count), _stream()), "xml_moments_decode")
