@@ -892,6 +892,37 @@ int xml_merge_shard_topk(const float* recv_score, const int32_t* recv_id, int wo
                          float* out_val, int32_t* out_id, void* ws, size_t ws_bytes, xml_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * In-place updates of a resident index with a fixed number of video SLOTS (inference.MutableCorpusIndex).
+ * All pointers are device memory; both entries are one stream-ordered launch and read nothing back.
+ *
+ * xml_index_put_rows: scatter one encoded context batch -- per modality (n_mod = 1 | 2; "_a" = first, "_b" = second, NULL when
+ * n_mod == 1) f1 / f2 (b, lb, hidden) of dtype dt and mask (b, lb) f32 -- to the b DISTINCT slots `slots` (int32, each in
+ * [0, capacity)) of an index of `capacity` slots of lpad rows.  Every slot is left as the one-shot build leaves a video of
+ * that batch:
+ *   k6     rows [0, lb): f1 L2-normalised (F.normalize; bitwise xml_l2norm_rows / xml_q2c_tile_rows_l2norm), rows [lb, lpad)
+ *          zero; tiled != 0 (lpad == 128 only): K6's slice-major tile image of (capacity * 128) rows (xml_q2c_tiled_bytes),
+ *          else row-major (capacity, lpad, hidden)
+ *   feat2  (capacity, lpad, hidden): rows [0, lb) = f2, the rest zero;  imask (capacity, lpad) f32 = mask, zero beyond lb
+ *   bits   (capacity, 4) int32: bit c of the slot's 128 = (mask[c] != 0)  (the mask-bit operand of xml_q2c_scores_tiled)
+ *   vlen   (capacity) int32: max over the modalities of (last c with mask[c] != 0) + 1, l_ref when there is none, <= l_ref
+ *   slot_ids (capacity) int32 = ids[i] (ids NULL: the slot number);  live (ceil(capacity / 32)) int32: the slot's bit is set
+ *   (atomicOr: slots of one call may share a word)
+ * All lpad rows of a slot are written: nothing of a previous occupant remains.  b <= 65535.
+ * XML_ERR_UNSUPPORTED: dt other than XML_F32 / XML_BF16, hidden that xml_q2c_tile_rows_l2norm_ok refuses, lpad % 16 != 0 or
+ * lpad > 128, tiled with lpad != 128.
+ * xml_index_clear_rows: free n distinct slots -- live bit cleared (atomicAnd), imask rows and bits zeroed, vlen = l_ref; the
+ * feature rows stay (a search never reaches a slot whose live bit is 0).
+ * --------------------------------------------------------------------------------------------- */
+int xml_index_put_rows(int n_mod, const void* f1_a, const void* f2_a, const float* mask_a, const void* f1_b,
+                       const void* f2_b, const float* mask_b, const int32_t* slots, const int32_t* ids, int b, int lb,
+                       void* k6_a, void* feat2_a, float* imask_a, int32_t* bits_a, void* k6_b, void* feat2_b,
+                       float* imask_b, int32_t* bits_b, int32_t* vlen, int32_t* slot_ids, int32_t* live, int capacity,
+                       int lpad, int l_ref, int hidden, int dt, int tiled, xml_stream_t stream);
+int xml_index_clear_rows(int n_mod, const int32_t* slots, int n, float* imask_a, int32_t* bits_a, float* imask_b,
+                         int32_t* bits_b, int32_t* vlen, int32_t* live, int capacity, int lpad, int l_ref,
+                         xml_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * HOST post-processing ("next" row 8f-1; pointers are HOST memory): greedy temporal NMS.
  *   xml_nms_vcmr_host = filter_vcmr_by_nms (baselines/clip_alignment_with_language/inference.py:189-225):
  *     first max_before predictions, grouped by video in order of appearance, NMS per video

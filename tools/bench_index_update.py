@@ -1,0 +1,239 @@
+"""Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
+
+usage: python tools/bench_index_update.py [--legs put,e2e,c3,c3r] [--batch 200] [--reps 21] [--pass-reps 5] [--queries 10000]
+                                          [--videos 21793] [--suite-wall "..."] [--out profiles/index_update_timing.md]
+
+  put   xml_index_put_rows alone on a --batch-video batch at the headline shape (H = 768, lpad = 128, bf16, two modalities),
+        next to the existing passes it replaces run on the same rows in the same process: the fused normalise-and-tile pass
+        (what pack_q2c_corpus(normalize=True) launches; its host read-back of the masks is left out) and the feat2 / mask copies
+  e2e   add() of the batch, encoder included, against build_corpus_index on the same batch
+  c3    the full-length headline corpus: search on a mutable index at capacity = n_videos against the one-shot index (the
+        price of mask-bit mode against the mask-free K6), the 10 000-query pass and the 50-query graph replay
+  c3r   the same on the ragged corpus with the real TVR clip counts (the price of giving up the length-bucketed image)
+
+Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
+same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
+slot's K6 rows and feat2 rows written once, plus the masks.  --suite-wall: a sentence on the GPU suite's wall time, copied into
+the report (the suite is not run from here)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from tvretrieval_amd import inference as inf, ops  # noqa: E402
+from tvretrieval_amd.index_update import MutableCorpusIndex  # noqa: E402
+
+HBM_STREAM = 6.3e12       # bytes / s: the achievable HBM stream rate of an MI355X (8.0 TB/s is the specification)
+
+
+def timed(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for s, e in evs:
+        s.record(); fn(); e.record()
+    torch.cuda.synchronize()
+    ms = sorted(s.elapsed_time(e) for s, e in evs)
+    return ms[len(ms) // 2], ms[0], ms[-1]
+
+
+def fmt(t, unit="ms"):
+    k = 1e3 if unit == "us" else 1.0
+    return "%.3g %s (min %.3g .. max %.3g)" % (t[0] * k, unit, t[1] * k, t[2] * k)
+
+
+def put_leg(args, lines):
+    dev, dt, h, lpad, b = "cuda", torch.bfloat16, 768, 128, args.batch
+    cap = 2 * b
+    g = torch.Generator(device=dev).manual_seed(0)
+    enc = [(torch.randn((b, lpad, h), device=dev, generator=g).to(dt), torch.randn((b, lpad, h), device=dev, generator=g).to(dt),
+            torch.ones((b, lpad), device=dev)) for _ in range(2)]
+    k6 = [ops.TiledRows(torch.zeros(ops.q2c_tiled_numel(cap * lpad, h, dt), dtype=dt, device=dev), cap * lpad, h, (cap, lpad, h))
+          for _ in range(2)]
+    f2 = [torch.zeros((cap, lpad, h), dtype=dt, device=dev) for _ in range(2)]
+    mk = [torch.zeros((cap, lpad), device=dev) for _ in range(2)]
+    bits = [torch.zeros((cap, 4), dtype=torch.int32, device=dev) for _ in range(2)]
+    vlen = torch.zeros(cap, dtype=torch.int32, device=dev)
+    sid = torch.zeros(cap, dtype=torch.int32, device=dev)
+    live = torch.zeros((cap + 31) // 32, dtype=torch.int32, device=dev)
+    scattered = torch.from_numpy(np.random.default_rng(0).permutation(cap)[:b].astype(np.int32)).to(dev)
+    dense = torch.arange(b, dtype=torch.int32, device=dev)
+
+    def put(slots):
+        ops.index_put_rows([e[0] for e in enc], [e[1] for e in enc], [e[2] for e in enc], slots, None, k6, f2, mk, bits, vlen,
+                           sid, live, lpad)
+
+    # the one-shot build's passes for the same rows (rows [0, b) of the same tensors)
+    head = [t.data[:ops.q2c_tiled_numel(b * lpad, h, dt)] for t in k6]
+
+    def passes():
+        for m in range(2):
+            ops._tile(enc[m][0], b * lpad, None, True, head[m])
+            f2[m][:b, :lpad] = enc[m][1]
+            mk[m][:b, :lpad] = enc[m][2]
+
+    def tile_only():
+        for m in range(2):
+            ops._tile(enc[m][0], b * lpad, None, True, head[m])
+
+    nbytes = 2 * (4 * b * lpad * h * 2 + 2 * b * lpad * 4 + b * 16)
+    res = [("xml_index_put_rows, scattered slots", timed(lambda: put(scattered), args.reps)),
+           ("existing passes (normalise + tile, feat2 copy, mask copy; 6 launches)", timed(passes, args.reps)),
+           ("xml_index_put_rows, slots 0 .. b - 1", timed(lambda: put(dense), args.reps)),
+           ("existing passes, again", timed(passes, args.reps)),
+           ("of which the normalise + tile pass (2 launches)", timed(tile_only, args.reps))]
+    lines += ["## The put kernel alone", "",
+              "%d videos x %d clips x H = %d, bf16, two modalities into an index of %d slots: %.1f MB read + written per call "
+              "(counted from the shapes), %.1f us at the %.1f TB/s HBM stream rate." % (b, lpad, h, cap, nbytes / 1e6,
+                                                                                     nbytes / HBM_STREAM * 1e6, HBM_STREAM / 1e12),
+              "", "| what | time per call | bytes / s |", "|---|---|---|"]
+    for name, t in res:
+        moved = nbytes if "tile pass" not in name else 2 * 2 * b * lpad * h * 2
+        lines.append("| %s | %s | %.2f TB/s |" % (name, fmt(t, "us"), moved / (t[0] * 1e-3) / 1e12))
+    old = (res[1][1][0] + res[3][1][0]) / 2
+    new = (res[0][1][0] + res[2][1][0]) / 2
+    lines += ["", "Rate of the new kernel over the rate of the passes it replaces (same bytes, medians, mean of both rounds): %.2f."
+              % (old / new)]
+    for ln in lines[-10:]:
+        print(ln, flush=True)
+
+
+def wall(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    out.sort()
+    return out[len(out) // 2], out[0], out[-1]
+
+
+def e2e_leg(args, lines):
+    import bench
+    _, _, l, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3"]
+    be = bench.HipBackend(0)
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), torch.bfloat16)
+    b = args.batch
+    batch = tuple(t[:b].contiguous() for t in next(iter(bench.context_batches(0, bench.CHUNK, l, dv, ds, True, True, be.device))))
+    index = MutableCorpusIndex.create(model, 2 * b)
+    slots = index.add(*batch)
+
+    def readd():
+        index.replace(slots, *batch)
+
+    def build():
+        with torch.no_grad():
+            inf.build_corpus_index(model, [batch], l_ref=l, n_videos=b)
+
+    def encode():
+        index.encode(*batch)
+
+    rows = [("MutableCorpusIndex: encode + put of %d videos (replace of live slots: the path of add)" % b, wall(readd, args.pass_reps)),
+            ("build_corpus_index on the same batch (encode, copies, packing pass, valid lengths)", wall(build, args.pass_reps)),
+            ("MutableCorpusIndex, again", wall(readd, args.pass_reps)), ("build_corpus_index, again", wall(build, args.pass_reps)),
+            ("model.encode_context alone", wall(encode, args.pass_reps))]
+    lines += ["", "## Adding %d videos end to end (headline model, %d clips, bf16), host clock around a device synchronise" % (b, l),
+              "", "| what | wall time per call |", "|---|---|"]
+    lines += ["| %s | %s |" % (n, fmt(t)) for n, t in rows]
+    for ln in lines[-7:]:
+        print(ln, flush=True)
+
+
+def graph_ms(model, index, qf, qm, batch=50, n=60):
+    with torch.no_grad():
+        g = inf.GraphedVcmrSearch(model, index, batch, qf.shape[1], qf.shape[2])
+    return timed(lambda: g(qf[:batch], qm[:batch]), n)
+
+
+def search_leg(name, args, lines):
+    import bench
+    _, _, l, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS[name]
+    nv, nq = args.videos, args.queries
+    be = bench.HipBackend(0)
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), torch.bfloat16)
+    lens = bench.real_clip_counts(nv, l) if name in bench.RAGGED else None
+    batches = lambda: bench.context_batches(0, nv, l, dv, ds, True, True, be.device, lens=lens)      # noqa: E731
+    with torch.no_grad():
+        fixed = inf.build_corpus_index(model, batches(), l_ref=l, n_videos=nv)
+        t0 = time.perf_counter()
+        mut = MutableCorpusIndex.from_batches(model, batches(), nv, l_ref=l)
+        torch.cuda.synchronize()
+        fill_s = time.perf_counter() - t0
+        qf, qm = bench.synth_queries(nq, dq, be.device)
+        kw = dict(n_valid_tokens=int(qm.sum().item()))
+        rows = []
+        for rnd in ("", ", again"):
+            rows.append(("one-shot index" + rnd, timed(lambda: inf.vcmr_search(model, fixed, qf, qm, **kw), args.pass_reps, 2)))
+            rows.append(("mutable index" + rnd, timed(lambda: inf.vcmr_search(model, mut, qf, qm, **kw), args.pass_reps, 2)))
+        a = inf.vcmr_search(model, fixed, qf[:512], qm[:512])
+        b = inf.vcmr_search(model, mut, qf[:512], qm[:512])
+        same = bool(torch.equal(a["top_indices"], b["top_indices"]))
+        g_fixed, g_mut = graph_ms(model, fixed, qf, qm), graph_ms(model, mut, qf, qm)
+    t = fixed.feat1n[fixed.modalities[0]]
+    layout = "length-bucketed image, %d tiles" % t.plan.n_tiles if getattr(t, "plan", None) is not None else \
+        ("mask-free K6 (all_valid)" if getattr(t, "all_valid", False) else "plain tiles, mask bits")
+    fa, fb = (rows[0][1][0] + rows[2][1][0]) / 2, (rows[1][1][0] + rows[3][1][0]) / 2
+    lines += ["", "## Search on the %s corpus (%d videos x %d clips%s, hidden %d, bf16)" %
+              (name, nv, l, ", real TVR clip counts" if lens is not None else ", full length", hidden), "",
+              "One-shot index: %s, %.2f GB.  Mutable index at capacity = n_videos: plain tiles, mask bits, valid lengths always "
+              "on, %.2f GB; filled by add() in %.1f s.  First 512 queries: the video lists are %s."
+              % (layout, fixed.hbm_bytes() / 1e9, mut.hbm_bytes() / 1e9, fill_s, "identical" if same else "NOT identical"),
+              "", "| index | vcmr_search, %d queries | 50-query graph replay |" % nq, "|---|---|---|"]
+    for i, (n, tm) in enumerate(rows):
+        lines.append("| %s | %s | %s |" % (n, fmt(tm), fmt((g_fixed, g_mut)[i & 1]) if i < 2 else ""))
+    lines += ["", "Price of mutability on this corpus (medians, mean of both rounds): %.1f ms -> %.1f ms per %d-query pass (%+.1f %%); "
+              "50-query replay %.3f ms -> %.3f ms (%+.1f %%)."
+              % (fa, fb, nq, (fb / fa - 1) * 100, g_fixed[0], g_mut[0], (g_mut[0] / g_fixed[0] - 1) * 100)]
+    for ln in lines[-12:]:
+        print(ln, flush=True)
+    del fixed, mut
+    torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="put,e2e,c3,c3r")
+    ap.add_argument("--batch", type=int, default=200)
+    ap.add_argument("--videos", type=int, default=21793)
+    ap.add_argument("--queries", type=int, default=10000)
+    ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("--pass-reps", type=int, default=5)
+    ap.add_argument("--suite-wall", default="")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_update_timing.md"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_index_update.py measures on the GPU; none is visible")
+    p = torch.cuda.get_device_properties(0)
+    lines = ["# An index that takes updates: what it costs", "",
+             "`python tools/bench_index_update.py` on one %s (%d CUs, clock %d MHz as reported by the runtime), torch %s.  Medians of "
+             "repeated runs between HIP events after warm-up runs (min .. max); compared versions run in one process, alternating."
+             % (p.name, p.multi_processor_count, getattr(p, "clock_rate", 0) // 1000, torch.__version__), ""]
+    legs = args.legs.split(",")
+    if "put" in legs:
+        put_leg(args, lines)
+    if "e2e" in legs:
+        e2e_leg(args, lines)
+    for name in ("c3", "c3r"):
+        if name in legs:
+            search_leg(name, args, lines)
+    if args.suite_wall:
+        lines += ["", "## GPU test wall time", "", args.suite_wall]
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote %s" % args.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -181,6 +181,8 @@ SIGNATURES = {
                                 c_void_p]),
     "xml_attn_softmax": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                  c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "xml_index_put_rows": (c_int, [c_int] + [c_void_p] * 8 + [c_int, c_int] + [c_void_p] * 11 + [c_int] * 6 + [c_void_p]),
+    "xml_index_clear_rows": (c_int, [c_int, c_void_p, c_int] + [c_void_p] * 6 + [c_int] * 3 + [c_void_p]),
     "xml_q2c_tile_rows_l2norm_ok": (c_int, [c_int, c_int]),
     "xml_q2c_tile_rows_l2norm": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p]),
     "xml_gemm_tn_supported": (c_int, [c_int64, c_int, c_int, c_int]),

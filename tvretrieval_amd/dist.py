@@ -123,6 +123,9 @@ def check_shards(index, group=None):
     if getattr(index, "parts", None) is not None:
         raise ValueError("a parts index (build_corpus_index(parts=)) cannot be a corpus shard: the sharded drivers merge "
                          "per-shard video lists and know nothing of parts that fold into one video")
+    if getattr(index, "live", None) is not None:
+        raise ValueError("an index that takes updates (index_update.MutableCorpusIndex) cannot be a corpus shard: the sharded "
+                         "drivers number videos by their position in a fixed global corpus, its rows are slots")
     if getattr(index, "_shards_checked", False):
         return
     world = dist.get_world_size(group) if dist.is_initialized() else 1

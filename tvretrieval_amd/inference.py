@@ -29,8 +29,9 @@ and the sharded drivers call:
   F16S                                                    the dtype sentinel of split-f16 models and rows
 The split-f16 exact mode (split_f16_rows, SplitRows, F16_UNIT_LOG2), explain_moments (span_evidence), the device-side result
 records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and searches on an index of parts (group_best_allow,
-best_part_rows, moments_decode(part_offset=)) call further entries of tvretrieval_amd.ops; a backend without them serves
-every search that does not ask for those.
+best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
+index_clear_rows) call further entries of tvretrieval_amd.ops; a backend without them serves every search that does not ask
+for those.
 """
 import numpy as np
 import torch
@@ -77,6 +78,10 @@ class CorpusIndex(object):
         # of the index are then PARTS (n_videos keeps meaning index rows) and n_source_videos the videos they fold back into
         self.parts = None
         self.n_source_videos = self.n_videos
+        # an index that takes updates (index_update.MutableCorpusIndex): rows are SLOTS, live the
+        # (1, ceil(n_videos / 32)) int32 words of the occupied ones -- every search sees live AND video_allow -- and slot_ids
+        # the slot -> caller's id table (the meta2vid of a search that passes none).  None on every other index.
+        self.live = self.slot_ids = None
 
     def set_valid_lengths(self):
         """Per-video valid length from the masks (one small device pass + one host read at build time)."""
@@ -776,13 +781,17 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
     holds only its allowed videos (indices in this index's numbering); a query with a < K of them ends in K - a empty slots
     (top_i -1, top_w 0, or -inf when alpha == 0), which yield no moments.  K6 still scores every video.
     A parts index: K6, then ops.group_best_allow (each video's best part AND the caller's mask over source videos), then K8 under
-    those bits -- top_i are index rows, one per video; slots beyond the number of allowed videos are empty."""
+    those bits -- top_i are index rows, one per video; slots beyond the number of allowed videos are empty.
+    An index that takes updates (index.live): the allow words are ANDed with the live words -- one small (rows, words) int32
+    pass, part of a captured search -- so the lists are those of the corpus of the live videos, in slot numbering."""
     exact = None
     if video_allow is not None:
         if external_top is not None:
             raise ValueError("video_allow and external_top exclude each other: a caller's video lists replace the ranking "
                              "the mask restricts (filter the lists instead)")
         _check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0])
+    if index.live is not None and external_top is None:
+        video_allow = index.live if video_allow is None else video_allow[:, :index.live.shape[1]] & index.live
     if index.parts is not None:
         # long videos in parts: K6 scores every part, the fold keeps each video's best part (and the caller's mask, which
         # numbers source videos), K8 ranks those -- the restricted search over the index rows, one row per video
@@ -862,6 +871,12 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
                          "rows in the empty video slots of a restricted list")
     parts = index.parts
     pkw = {}
+    if index.live is not None:
+        if pad_tail:
+            raise ValueError("pad_tail=True on an index that takes updates: the reference-shaped tail would have to invent rows "
+                             "in the video slots that stay empty when fewer than K videos are live")
+        if meta2vid is None:
+            meta2vid = index.slot_ids
     if parts is not None:
         _check_parts_search(index, max_pred_l, external_top, pad_tail)
         meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=parts.part_offset)
@@ -1100,6 +1115,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     nq = (row_start.numel() - 1) if ragged else query_feat.shape[0]
     if index.parts is not None:
         _check_parts_search(index, max_pred_l, None, pad_tail)
+    if index.live is not None and pad_tail:
+        raise ValueError("pad_tail=True on an index that takes updates (see vcmr_search)")
     if video_allow is not None:
         if pad_tail:
             raise ValueError("video_allow and pad_tail=True exclude each other (see vcmr_search)")
@@ -1134,8 +1151,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     pkw = {}
     if index.parts is not None:      # records name source videos, in whole-video time (see vcmr_search)
         meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=index.parts.part_offset)
-    elif meta2vid is None:
-        meta2vid = torch.arange(index.n_videos, dtype=torch.int32, device=dev)
+    elif meta2vid is None:       # (an index that takes updates: the records carry the caller's ids of the slots)
+        meta2vid = index.slot_ids if index.slot_ids is not None else torch.arange(index.n_videos, dtype=torch.int32, device=dev)
     copied, freed = [None, None], buffers.freed
     ev_h2d = []
 
@@ -1241,7 +1258,9 @@ class GraphedVcmrSearch(object):
     the chain.  Inputs are copied into static buffers, the returned tensors are the graph's static outputs
     (overwritten by the next call: copy them if they must outlive it).  Weights are packed and workspaces sized by
     two eager warm-up passes before the capture; the corpus index and the model weights must not be re-allocated
-    afterwards (re-create the object after load_state_dict / an optimizer step)."""
+    afterwards (re-create the object after load_state_dict / an optimizer step).  An index_update.MutableCorpusIndex never
+    re-allocates and takes no data-dependent launch decision, so it may be updated (add / replace / remove) between replays:
+    the live words are read by the captured pass, and a replay after an update returns the updated result."""
 
     def __init__(self, model, index, nq, lq, d_in, video_allow_rows=None, **search_kwargs):
         """video_allow_rows = None | 1 | nq: a restricted search -- a static (rows, ceil(Nv / 32)) allow-word buffer (all videos

@@ -1338,3 +1338,86 @@ def unsplit_f16_rows(sr):
     check(_lib.load().xml_unsplit_f16_rows(_p(sr.data), _p(sr.inv), _p(x), sr.data.numel() // k, k, _stream()),
           "xml_unsplit_f16_rows")
     return x
+
+
+# ---- in-place index updates (include/xmlhip.h "In-place updates of a resident index"; inference.MutableCorpusIndex) ---------
+def _index_sides(k6, feat2, imask, bits):
+    """Checks the per-modality index tensors of the two update entries; returns (capacity, lpad, hidden, tiled, k6 buffers)."""
+    n_mod = len(feat2)
+    if n_mod not in (1, 2) or not (len(k6) == len(imask) == len(bits) == n_mod):
+        raise _lib.XmlHipError("index update: 1 or 2 modalities, the same number of k6 / feat2 / mask / bits tensors")
+    cap, lpad, hidden = feat2[0].shape
+    tiled = isinstance(k6[0], TiledRows)
+    data = []
+    for m in range(n_mod):
+        _req(feat2[m], "feat2", feat2[0].dtype); _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
+        if tuple(feat2[m].shape) != (cap, lpad, hidden) or tuple(imask[m].shape) != (cap, lpad) or tuple(bits[m].shape) != (cap, 4):
+            raise _lib.XmlHipError("index update: feat2 (capacity, lpad, H), mask (capacity, lpad), bits (capacity, 4) expected")
+        if isinstance(k6[m], TiledRows) != tiled:
+            raise _lib.XmlHipError("index update: the K6 operands of the modalities differ in layout")
+        d = k6[m].data if tiled else k6[m]
+        _req(d, "k6", feat2[0].dtype)
+        if tiled:
+            if k6[m].shape != (cap, lpad, hidden) or lpad != 128 or d.numel() != q2c_tiled_numel(cap * lpad, hidden, d.dtype):
+                raise _lib.XmlHipError("index update: the tile image does not hold (capacity, 128, H) rows")
+        elif tuple(d.shape) != (cap, lpad, hidden):
+            raise _lib.XmlHipError("index update: row-major K6 operand of shape %s expected" % ((cap, lpad, hidden),))
+        data.append(d)
+    return int(cap), int(lpad), int(hidden), tiled, data
+
+
+def _index_state(vlen, live, cap, slot_ids=None):
+    _req(vlen, "vlen", torch.int32); _req(live, "live", torch.int32)
+    if vlen.numel() != cap or live.numel() != (cap + 31) // 32:
+        raise _lib.XmlHipError("index update: vlen (capacity,) and live (ceil(capacity / 32),) int32 expected")
+    if slot_ids is not None:
+        _req(slot_ids, "slot_ids", torch.int32)
+        if slot_ids.numel() != cap:
+            raise _lib.XmlHipError("index update: slot_ids (capacity,) int32 expected")
+
+
+def index_put_rows(f1, f2, masks, slots, ids, k6, feat2, imask, bits, vlen, slot_ids, live, l_ref):
+    """xml_index_put_rows: one encoded context batch into its slots of a fixed-capacity index, one launch, nothing read back.
+    f1 / f2 / masks: per-modality lists of the batch's (b, lb, H), (b, lb, H), (b, lb) f32 tensors; slots (b,) int32 device,
+    DISTINCT and in [0, capacity) (the caller's slot table guarantees both); ids (b,) int32 device or None (the slot number).
+    k6 / feat2 / imask / bits: per-modality lists of the index's K6 operand (TiledRows or (capacity, lpad, H)), feat2, f32 mask
+    and (capacity, 4) mask-bit words; vlen / slot_ids (capacity,) int32, live (ceil(capacity / 32),) int32."""
+    cap, lpad, hidden, tiled, data = _index_sides(k6, feat2, imask, bits)
+    _index_state(vlen, live, cap, slot_ids)
+    n_mod = len(feat2)
+    if not (len(f1) == len(f2) == len(masks) == n_mod):
+        raise _lib.XmlHipError("index_put_rows: the batch holds %d modalities, the index %d" % (len(f1), n_mod))
+    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
+    for m in range(n_mod):
+        _req(f1[m], "f1", feat2[0].dtype); _req(f2[m], "f2", feat2[0].dtype); _req(masks[m], "mask", torch.float32)
+        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
+            raise _lib.XmlHipError("index_put_rows: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected")
+    _req(slots, "slots", torch.int32)
+    if slots.numel() != b or (ids is not None and (_req(ids, "ids", torch.int32).numel() != b)):
+        raise _lib.XmlHipError("index_put_rows: one slot (and id) per video of the batch")
+    j = n_mod - 1
+    sec = (lambda t: _p(t[j])) if n_mod == 2 else (lambda t: None)
+    check(_lib.load().xml_index_put_rows(
+        n_mod, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), b, lb,
+        _p(data[0]), _p(feat2[0]), _p(imask[0]), _p(bits[0]), sec(data), sec(feat2), sec(imask), sec(bits),
+        _p(vlen), _p(slot_ids), _p(live), cap, lpad, int(l_ref), hidden, dt_of(feat2[0]), int(tiled), _stream()),
+        "xml_index_put_rows")
+
+
+def index_clear_rows(slots, imask, bits, vlen, live, l_ref):
+    """xml_index_clear_rows: free the DISTINCT slots (n,) int32 device -- live bits cleared, mask rows and mask bits zeroed,
+    vlen = l_ref; one launch, nothing read back."""
+    n_mod = len(imask)
+    if n_mod not in (1, 2) or len(bits) != n_mod:
+        raise _lib.XmlHipError("index_clear_rows: 1 or 2 modalities")
+    cap, lpad = imask[0].shape
+    for m in range(n_mod):
+        _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
+        if tuple(imask[m].shape) != (cap, lpad) or tuple(bits[m].shape) != (cap, 4):
+            raise _lib.XmlHipError("index_clear_rows: mask (capacity, lpad) and bits (capacity, 4) expected")
+    _index_state(vlen, live, cap)
+    _req(slots, "slots", torch.int32)
+    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    check(_lib.load().xml_index_clear_rows(n_mod, _p(slots), int(slots.numel()), _p(imask[0]), _p(bits[0]), sec(imask), sec(bits),
+                                           _p(vlen), _p(live), int(cap), int(lpad), int(l_ref), _stream()),
+          "xml_index_clear_rows")
