@@ -16,6 +16,20 @@
  *   - all calls are asynchronous on `stream`, never allocate, never synchronise and are re-entrant per
  *     stream; scratch comes from the caller: `ws`/`ws_bytes`, sized by the matching *_workspace_bytes();
  *   - return value: 0 = XML_OK, negative = xml_status (never throws, never aborts).
+ *
+ * Extents, scratch and alignment (enforced by tests/test_gpu_abi_arena.py: every operand, output and workspace of a call lies
+ * in one arena of known bytes, once filled with 0x00 and once with 0xFF)
+ *   - an entry writes only the documented extent of its outputs and of `ws`: for an output with a leading dimension
+ *     (ld, ld_out, ld_index, out_ld) that is the first n elements of every row -- the elements between rows are never written
+ *     -- and nothing before the first or behind the last documented element.  Inputs are never written;
+ *   - an entry reads only the documented extents of its inputs (a ragged tile re-reads an in-range row instead of running
+ *     past the operand); the tests enforce the observable half of this: no result depends on bytes outside them;
+ *   - `ws` need not be initialised and is EXACTLY *_workspace_bytes() bytes: nothing is carried in it from call to call;
+ *   - elements the text of an entry calls "not written" / "left untouched" keep the caller's bytes;
+ *   - alignment: pointers to dt rows (activations, weights, K6 tile images, xml_moment records) and `ws` are 16-byte
+ *     aligned, and a leading dimension of dt rows is a multiple of 8 elements; f32 / int32 / uint32 matrices that come with
+ *     a free leading dimension (scores / ld, out / ld_out, allow / ld_allow, idx_in, out_bits / out_ld, flat and score /
+ *     ld_in, out_index / ld_index) need 4-byte alignment only and take any ld >= the row.
  */
 #ifndef XMLHIP_H
 #define XMLHIP_H
@@ -117,7 +131,9 @@ int xml_attention_core(const void* q, int ldq, const void* k, int ldk, const voi
  * sequence i = rows cu_seqlens[i] .. cu_seqlens[i+1]-1 (cu_seqlens: n+1 int32, cu_seqlens[n] == rows), every sequence
  * 1 .. max_len <= 32 tokens.  Per valid token the result is that of xml_attention_block / xml_modular_pool on the padded
  * batch: projections and LayerNorm are row-wise, and a padded key adds exp(-10000 + s - max) = +0 to the softmax sum and
- * 0 * v to P V.  (K1+K2 on packed rows: xml_linear_ln_relu_pos_packed below.)  hidden % (32 * n_heads) == 0 as for xml_attention_block; xml_modular_pool_varlen: hidden <= 1024.
+ * 0 * v to P V.  (K1+K2 on packed rows: xml_linear_ln_relu_pos_packed below.)  hidden % (32 * n_heads) == 0 as for xml_attention_block;
+ * xml_modular_pool_varlen / _att_varlen: hidden % 8 == 0 and hidden <= 1024 -- the packed forms have no scalar path, any other
+ * hidden returns XML_ERR_UNSUPPORTED before a launch (xml_modular_pool / _att take any hidden).
  * --------------------------------------------------------------------------------------------- */
 /* Packing plan of a padded batch: mask (n, lq) f32, every row a non-empty prefix of ones (lq <= 64).
  *   cu_seqlens (n + 1) int32, src_row (>= n * lq) int32: packed token i is row src_row[i] = seq * lq + t of the padded batch;
@@ -263,7 +279,7 @@ int xml_q2c_scores_tiled(int n_mod, const void* qt0, const void* ct0, const floa
 
 /* ---------------------------------------------------------------------------------------------
  * K8: per-row top-k, torch.topk(exp(alpha*s), k) (xml/inference.py:317,347-348)
- *   scores (rows, n) f32 row stride ld; optional idx_in (rows, n) int32 payload (NULL: column index)
+ *   scores (rows, n) f32 row stride ld; optional idx_in (rows, n) int32 payload, the SAME row stride ld (NULL: column index)
  *   out_val (rows, k) f32 = alpha != 0 ? expf(alpha*s) : s, descending; out_idx (rows, k) int32.
  *   Order: value descending, then payload/column index ascending (torch leaves ties unspecified).
  *   k <= 256, k <= n.
@@ -465,7 +481,7 @@ int xml_moment_topk(const float* st, const float* ed, const float* w, float* out
  * the st / ed rows of a pair with video v are taken as 0 WITHOUT being read (xml_convse_rerank_ex with the same vid_len left
  * them unwritten), pairs with pair_vid < 0 as empty.  Same lists, bit for bit.
  * Batches too small to fill the chip with one 256-thread workgroup per query (nq <= 128: the reference's eval_query_bsz = 50)
- * run 1024-thread workgroups -- the same algorithm over sixteen waves, the same lists, bit for bit. */
+ * with enough pairs to give sixteen waves work (kpairs >= 32) run 1024-thread workgroups -- the same algorithm over sixteen waves, the same lists, bit for bit. */
 int xml_moment_topk_ex(const float* st, const float* ed, const float* w, const float* summ, const int32_t* pair_vid,
                        const int32_t* vid_len, float* out_score, int32_t* out_flat, int nq, int kpairs, int lpad, int l_ref,
                        int min_l, int max_l, int n_out, xml_stream_t stream);
@@ -838,7 +854,9 @@ int xml_clip_grad_norm(float* g, int64_t n, float max_norm, float* ws, xml_strea
  *     their warm-up;
  *   norm_ws: ceil(total / XML_ADAM_NORM_BLOCK) floats of device scratch or NULL.  Given: the per-tensor gradient norms are
  *     summed from per-block partials in a fixed order (25 us for 20 M parameters) instead of by one f32 atomic per block
- *     (92 us). */
+ *     (92 us).  A block that holds a tensor boundary -- and every block when total % 4 != 0 (the vector loads need whole
+ *     groups of 4; BertAdam pads its tensors to 4 elements) -- still adds its sums with f32 atomics: the last bits of the
+ *     norms of the tensors that touch such a block, hence of their clipped gradients, can vary from run to run. */
 #define XML_ADAM_NORM_BLOCK 1024
 int xml_bert_adam_step(float* p, float* g, float* m, float* v, const int64_t* seg_off, const float* seg_lr,
                        const float* seg_wd, int n_seg, int64_t total, float lr_mult, float b1, float b2,
