@@ -12,64 +12,15 @@ import ctypes
 import pytest
 import torch
 
+from dispatch_mirror import (cdiv, few, gemm256_ok, gemm256p_ok, gemm_form, gemm_ln_fused,  # noqa: F401
+                             small_bmn, small_kloop)      # the dispatch predicates, one per C++ decision
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 DTYPES = [torch.float32, torch.bfloat16]
 U32 = 2.0 ** -24                       # unit roundoff of f32
 BIG_BYTES = 3 << 30                    # largest A operand built for an edge (the gemm256p edge of N = 256 at K = 3 072 is 9.7 GB)
-
-
-def cdiv(a, b):
-    return -(-a // b)
-
-
-# ---- the dispatch predicates, one per C++ decision --------------------------------------------------------------------
-def few(m, n):
-    """linear.hip xmli_gemm: `few` -- fewer than 64 tiles of 256 x 256 -> the small-tile gemm_bias_act_kernel."""
-    return cdiv(m, 256) * cdiv(n, 256) < 64
-
-
-def small_bmn(m, n):
-    """linear.hip launch_gemm: tile size of gemm_bias_act_kernel (bmn from wg128)."""
-    wg128 = cdiv(n, 128) * cdiv(m, 128)
-    return 128 if wg128 >= 512 else 64 if wg128 * 4 >= 192 else 32
-
-
-def small_kloop(k, es, bmn):
-    """linear.hip gemm_bias_act_kernel: K loop of the small tiles -- deep-3 / deep-2 / plain by the number of 128-byte steps."""
-    if bmn == 128:
-        return "plain"
-    ns = cdiv(k * es, 128)
-    return "deep3" if ns % 3 == 0 else "deep2" if ns % 2 == 0 else "plain"
-
-
-def gemm256_ok(m, n, k, es):
-    """gemm256.hip xmli_gemm256_eligible."""
-    kb = k * es
-    return m >= 256 and n >= 128 and kb % 128 == 0 and kb >= 256
-
-
-def gemm256p_ok(m, n, k, es):
-    """gemm256p.hip xmli_gemm256p_eligible."""
-    kb = k * es
-    return kb % 128 == 0 and kb >= 256 and n >= 128 and n % 8 == 0 and cdiv(m, 256) * cdiv(n, 256) >= 3072
-
-
-def gemm_ln_fused(m, n, k, es):
-    """gemm256p.hip xmli_gemm_ln_eligible (f32 / bf16): LN_FUSED_MIN_ROWS = 2 048."""
-    kb = k * es
-    return kb % 128 == 0 and kb >= 256 and n % 256 == 0 and n // 256 <= 3 and m >= 2048
-
-
-def gemm_form(m, n, k, es):
-    """the kernel the product library's xmli_gemm runs for f32 / bf16."""
-    if not few(m, n) and gemm256p_ok(m, n, k, es):
-        return "gemm256p"
-    if not few(m, n) and gemm256_ok(m, n, k, es):
-        return "gemm256"
-    b = small_bmn(m, n)
-    return "small%d-%s" % (b, small_kloop(k, es, b))
 
 
 def first_true(pred, hi=1 << 24):

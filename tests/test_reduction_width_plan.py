@@ -1,0 +1,234 @@
+"""The plan of tests/test_gpu_reduction_width.py, checked without a GPU: from the same tables (tests/reduction_width_cases.py)
+* every case lands on the kernel it is meant for, by the mirrors of the dispatch predicates (tests/dispatch_mirror.py);
+* every residue class of the slice count modulo the ring depth, every minimum count and a count above the model's largest
+  width is present for every form -- a table edit that empties a class fails here with the class named;
+* the threshold literals of the mirrors are the ones in the .hip sources, so a kernel change that moves a threshold cannot
+  silently move the cases to another kernel."""
+import os
+import re
+
+import dispatch_mirror as DM
+import reduction_width_cases as RC
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tvretrieval_amd", "csrc")
+
+
+def src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def need(present, required, what):
+    """one line per required class that `present` lacks."""
+    return ["%s: no case with %s" % (what, r) for r in required if r not in present]
+
+
+def report(problems):
+    assert not problems, "classes missing from tests/reduction_width_cases.py:\n  " + "\n  ".join(problems)
+
+
+def residues(slices, depth):
+    return {"n_slices = %d (mod %d)" % (s % depth, depth) for s in slices}
+
+
+def all_residues(depth, step=2):
+    """the slice count is even (K bytes % 128 == 0), so a four-slot ring sees 0 and 2, a five-slot ring every residue."""
+    return sorted({"n_slices = %d (mod %d)" % (s % depth, depth) for s in range(0, 2 * depth * step, step)})
+
+
+# ---- every case lands in its form -------------------------------------------------------------------------------------------
+def test_gemm_cases_reach_their_kernels():
+    for form, dt, (m, n), s in RC.gemm256_cases() + RC.gemm256p_cases():
+        assert DM.gemm_form(m, n, RC.k_of(s, dt), RC.ES[dt]) == form, (form, dt, m, n, s)
+        assert RC.k_of(s, dt) * RC.ES[dt] == s * DM.SLICE_BYTES
+    (m, n), = RC.GEMM256P_SHAPES
+    tiles = DM.cdiv(m, 256) * DM.cdiv(n, 256)
+    assert DM.GEMM256P_MIN_TILES <= tiles < DM.GEMM256P_MIN_TILES + 8 and m % 256 == 1      # just over the threshold, ragged last row tile
+    assert tiles > 2 * 256, "every workgroup of the persistent kernel must walk several tiles"
+    for m, n in RC.GEMM256_SHAPES:
+        assert DM.FEW_TILES <= DM.cdiv(m, 256) * DM.cdiv(n, 256) < DM.GEMM256P_MIN_TILES // 4
+    assert any(m % 256 and n % 256 for m, n in RC.GEMM256_SHAPES), "gemm256: no ragged M with an N that is no multiple of 256"
+    for form, dt, (m, n), ns, k in RC.small_cases():
+        es = RC.ES[dt]
+        assert DM.few(m, n) or not (DM.gemm256_ok(m, n, k, es) or DM.gemm256p_ok(m, n, k, es)), (form, dt, m, n, k)
+        assert DM.gemm_form(m, n, k, es).startswith(form + "-") and DM.cdiv(k * es, 128) == ns and k % (16 // es) == 0
+    for form, dt, h, s in RC.ln_cases():
+        assert DM.gemm_ln_fused(RC.LN_SEQS * RC.LN_LEN, h, RC.k_of(s, dt), RC.ES[dt]), (form, dt, h, s)
+    for form, dt, h, nh in RC.ATTENTION_BLOCK_CASES:
+        assert DM.gemm_ln_fused(RC.LN_SEQS * RC.LN_LEN, h, h, RC.ES[dt]) and DM.attn_form(RC.LN_LEN, RC.LN_LEN, h, nh, RC.ES[dt]) == "large"
+    assert RC.LN_SEQS * RC.LN_LEN >= DM.LN_FUSED_MIN_ROWS
+    for form, m, k in RC.f16s_cases():
+        assert DM.f16s_form(m, RC.F16S_N, k) == ("gemm256-f16s" if m >= 256 else "small%d-f16s" % DM.small_bmn(m, RC.F16S_N))
+
+
+def test_k6_cases_reach_their_kernels():
+    for form, dt, s, (nq, nv), n_mod in RC.k6_persist_cases():
+        hidden, es = RC.k_of(s, dt), RC.ES[dt]
+        assert hidden * es == s * DM.SLICE_BYTES and hidden % 8 == 0
+        assert DM.q2c_tiled_ok(128, hidden, es), (form, dt, s)
+        if form == "rowmajor":
+            assert DM.q2c_fused_forms(n_mod, 128, hidden, es, f16=dt == "f16") == ["persist"], (form, dt, s)
+            assert DM.q2c_form(128, hidden, es, combine=False, f16=dt == "f16") == "persist"
+        assert DM.q2c_persist_slots(RC.K6_TILED[form], RC.K6_MASK[form]) == (5 if form in ("nomask", "bitmask") else 4)
+    (nq, nv), (nq2, nv2) = RC.K6_PERSIST_SHAPES
+    assert DM.q2c_persist_qsh(nq, nv) == 2 and DM.q2c_persist_tiles_per_workgroup(nq, nv) == 3, "the ring phase must carry across tiles"
+    assert nv2 % 2 == 1, "an odd number of videos leaves half a clip tile"
+    for form, dt, lpad, s in RC.k6_ring_cases():
+        hidden, es = RC.k_of(s, dt), RC.ES[dt]
+        persist = lpad == 128 and s * DM.SLICE_BYTES >= DM.K6_PERSIST_MIN_KB
+        assert DM.q2c_form(lpad, hidden, es, combine=False) == ("persist" if persist else "ring"), (dt, lpad, s)
+        assert DM.q2c_form(lpad, hidden, es, combine=True) == "ring", (dt, lpad, s)
+    for form, dt, lpad, hidden in RC.k6_staged_cases():
+        assert [DM.q2c_form(lpad, hidden, RC.ES[dt], combine=c) for c in (False, True)] == ["staged", "staged"], (dt, lpad, hidden)
+    for form, dt, d in RC.l2n_cases():
+        es = RC.ES[dt]
+        lim, beyond = RC.L2N_WIDTHS[dt]
+        assert lim // (16 // es) == 32 * DM.L2N_MAXJ and beyond == lim + 8 and beyond % (16 // es) == 0      # refused for its width alone
+        assert DM.l2n_vec_ok(lim, es) and not DM.l2n_vec_ok(beyond, es)
+        assert DM.tile_rows_l2norm_ok(lim, es) and not DM.tile_rows_l2norm_ok(beyond, es)
+
+
+def test_attention_cases_reach_both_kernels():
+    problems = []
+    for dt in RC.GEMM_DTYPES:
+        forms = {}
+        for _, _, dh, nh, (n, lq, lk) in RC.attention_cases((dt,)):
+            forms.setdefault((DM.attn_form(lq, lk, dh * nh, nh, RC.ES[dt]), dh), set()).add(nh)
+        for dh in DM.ATTN_DH:
+            for kern in ("small", "large"):
+                heads = forms.get((kern, dh), set())
+                problems += need(heads, [h for h in RC.ATTN_HEADS], "attention %s kernel, %s, DH = %d, n_heads" % (kern, dt, dh))
+        refused = sorted(k for k in forms if k[0].startswith("refused"))
+        assert not refused, refused                  # (a refusal would show as a skipped GPU case with its reason in the id)
+    assert set(RC.ATTN_HEADS) - {4} and 96 in DM.ATTN_DH
+    # the whole block: both kernels x every DH x every head count, BertSelfOutput on its unfused tail, hidden sizes beyond the model's
+    for dt in RC.GEMM_DTYPES:
+        forms, hidden = {}, set()
+        for _, _, dh, nh, (n, l) in RC.attention_block_cases((dt,)):
+            assert not DM.gemm_ln_fused(n * l, dh * nh, dh * nh, RC.ES[dt]) and (dh * nh) % 8 == 0, (dt, dh, nh, n, l)
+            form = DM.attn_form(l, l, dh * nh, nh, RC.ES[dt])
+            assert not form.startswith("refused"), (dt, dh, nh, l, form)
+            forms.setdefault((form, dh), set()).add(nh)
+            hidden.add(dh * nh)
+        for dh in DM.ATTN_DH:
+            for kern in ("small", "large"):
+                problems += need(forms.get((kern, dh), set()), list(RC.ATTN_HEADS),
+                                 "attention_block %s kernel, %s, DH = %d, n_heads" % (kern, dt, dh))
+        problems += need(hidden, [96, 288, 576, 1536], "attention_block %s unfused BertSelfOutput, hidden" % dt)
+    # the small kernel packs four (sequence, head) units per workgroup: the unit counts leave every remainder
+    rem = {(n * nh) % 4 for _, _, _, nh, (n, lq, lk) in RC.attention_cases(("bf16",)) if max(lq, lk) <= DM.ATTN_SMALL_MAX_L}
+    problems += need(rem, [0, 1, 2, 3], "attention small kernel, units % 4")
+    for _, _, dh, nh, (n, lq, lk) in RC.attention_cases(("bf16",)):
+        assert DM.attn_train_ok(lq, lk, dh * nh, nh)
+    report(problems)
+
+
+# ---- no class is missing ------------------------------------------------------------------------------------------------------
+def test_every_slice_class_of_the_gemm_forms_is_present():
+    problems = []
+    for dt in RC.GEMM_DTYPES:
+        for mn in RC.GEMM256P_SHAPES:
+            sl = [s for f, d, shp, s in RC.gemm256p_cases() if d == dt and shp == mn]
+            problems += need(residues(sl, 4), all_residues(4), "gemm256p %s %s" % (dt, mn))
+            problems += need(sl, [DM.GEMM_MIN_KB // DM.SLICE_BYTES], "gemm256p %s %s: the minimum n_slices =" % (dt, mn))
+        for mn in RC.GEMM256_SHAPES:
+            sl = [s for f, d, shp, s in RC.gemm256_cases() if d == dt and shp == mn]
+            main = {"no steady-state step (n_slices = 4)" if s == 4 else "one steady-state pair (n_slices = 6)" if s == 6
+                    else "several steady-state pairs, n_slices = %d (mod 4)" % (s % 4) for s in sl}
+            problems += need(main, ["no steady-state step (n_slices = 4)", "one steady-state pair (n_slices = 6)",
+                                    "several steady-state pairs, n_slices = 0 (mod 4)",
+                                    "several steady-state pairs, n_slices = 2 (mod 4)"], "gemm256 %s %s" % (dt, mn))
+            problems += need(sl, [10, 14], "gemm256 %s %s: n_slices =" % (dt, mn))
+        for h in RC.LN_WIDTHS:
+            sl = [s for f, d, n, s in RC.ln_cases() if d == dt and n == h]
+            problems += need(residues(sl, 4), all_residues(4), "LayerNorm-epilogue GEMM %s N = %d" % (dt, h))
+            problems += need(sl, [DM.GEMM_MIN_KB // DM.SLICE_BYTES], "LayerNorm-epilogue GEMM %s N = %d: the minimum n_slices =" % (dt, h))
+        for bmn in (32, 64, 128):
+            loops = {}
+            for f, d, (m, n), ns, k in RC.small_cases():
+                if d == dt and f == "small%d" % bmn:
+                    loops.setdefault(DM.small_kloop(k, RC.ES[dt], bmn), set()).add((ns, (k * RC.ES[dt]) % 128 != 0))
+            for loop in (("plain",) if bmn == 128 else ("deep3", "deep2", "plain")):
+                got = loops.get(loop, set())
+                if len({ns for ns, _ in got}) < 2:
+                    problems.append("small-tile GEMM %d %s: fewer than two step counts on the %s K loop" % (bmn, dt, loop))
+                problems += need({p for _, p in got}, [False, True], "small-tile GEMM %d %s, %s K loop, partial last step =" % (bmn, dt, loop))
+    forms = {DM.f16s_form(m, RC.F16S_N, k).split("-")[0].rstrip("0123456789") for _, m, k in RC.f16s_cases()}
+    problems += need(forms, ["gemm", "small"], "split-f16 GEMM, kernel")
+    problems += need(residues([6 * k // 64 for k in RC.F16S_KS], 4), all_residues(4), "split-f16 GEMM")
+    report(problems)
+
+
+def test_every_slice_class_of_the_k6_forms_is_present():
+    problems = []
+    for form in RC.K6_FORMS:
+        depth = DM.q2c_persist_slots(RC.K6_TILED[form], RC.K6_MASK[form])
+        for dt in RC.K6_DTYPES[form]:
+            for shp in RC.K6_PERSIST_SHAPES:
+                for n_mod in RC.K6_N_MOD:
+                    what = "q2c_persist %s (%d slots) %s %s n_mod %d" % (form, depth, dt, shp, n_mod)
+                    sl = [s for f, d, s, sh, nm in RC.k6_persist_cases() if (f, d, sh, nm) == (form, dt, shp, n_mod)]
+                    problems += need(residues(sl, depth), all_residues(depth), what)
+                    problems += need(sl, [DM.K6_PERSIST_MIN_KB // DM.SLICE_BYTES], what + ": the minimum n_slices =")
+                    if not any(s > RC.MODEL_MAX_SLICES for s in sl):
+                        problems.append("%s: no case with n_slices > %d (the largest model width)" % (what, RC.MODEL_MAX_SLICES))
+    problems += need([f for f in RC.K6_FORMS if "f16" in RC.K6_DTYPES[f]], [f for f in RC.K6_FORMS if RC.K6_TILED[f]],
+                     "q2c_persist f16 operands, tiled form")
+    for dt in RC.GEMM_DTYPES:
+        for lpad in (16, 48, 112):
+            sl = [s for f, d, lp, s in RC.k6_ring_cases() if d == dt and lp == lpad]
+            problems += need(sl, [2, 4, 6, 8, 10, 12, 14], "q2c_ring %s lpad %d: n_slices =" % (dt, lpad))
+        sl = [s for f, d, lp, s in RC.k6_ring_cases() if d == dt and lp == 128]
+        problems += need(sl, [2, 4], "q2c_ring %s lpad 128 below the persistent kernel's minimum: n_slices =" % dt)
+        problems += need(sl, [6, 8, 10, 12, 14], "q2c_ring %s lpad 128 combine pass: n_slices =" % dt)
+        for lpad in RC.K6_STAGED_LPADS:
+            hs = [h for f, d, lp, h in RC.k6_staged_cases() if d == dt and lp == lpad]
+            steps = {"%s 128-byte steps" % ("<= 1" if h * RC.ES[dt] <= 128 else "2" if h * RC.ES[dt] <= 256 else "> 2") for h in hs}
+            problems += need(steps, ["<= 1 128-byte steps", "2 128-byte steps", "> 2 128-byte steps"],
+                             "register-staged q2c %s lpad %d" % (dt, lpad))
+        problems += need(RC.K6_STAGED_LPADS, [16, 48, 128], "register-staged q2c %s: lpad =" % dt)
+    report(problems)
+
+
+def test_a_removed_class_is_named(monkeypatch):
+    """the failure message names the form and the class: drop every count = 0 (mod 5) from the K6 sweep."""
+    import pytest
+    monkeypatch.setattr(RC, "K6_PERSIST_SLICES", tuple(s for s in RC.K6_PERSIST_SLICES if s % 5))
+    with pytest.raises(AssertionError) as e:
+        test_every_slice_class_of_the_k6_forms_is_present()
+    assert "q2c_persist nomask (5 slots) bf16 (520, 300) n_mod 2: no case with n_slices = 0 (mod 5)" in str(e.value)
+    assert "q2c_persist rowmajor" not in str(e.value)        # the four-slot forms keep both of their classes
+
+
+# ---- the mirrors' literals are the sources' --------------------------------------------------------------------------------------
+def ints(pattern, text):
+    found = re.findall(pattern, text)
+    assert found, "pattern %r no longer matches the source" % pattern
+    return [tuple(int(v) for v in f) if isinstance(f, tuple) else int(f) for f in found]
+
+
+def test_threshold_literals_agree_with_the_sources():
+    linear, g256, g256p = src("linear.hip"), src("gemm256.hip"), src("gemm256p.hip")
+    assert ints(r"cdiv\(M, 256\) \* cdiv\(N, 256\) < (\d+)", linear) == [DM.FEW_TILES]
+    assert ints(r"cdiv\(M, 256\) \* cdiv\(N, 256\) >= (\d+)", g256p) == [DM.GEMM256P_MIN_TILES]
+    assert ints(r"LN_FUSED_MIN_ROWS = (\d+)", g256p) == [DM.LN_FUSED_MIN_ROWS]
+    assert set(ints(r"kb % 128 == 0 && kb >= (\d+)", g256 + g256p)) == {DM.GEMM_MIN_KB}
+    assert ints(r"M >= (\d+) && N >= (\d+) && kb % 128", g256) == [(256, 128)]
+    assert ints(r"K3 \* 2\) % 128 == 0 && K3 \* 2 >= (\d+)", g256) == [DM.GEMM_MIN_KB]
+    assert ints(r"wg128 >= (\d+) \? 128 : wg128 \* 4 >= (\d+) \? 64 : 32", linear) == [(512, 192)]
+    assert ints(r"nsteps % (\d) == 0\) gemm_mainloop_deep", linear) == [3, 2]
+    q2c, persist, ring = src("q2c.hip"), src("q2c_persist.hip"), src("q2c_ring.hip")
+    assert set(ints(r"dt_size\(dt\) >= (\d+)", q2c) + ints(r"kb % 128 == 0 && kb >= (\d+)", q2c + persist)) == {DM.K6_PERSIST_MIN_KB}
+    assert ints(r"NSLOT = FIVE \? (\d) : (\d)", persist) == [(5, 4)] and "FIVE = NOMASK || BITMASK" in persist
+    assert ints(r"constexpr int LEAD = (\d+)", ring) == [5]
+    assert ints(r"ROWB = (\d+)", persist + ring + g256 + g256p).count(DM.SLICE_BYTES) >= 4
+    assert ints(r"L2N_MAXJ = (\d+)", src("l2norm.h")) == [DM.L2N_MAXJ]
+    assert ints(r"hidden / vec <= (\d+) \* L2N_MAXJ", src("index_build.hip")) == [32]
+    assert set(ints(r"d / \d <= (\d+) \* L2N_MAXJ", linear)) == {32}
+    att, att_t = src("attention.hip"), src("attention_train.hip")
+    assert tuple(ints(r"XML_ATTN_CASE\((\d+)\)", att)) == DM.ATTN_DH
+    assert tuple(ints(r"case (\d+): return at_launch", att_t)) == DM.ATTN_DH
+    assert ints(r"if \(lq <= (\d+) && lk <= (\d+)\)", att) == [(DM.ATTN_SMALL_MAX_L, DM.ATTN_SMALL_MAX_L)]
+    assert ints(r"lq > (\d+) \|\| lk > (\d+)", att + att_t) == [(DM.ATTN_MAX_L, DM.ATTN_MAX_L)] * 3
+    assert ints(r"lds > (\d+) \* 1024\) return XML_ERR_UNSUPPORTED", att) == [DM.LDS_BYTES // 1024]
+    assert set(ints(r"units \+ 3\) / (\d)", att)) == {4}

@@ -98,6 +98,12 @@ template <> struct MmaInit<f16_t> {
 // XML_F16 operands are the hi planes of xml_split_f16_rows(fixed_log2 = XML_F16_UNIT_LOG2): unit-norm rows scaled by
 // 2^14 on both sides, so a score leaves the accumulators scaled by 2^28 (the exact-rank FILTER, inference.stage_exact_topk)
 static constexpr float K6_F16_OUT_SCALE = 1.f / (float)(1u << (2 * XML_F16_UNIT_LOG2));
+// mask_logits' fill value in the accumulators' scale.  f16 scores are scaled back AFTER the masked maximum and the mean over
+// the modalities, so their fill carries the same 2^28 (a power of two: every masked expression is exactly the unscaled one
+// times 2^28) -- a video without a valid clip comes out at -1e10 (-5e9 when one of two modalities has none), as in every
+// other K6 kernel and as the exact-rank certificate assumes (exact.hip), not at -1e10 / 2^28 = -37.25.
+template <typename T> struct K6Fill { static constexpr float v = -1e10f; };
+template <> struct K6Fill<f16_t> { static constexpr float v = -1e10f * (float)(1u << (2 * XML_F16_UNIT_LOG2)); };
 
 // MFMA issue order inside a 4 x 4 block.  Boustrophedon (row m walks n upwards, row m + 1 downwards: exactly ONE operand
 // changes between consecutive MFMAs, 15 operand switches per 16 instead of 18) measured on one box, same process pair:
@@ -490,7 +496,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
           for (int r = 0; r < 4; ++r) {
             const bool on = (lw >> r) & 1u;
 #pragma unroll
-            for (int m = 0; m < 4; ++m) run[m] = fmaxf(run[m], on ? acc[m][n][r] : -1e10f);
+            for (int m = 0; m < 4; ++m) run[m] = fmaxf(run[m], on ? acc[m][n][r] : K6Fill<T>::v);
           }
         }
         if (id >= 0 || (n == 7 && id == -3)) {                               // a video ends here (or leaves this wave tile)
@@ -547,7 +553,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
             for (int r = 0; r < 4; ++r) {
               const bool on = (lw >> r) & 1u;
 #pragma unroll
-              for (int m = 0; m < 4; ++m) run[m] = fmaxf(run[m], on ? acc[m][n][r] : -1e10f);
+              for (int m = 0; m < 4; ++m) run[m] = fmaxf(run[m], on ? acc[m][n][r] : K6Fill<T>::v);
             }
           }
         }
@@ -577,7 +583,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
             for (int r = 0; r < 4; ++r)
 #pragma unroll
               for (int m = 0; m < 4; ++m)
-                run[m] = fmaxf(run[m], acc[m][n][r] * mv[r] + (1.f - mv[r]) * -1e10f);   // mask_logits, xml/model_xml.py:640-641
+                run[m] = fmaxf(run[m], acc[m][n][r] * mv[r] + (1.f - mv[r]) * K6Fill<T>::v);   // mask_logits, xml/model_xml.py:640-641
           }
         }
       }

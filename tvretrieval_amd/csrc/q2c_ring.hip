@@ -123,7 +123,10 @@ __global__ __launch_bounds__(512, 2) void q2c_scores_kernel_ring(const T* __rest
 #pragma unroll
   for (int u = 0; u < LEAD; ++u)
     if (u < n_units) issue_unit(u);
-  __builtin_amdgcn_s_waitcnt(0x0f76);       // vmcnt(6): units 0, 1 (slice 0) landed
+  // units 0, 1 (slice 0) landed: all but the 3 younger units' 6 DMAs -- or all but 2 units' 4 DMAs when the whole operand is
+  // two slices (hidden * sizeof(T) == 128: only 4 units exist, vmcnt(6) would cover unit 0 alone)
+  if (n_units >= LEAD) __builtin_amdgcn_s_waitcnt(0x0f76);
+  else __builtin_amdgcn_s_waitcnt(0x0f74);
   __builtin_amdgcn_s_barrier();
   if (wave >= 4) __builtin_amdgcn_s_barrier();   // stagger the second wave group by one barrier interval
 
