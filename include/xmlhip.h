@@ -963,6 +963,56 @@ int xml_nms_svmr_batched_host(const double* st, const double* ed, const double* 
                               int64_t ld, double thd, int max_before, int max_after, int32_t* out_index, int64_t ld_out,
                               int32_t* out_count, int n_threads);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dispatch introspection: which kernel a shape lands on.  Host arithmetic only -- no device memory, no GPU, no stream.
+ * Every answer is the PRODUCT dispatch (the debug library's xml_debug_* switches do not move it) and comes from the
+ * function the launcher itself calls (csrc/dispatch.h), like xml_q2c_tiled_ok, xml_q2c_tile_rows_l2norm_ok,
+ * xml_gemm_tn_supported and xml_attention_train_supported above.  Callers: tests that place a case on a kernel, tools
+ * that label a measurement.  A value outside an entry's domain (unknown dt, sizes <= 0) returns -1.
+ * --------------------------------------------------------------------------------------------- */
+typedef enum { XML_GEMM_SMALL = 0, XML_GEMM_256 = 1, XML_GEMM_256P = 2 } xml_gemm_kernel;
+/* flags; the small-tile kernel's tile size for (M, N) is one of the three TILE bits, whatever kernel the shape takes */
+typedef enum {
+  XML_GEMM_FEW = 1,           /* fewer 256 x 256 tiles than the ring kernels are worth: the small-tile kernel    */
+  XML_GEMM_256_OK = 2,        /* the one-tile-per-workgroup ring kernel takes the shape (dt XML_F16S: its f16 form) */
+  XML_GEMM_256P_OK = 4,       /* the persistent ring kernel takes the shape                                       */
+  XML_GEMM_LN_FUSED = 8,      /* a LayerNorm behind this GEMM runs in its epilogue (xml_linear_ln_relu_pos, ...)  */
+  XML_GEMM_TILE32 = 32, XML_GEMM_TILE64 = 64, XML_GEMM_TILE128 = 128
+} xml_gemm_rules;
+typedef enum { XML_KLOOP_PLAIN = 1, XML_KLOOP_DEEP2 = 2, XML_KLOOP_DEEP3 = 3 } xml_gemm_kloop;   /* loads N steps ahead */
+typedef enum { XML_Q2C_UNSUPPORTED = 0, XML_Q2C_STAGED = 1, XML_Q2C_RING = 2, XML_Q2C_PERSIST = 3, XML_Q2C_NONE = 4 } xml_q2c_kernel;
+typedef enum { XML_Q2C_WALK_QSH = 0, XML_Q2C_WALK_TILES_PER_WORKGROUP = 1, XML_Q2C_WALK_RING_SLOTS = 2 } xml_q2c_walk;
+typedef enum {
+  XML_ATTN_SMALL = 0, XML_ATTN_LARGE = 1, XML_ATTN_REFUSED_HEADS = 2, XML_ATTN_REFUSED_LENGTH = 3,
+  XML_ATTN_REFUSED_LDS = 4, XML_ATTN_REFUSED_DH = 5
+} xml_attn_kernel;
+typedef enum { XML_L2N_SCALAR = 0, XML_L2N_VEC16 = 1 } xml_l2norm_kernel;
+typedef enum {
+  XML_DC_SLICE_BYTES = 0,           /* bytes of K per row in one ring slot                                        */
+  XML_DC_RING_SLOTS,                /* ring depth of gemm256 / gemm256p / q2c_ring / q2c_persist ...              */
+  XML_DC_RING_SLOTS_NOMASK,         /* ... and of q2c_persist's tiled forms that need no mask patches             */
+  XML_DC_RING_LEAD,                 /* q2c_ring: DMA units in front of the phase being computed                   */
+  XML_DC_LDS_BYTES,
+  XML_DC_GEMM_FEW_TILES, XML_DC_GEMM256P_MIN_TILES, XML_DC_GEMM_LN_MIN_ROWS, XML_DC_GEMM_MIN_K_BYTES,
+  XML_DC_GEMM256_MIN_M, XML_DC_GEMM256_MIN_N,
+  XML_DC_GEMM_TILE128_MIN_WG, XML_DC_GEMM_TILE64_MIN_WG,      /* workgroups a tile size must reach to be taken     */
+  XML_DC_Q2C_PERSIST_MIN_K_BYTES,
+  XML_DC_L2N_MAXJ, XML_DC_L2N_LANES,                          /* 16-byte chunks per lane, lanes per row             */
+  XML_DC_ATTN_MAX_L, XML_DC_ATTN_SMALL_MAX_L, XML_DC_ATTN_SMALL_UNITS,
+  XML_DC_ATTN_N_HEAD_SIZES, XML_DC_ATTN_HEAD_SIZE0            /* head size i is XML_DC_ATTN_HEAD_SIZE0 + i          */
+} xml_dispatch_constant;
+int64_t xml_dispatch_const(int which);                                       /* xml_dispatch_constant -> value  */
+int xml_dispatch_gemm(int64_t M, int N, int K, int dt);                      /* xml_gemm_kernel; dt f32 / bf16 / f16s */
+int xml_dispatch_gemm_rules(int64_t M, int N, int K, int dt);                /* xml_gemm_rules flags            */
+int xml_dispatch_gemm_kloop(int K, int dt, int tile);                        /* xml_gemm_kloop of the small-tile kernel */
+int xml_dispatch_q2c(int lpad, int hidden, int dt, int combine);             /* xml_q2c_kernel of xml_q2c_scores */
+/* launch number `launch` (0, 1, ...) of one xml_q2c_scores_fused call; XML_Q2C_NONE behind its last launch */
+int xml_dispatch_q2c_fused(int n_mod, int lpad, int hidden, int dt, int launch);
+/* the persistent K6 kernel's walk: QSH / TILES_PER_WORKGROUP of (a, b) = (nq, nv); RING_SLOTS of (a, b) = (tiled, mask_mode) */
+int xml_dispatch_q2c_walk(int what, int a, int b);
+int xml_dispatch_attention(int lq, int lk, int hidden, int n_heads, int dt); /* xml_attn_kernel of the attention core */
+int xml_dispatch_l2norm(int d, int dt);                                      /* xml_l2norm_kernel of xml_l2norm_rows */
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ kernels (gemm256p.hip, q2c_persist.hip) do not restart their ring per tile or pe
 ring depth decides in which slot every later tile starts.  The model's own widths (128 ... 768, 3 072) reach only some classes.
 
 Every case is a plain tuple whose first entries name the form; `case_id` makes the pytest id."""
-import dispatch_mirror as DM
+import kernel_forms as DM
 
 ES = {"f32": 4, "bf16": 2, "f16": 2}
 MODEL_MAX_SLICES = 48           # hidden 768 in f32: the largest count the model's hidden sizes give K6

@@ -590,7 +590,7 @@ for dt in (F32, BF16, "f16s"):
     for rows, note in ((118, "one ragged row tile"), (300, "more rows than one 256-row block, ragged end")):
         _ln_relu_pos_packed(dt, 72, 128, rows, note)
         _attention_block_varlen(dt, 128, 4, rows, note)
-for dt, d_in in ((F32, 64), (BF16, 128)):          # K bytes = 256; rows = 2048 + 37: xmli_gemm_ln_eligible accepts both entries
+for dt, d_in in ((F32, 64), (BF16, 128)):          # K bytes = 256; rows = 2048 + 37: dispatch::gemm_ln_fused accepts both entries
     _ln_relu_pos_packed(dt, d_in, 256, 2085, "hidden 256: the LayerNorm-epilogue GEMM beside the 3-launch scratch formula", nbytes=1 << 25)
     _ln_relu_pos_packed(dt, d_in, 512, 2085, "hidden 512: the epilogue GEMM's 64 MiB scratch inside the packed workspace",
                         nbytes=(64 << 20) + (1 << 26))
@@ -2004,6 +2004,9 @@ for _s in ("xml_rccl_available", "xml_rccl_unique_id", "xml_rccl_comm_init", "xm
            "xml_rccl_allreduce_avg_f32", "xml_rccl_allgather_topk_workspace_bytes", "xml_rccl_allgather_topk",
            "xml_rccl_topk_by_owner_workspace_bytes", "xml_rccl_topk_by_owner"):
     EXEMPT[_s] = "xml_rccl_*: needs a communicator; tests/test_gpu_dist.py"
+for _s in ("xml_dispatch_const", "xml_dispatch_gemm", "xml_dispatch_gemm_rules", "xml_dispatch_gemm_kloop", "xml_dispatch_q2c",
+           "xml_dispatch_q2c_fused", "xml_dispatch_q2c_walk", "xml_dispatch_attention", "xml_dispatch_l2norm"):
+    EXEMPT[_s] = "dispatch introspection: integers in, an enum out, no memory; tests/test_reduction_width_plan.py"
 
 
 # =====================================================================================================================

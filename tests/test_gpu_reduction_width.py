@@ -25,7 +25,7 @@ import math
 import pytest
 import torch
 
-import dispatch_mirror as DM
+import kernel_forms as DM
 import numerics_regimes as NR
 import reduction_width_cases as RC
 import train_bf16_cases as TC

@@ -3,8 +3,8 @@
 The library picks kernels by row count (linear.hip xmli_gemm / launch_gemm, gemm256.hip, gemm256p.hip and the LayerNorm
 epilogue's row threshold).  The corpus index being independent of the context batch, vcmr_search_host's chunked records
 equalling the single launch and the packed query encoder equalling the padded one all rest on those forms giving the
-same bits.  Each test below recomputes row PREFIXES of one large input on both sides of every edge (the helpers mirror
-the C++ predicates and assert that the chosen pairs really straddle them) and compares bit for bit; the GEMMs are also
+same bits.  Each test below recomputes row PREFIXES of one large input on both sides of every edge (the helpers ask the
+library for its dispatch rules, tests/kernel_forms.py, and assert that the chosen pairs really straddle them) and compares bit for bit; the GEMMs are also
 held against float64 with a bound that scales with K, the LayerNorm rows against a float64 LayerNorm of the same
 pre-LayerNorm values.  Run on the MI355X box:  pytest -m gpu"""
 import ctypes
@@ -12,8 +12,8 @@ import ctypes
 import pytest
 import torch
 
-from dispatch_mirror import (cdiv, few, gemm256_ok, gemm256p_ok, gemm_form, gemm_ln_fused,  # noqa: F401
-                             small_bmn, small_kloop)      # the dispatch predicates, one per C++ decision
+from kernel_forms import (cdiv, few, gemm256_ok, gemm256p_ok, gemm_form, gemm_ln_fused,  # noqa: F401
+                          small_bmn, small_kloop)      # the library's dispatch rules (xml_dispatch_*)
 
 pytestmark = pytest.mark.gpu
 

@@ -1,21 +1,11 @@
 """The plan of tests/test_gpu_reduction_width.py, checked without a GPU: from the same tables (tests/reduction_width_cases.py)
-* every case lands on the kernel it is meant for, by the mirrors of the dispatch predicates (tests/dispatch_mirror.py);
+* every case lands on the kernel it is meant for, by the library's own dispatch rules (tests/kernel_forms.py);
 * every residue class of the slice count modulo the ring depth, every minimum count and a count above the model's largest
   width is present for every form -- a table edit that empties a class fails here with the class named;
-* the threshold literals of the mirrors are the ones in the .hip sources, so a kernel change that moves a threshold cannot
-  silently move the cases to another kernel."""
-import os
-import re
-
-import dispatch_mirror as DM
+* the thresholds the tables were laid out for are the ones the library reports, so a kernel change that moves a threshold
+  cannot silently move the cases to another kernel."""
+import kernel_forms as DM
 import reduction_width_cases as RC
-
-CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tvretrieval_amd", "csrc")
-
-
-def src(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
 
 
 def need(present, required, what):
@@ -200,35 +190,25 @@ def test_a_removed_class_is_named(monkeypatch):
     assert "q2c_persist rowmajor" not in str(e.value)        # the four-slot forms keep both of their classes
 
 
-# ---- the mirrors' literals are the sources' --------------------------------------------------------------------------------------
-def ints(pattern, text):
-    found = re.findall(pattern, text)
-    assert found, "pattern %r no longer matches the source" % pattern
-    return [tuple(int(v) for v in f) if isinstance(f, tuple) else int(f) for f in found]
-
-
-def test_threshold_literals_agree_with_the_sources():
-    linear, g256, g256p = src("linear.hip"), src("gemm256.hip"), src("gemm256p.hip")
-    assert ints(r"cdiv\(M, 256\) \* cdiv\(N, 256\) < (\d+)", linear) == [DM.FEW_TILES]
-    assert ints(r"cdiv\(M, 256\) \* cdiv\(N, 256\) >= (\d+)", g256p) == [DM.GEMM256P_MIN_TILES]
-    assert ints(r"LN_FUSED_MIN_ROWS = (\d+)", g256p) == [DM.LN_FUSED_MIN_ROWS]
-    assert set(ints(r"kb % 128 == 0 && kb >= (\d+)", g256 + g256p)) == {DM.GEMM_MIN_KB}
-    assert ints(r"M >= (\d+) && N >= (\d+) && kb % 128", g256) == [(256, 128)]
-    assert ints(r"K3 \* 2\) % 128 == 0 && K3 \* 2 >= (\d+)", g256) == [DM.GEMM_MIN_KB]
-    assert ints(r"wg128 >= (\d+) \? 128 : wg128 \* 4 >= (\d+) \? 64 : 32", linear) == [(512, 192)]
-    assert ints(r"nsteps % (\d) == 0\) gemm_mainloop_deep", linear) == [3, 2]
-    q2c, persist, ring = src("q2c.hip"), src("q2c_persist.hip"), src("q2c_ring.hip")
-    assert set(ints(r"dt_size\(dt\) >= (\d+)", q2c) + ints(r"kb % 128 == 0 && kb >= (\d+)", q2c + persist)) == {DM.K6_PERSIST_MIN_KB}
-    assert ints(r"NSLOT = FIVE \? (\d) : (\d)", persist) == [(5, 4)] and "FIVE = NOMASK || BITMASK" in persist
-    assert ints(r"constexpr int LEAD = (\d+)", ring) == [5]
-    assert ints(r"ROWB = (\d+)", persist + ring + g256 + g256p).count(DM.SLICE_BYTES) >= 4
-    assert ints(r"L2N_MAXJ = (\d+)", src("l2norm.h")) == [DM.L2N_MAXJ]
-    assert ints(r"hidden / vec <= (\d+) \* L2N_MAXJ", src("index_build.hip")) == [32]
-    assert set(ints(r"d / \d <= (\d+) \* L2N_MAXJ", linear)) == {32}
-    att, att_t = src("attention.hip"), src("attention_train.hip")
-    assert tuple(ints(r"XML_ATTN_CASE\((\d+)\)", att)) == DM.ATTN_DH
-    assert tuple(ints(r"case (\d+): return at_launch", att_t)) == DM.ATTN_DH
-    assert ints(r"if \(lq <= (\d+) && lk <= (\d+)\)", att) == [(DM.ATTN_SMALL_MAX_L, DM.ATTN_SMALL_MAX_L)]
-    assert ints(r"lq > (\d+) \|\| lk > (\d+)", att + att_t) == [(DM.ATTN_MAX_L, DM.ATTN_MAX_L)] * 3
-    assert ints(r"lds > (\d+) \* 1024\) return XML_ERR_UNSUPPORTED", att) == [DM.LDS_BYTES // 1024]
-    assert set(ints(r"units \+ 3\) / (\d)", att)) == {4}
+# ---- the thresholds the tables were laid out for ----------------------------------------------------------------------------------
+def test_pinned_thresholds():
+    """moving a threshold is one edit in csrc/dispatch.h and one here -- and a look at the tables above."""
+    c = DM.const
+    assert (DM.FEW_TILES, DM.GEMM256P_MIN_TILES, DM.LN_FUSED_MIN_ROWS, DM.GEMM_MIN_KB) == (64, 3072, 2048, 256)
+    assert [c(n) for n in ("GEMM256_MIN_M", "GEMM256_MIN_N", "GEMM_TILE128_MIN_WG", "GEMM_TILE64_MIN_WG")] == [256, 128, 512, 192]
+    # the small tiles' K loop: deep 3, then deep 2, by the number of 128-byte steps; 128-wide tiles and f16 operands stay plain
+    assert [DM.small_kloop(32 * ns, 4, 64) for ns in (1, 2, 3, 4, 6)] == ["plain", "deep2", "deep3", "deep2", "deep3"]
+    assert DM.small_kloop(96, 4, 128) == "plain" and DM.small_kloop(192, 2, 32) == "deep3"
+    assert DM.K6_PERSIST_MIN_KB == 384 and (DM.L2N_MAXJ, DM.L2N_LANES) == (8, 32) and DM.ATTN_DH == (32, 64, 96, 128, 192)
+    assert (DM.ATTN_SMALL_MAX_L, DM.ATTN_MAX_L, DM.LDS_BYTES, DM.ATTN_SMALL_UNITS) == (32, 128, 160 * 1024, 4)
+    assert DM.SLICE_BYTES == 64 and (c("RING_SLOTS"), c("RING_SLOTS_NOMASK"), c("RING_LEAD")) == (4, 5, 5)
+    assert [DM.q2c_persist_slots(t, m) for t in (False, True) for m in DM.K6_MASK_FORMS] == [4, 4, 4, 4, 4, 5, 5, 4]
+    # the numbers are the rules' own: each predicate flips exactly at its constant
+    assert DM.few(63 * 256, 256) and not DM.few(63 * 256 + 1, 256)
+    assert not DM.gemm256p_ok(3071 * 256, 256, 64, 4) and DM.gemm256p_ok(3071 * 256 + 1, 256, 64, 4)
+    assert not DM.gemm256_ok(255, 128, 64, 4) and not DM.gemm256_ok(256, 127, 64, 4) and DM.gemm256_ok(256, 128, 64, 4)
+    assert not DM.gemm256_ok(256, 128, 32, 4) and not DM.gemm256_ok(256, 128, 80, 4)       # 128 bytes; 320 bytes: an odd slice count
+    assert [DM.small_bmn(128 * wg, 128) for wg in (47, 48, 511, 512)] == [32, 64, 64, 128]
+    assert not DM.q2c_tiled_ok(128, 64, 4) and DM.q2c_tiled_ok(128, 96, 4) and not DM.q2c_tiled_ok(112, 96, 4)
+    assert DM.attn_form(32, 32, 64, 1, 2) == "small" and DM.attn_form(33, 32, 64, 1, 2) == DM.attn_form(32, 33, 64, 1, 2) == "large"
+    assert DM.attn_form(128, 128, 64, 1, 2) == "large" and DM.attn_form(129, 128, 64, 1, 2) == "refused: longer than 128"

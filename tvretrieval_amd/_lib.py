@@ -230,6 +230,16 @@ SIGNATURES = {
     "xml_clip_grad_norm": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "xml_bert_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                                    c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # dispatch introspection (host arithmetic only; enums in include/xmlhip.h)
+    "xml_dispatch_const": (c_int64, [c_int]),
+    "xml_dispatch_gemm": (c_int, [c_int64, c_int, c_int, c_int]),
+    "xml_dispatch_gemm_rules": (c_int, [c_int64, c_int, c_int, c_int]),
+    "xml_dispatch_gemm_kloop": (c_int, [c_int, c_int, c_int]),
+    "xml_dispatch_q2c": (c_int, [c_int, c_int, c_int, c_int]),
+    "xml_dispatch_q2c_fused": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "xml_dispatch_q2c_walk": (c_int, [c_int, c_int, c_int]),
+    "xml_dispatch_attention": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "xml_dispatch_l2norm": (c_int, [c_int, c_int]),
 }
 
 _lib = None

@@ -14,3 +14,57 @@ extern "C" const char* xml_status_string(int status) {
     default: return "unknown status";
   }
 }
+
+// ---- dispatch introspection: dispatch.h's answers (the product dispatch, in the debug library too) ------------------
+extern "C" int64_t xml_dispatch_const(int which) {
+  namespace d = dispatch;
+  static const int64_t v[] = {      // in the order of xml_dispatch_constant
+      d::SLICE_BYTES, d::RING_SLOTS, d::RING_SLOTS_NOMASK, d::RING_LEAD, d::LDS_BYTES, d::GEMM_FEW_TILES, d::GEMM256P_MIN_TILES,
+      d::GEMM_LN_MIN_ROWS, d::GEMM_MIN_K_BYTES, d::GEMM256_MIN_M, d::GEMM256_MIN_N, d::GEMM_TILE128_MIN_WG, d::GEMM_TILE64_MIN_WG,
+      d::Q2C_PERSIST_MIN_K_BYTES, d::L2N_MAXJ, d::L2N_LANES, d::ATTN_MAX_L, d::ATTN_SMALL_MAX_L, d::ATTN_SMALL_UNITS,
+      d::ATTN_N_HEAD_SIZES};
+  static_assert(sizeof(v) / sizeof(v[0]) == XML_DC_ATTN_HEAD_SIZE0, "one value per xml_dispatch_constant");
+  if (which >= 0 && which < XML_DC_ATTN_HEAD_SIZE0) return v[which];
+  const int i = which - XML_DC_ATTN_HEAD_SIZE0;
+  return i >= 0 && i < d::ATTN_N_HEAD_SIZES ? d::ATTN_HEAD_SIZES[i] : -1;
+}
+static bool gemm_args_ok(int64_t M, int N, int K, int dt) {
+  return M > 0 && N > 0 && K > 0 && (dt == XML_F32 || dt == XML_BF16 || dt == XML_F16S);
+}
+extern "C" int xml_dispatch_gemm(int64_t M, int N, int K, int dt) {
+  return gemm_args_ok(M, N, K, dt) ? (int)dispatch::gemm_kernel(M, N, K, dt) : -1;
+}
+extern "C" int xml_dispatch_gemm_rules(int64_t M, int N, int K, int dt) {
+  if (!gemm_args_ok(M, N, K, dt)) return -1;
+  const int tile = dispatch::gemm_small_tile(M, N);       // 32 / 64 / 128 = XML_GEMM_TILE32 / 64 / 128
+  if (dt == XML_F16S) return tile | (dispatch::gemm256_f16s_ok(M, N, 3 * K) ? XML_GEMM_256_OK : 0);
+  return tile | (dispatch::gemm_few(M, N) ? XML_GEMM_FEW : 0) | (dispatch::gemm256_ok(M, N, K, dt) ? XML_GEMM_256_OK : 0) |
+         (dispatch::gemm256p_ok(M, N, K, dt) ? XML_GEMM_256P_OK : 0) | (dispatch::gemm_ln_fused(M, N, K, dt) ? XML_GEMM_LN_FUSED : 0);
+}
+extern "C" int xml_dispatch_gemm_kloop(int K, int dt, int tile) {
+  if (K <= 0 || (tile != 32 && tile != 64 && tile != 128) || !gemm_args_ok(1, 1, K, dt)) return -1;
+  if (dt == XML_F16S) return XML_KLOOP_PLAIN;             // f16 operands over K' = 3 K
+  return dispatch::gemm_small_deep(tile, false) ? dispatch::gemm_small_kloop(K * (int)dt_size(dt)) : XML_KLOOP_PLAIN;
+}
+extern "C" int xml_dispatch_q2c(int lpad, int hidden, int dt, int combine) {
+  return lpad <= 0 || hidden <= 0 || !dispatch::q2c_dt_ok(dt) ? -1 : dispatch::q2c_kernel(lpad, hidden, dt, combine != 0);
+}
+extern "C" int xml_dispatch_q2c_fused(int n_mod, int lpad, int hidden, int dt, int launch) {
+  if (n_mod < 1 || n_mod > 2 || launch < 0 || lpad <= 0 || hidden <= 0 || !dispatch::q2c_dt_ok(dt)) return -1;
+  return dispatch::q2c_fused_kernel(n_mod, lpad, hidden, dt, launch);
+}
+extern "C" int xml_dispatch_q2c_walk(int what, int a, int b) {
+  if (what == XML_Q2C_WALK_RING_SLOTS) return a < 0 || a > 1 || b < 0 || b > 3 ? -1 : dispatch::q2c_ring_slots(a != 0, b);
+  if (a <= 0 || b <= 0) return -1;
+  const int tq = dispatch::q2c_tq(a), tc = dispatch::q2c_tc(b);
+  if (what == XML_Q2C_WALK_QSH) return dispatch::q2c_qsh(tq, tc);
+  if (what == XML_Q2C_WALK_TILES_PER_WORKGROUP) return dispatch::q2c_tiles_per_workgroup(tq, tc);
+  return -1;
+}
+extern "C" int xml_dispatch_attention(int lq, int lk, int hidden, int n_heads, int dt) {
+  const bool ok = lq > 0 && lk > 0 && hidden > 0 && (dt == XML_F32 || dt == XML_BF16);
+  return ok ? dispatch::attn_kernel(lq, lk, hidden, n_heads, dt) : -1;
+}
+extern "C" int xml_dispatch_l2norm(int d, int dt) {
+  return d <= 0 || (dt != XML_F32 && dt != XML_BF16) ? -1 : dispatch::l2n_vec_ok(d, dt) ? XML_L2N_VEC16 : XML_L2N_SCALAR;
+}

@@ -510,43 +510,25 @@ __global__ __launch_bounds__(256) void attention_core_small_kernel(const T* __re
   }
 }
 
-static size_t attn_small_lds_bytes(int lk, int dh, int dt) {
-  const int es = (int)dt_size(dt), ce = 64 / es;
-  const int lkp = (lk + ce - 1) / ce * ce;
-  const size_t k_stride = (size_t)dh * es + 16, vt_stride = (size_t)lkp * es + 16;
-  const size_t kvb = es == 2 ? (size_t)32 * k_stride : std::max((size_t)32 * k_stride, (size_t)dh * vt_stride);
-  return 4 * (kvb + 16 * vt_stride);
-}
-
-static size_t attn_lds_bytes(int lk, int dh, int dt) {
-  const int es = (int)dt_size(dt), ce = 64 / es;
-  const int lkp = (lk + ce - 1) / ce * ce;
-  const size_t k_stride = (size_t)dh * es + 16, vt_stride = (size_t)lkp * es + 16;
-  const size_t kvb = es == 2 ? (size_t)lkp * k_stride          // bf16: V row-major over K (transpose reads)
-                             : std::max((size_t)((lk + 15) / 16 * 16) * k_stride, (size_t)dh * vt_stride);
-  return kvb + 4 * 16 * vt_stride;
-}
-
 template <typename T, typename OutT, int DH>
 static int launch_attn(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* q_mask,
                        const float* k_mask, void* out, int64_t n, int lq, int lk, int hidden, int n_heads,
-                       size_t lds, hipStream_t st) {
-  if (lq <= 32 && lk <= 32) {
-    const size_t lds_s = attn_small_lds_bytes(lk, DH, std::is_same<T, float>::value ? XML_F32 : XML_BF16);
-    if (lds_s <= 160 * 1024) {
-      auto ks = attention_core_small_kernel<T, OutT, DH>;
-      if (lds_s > 64 * 1024 && !xml_lds_attr_once<attention_core_small_kernel<T, OutT, DH>>(160 * 1024))
-        return XML_ERR_LAUNCH;
-      const int64_t units = n * n_heads;
-      hipLaunchKernelGGL(ks, dim3((unsigned)((units + 3) / 4)), dim3(256), lds_s, st, (const T*)q, ldq, (const T*)k, ldk,
-                         (const T*)v, ldv, q_mask, k_mask, (OutT*)out, hidden, lq, lk, n_heads, units,
-                         sqrtf((float)DH), (const int32_t*)nullptr);
-      XML_CHECK_LAUNCH();
-      return XML_OK;
-    }
+                       bool small, hipStream_t st) {
+  if (small) {
+    const size_t lds_s = dispatch::attn_small_lds_bytes(lk, DH, DT<T>::id);
+    auto ks = attention_core_small_kernel<T, OutT, DH>;
+    if (lds_s > 64 * 1024 && !xml_lds_attr_once<attention_core_small_kernel<T, OutT, DH>>(dispatch::LDS_BYTES))
+      return XML_ERR_LAUNCH;
+    const int64_t units = n * n_heads;
+    const dim3 grid((unsigned)((units + dispatch::ATTN_SMALL_UNITS - 1) / dispatch::ATTN_SMALL_UNITS));
+    hipLaunchKernelGGL(ks, grid, dim3(256), lds_s, st, (const T*)q, ldq, (const T*)k, ldk, (const T*)v, ldv, q_mask, k_mask,
+                       (OutT*)out, hidden, lq, lk, n_heads, units, sqrtf((float)DH), (const int32_t*)nullptr);
+    XML_CHECK_LAUNCH();
+    return XML_OK;
   }
+  const size_t lds = dispatch::attn_lds_bytes(lk, DH, DT<T>::id);
   auto kern = attention_core_kernel<T, OutT, DH>;
-  if (lds > 64 * 1024 && !xml_lds_attr_once<attention_core_kernel<T, OutT, DH>>(160 * 1024)) return XML_ERR_LAUNCH;
+  if (lds > 64 * 1024 && !xml_lds_attr_once<attention_core_kernel<T, OutT, DH>>(dispatch::LDS_BYTES)) return XML_ERR_LAUNCH;
   // (debug build: g_q2c_ablation selects a timing ablation inside the kernel; constant 0 in the product build)
   hipLaunchKernelGGL(kern, dim3(n_heads, (unsigned)n), dim3(256), lds, st, (const T*)q, ldq, (const T*)k, ldk,
                      (const T*)v, ldv, q_mask, k_mask, (OutT*)out, hidden, lq, lk, (float)g_q2c_ablation,
@@ -558,17 +540,13 @@ static int launch_attn(const void* q, int ldq, const void* k, int ldk, const voi
 template <typename T, typename OutT>
 static int dispatch_attn_dh(int dh, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,
                             const float* q_mask, const float* k_mask, void* out, int64_t n, int lq, int lk,
-                            int hidden, int n_heads, size_t lds, hipStream_t st) {
+                            int hidden, int n_heads, bool small, hipStream_t st) {
 #define XML_ATTN_CASE(D)                                                                                     \
   case D:                                                                                                    \
     return launch_attn<T, OutT, D>(q, ldq, k, ldk, v, ldv, q_mask, k_mask, out, n, lq, lk, hidden, n_heads, \
-                                   lds, st);
+                                   small, st);
   switch (dh) {
-    XML_ATTN_CASE(32)
-    XML_ATTN_CASE(64)
-    XML_ATTN_CASE(96)
-    XML_ATTN_CASE(128)
-    XML_ATTN_CASE(192)
+    XML_ATTN_HEAD_SIZES(XML_ATTN_CASE)
     default:
       return XML_ERR_UNSUPPORTED;
   }
@@ -579,20 +557,21 @@ int xmli_attention_core(const void* q, int ldq, const void* k, int ldk, const vo
                         const float* k_mask, void* out, int out_f32, int64_t n, int lq, int lk, int hidden,
                         int n_heads, int dt, hipStream_t st) {
   XML_ENTER();
-  if (n <= 0 || lq <= 0 || lk <= 0 || n_heads <= 0 || hidden % n_heads) return XML_ERR_BAD_ARG;
-  if (lq > 128 || lk > 128) return XML_ERR_UNSUPPORTED;
+  if (n <= 0 || lq <= 0 || lk <= 0) return XML_ERR_BAD_ARG;
+  const int form = dispatch::attn_kernel(lq, lk, hidden, n_heads, dt);
+  if (form == XML_ATTN_REFUSED_HEADS) return XML_ERR_BAD_ARG;
+  if (form == XML_ATTN_REFUSED_LENGTH || form == XML_ATTN_REFUSED_LDS) return XML_ERR_UNSUPPORTED;
   const int dh = hidden / n_heads;
-  const size_t lds = attn_lds_bytes(lk, dh, dt);
-  if (lds > 160 * 1024) return XML_ERR_UNSUPPORTED;
+  const bool small = form == XML_ATTN_SMALL;      // (XML_ATTN_REFUSED_DH: no case of the switch on dh)
   if (dt == XML_F32)
     return dispatch_attn_dh<float, float>(dh, q, ldq, k, ldk, v, ldv, q_mask, k_mask, out, n, lq, lk, hidden,
-                                          n_heads, lds, st);
+                                          n_heads, small, st);
   if (dt == XML_BF16) {
     if (out_f32)
       return dispatch_attn_dh<bf16_t, float>(dh, q, ldq, k, ldk, v, ldv, q_mask, k_mask, out, n, lq, lk, hidden,
-                                             n_heads, lds, st);
+                                             n_heads, small, st);
     return dispatch_attn_dh<bf16_t, bf16_t>(dh, q, ldq, k, ldk, v, ldv, q_mask, k_mask, out, n, lq, lk, hidden,
-                                            n_heads, lds, st);
+                                            n_heads, small, st);
   }
   return XML_ERR_BAD_ARG;
 }
@@ -615,7 +594,7 @@ extern "C" int xml_attention_core(const void* q, int ldq, const void* k, int ldk
 extern "C" size_t xml_attention_block_workspace_bytes(int64_t n, int seq_len, int hidden, int dt) {
   const size_t rows = (size_t)n * seq_len;
   const size_t pre = align_up(rows * hidden * 4, 256);      // f32 pre-LN rows, or the fused epilogue's per-workgroup scratch
-  const size_t lnw = xmli_gemm_ln_eligible((int64_t)rows, hidden, hidden, dt) ? xmli_gemm_ln_workspace_bytes((int64_t)rows, hidden) : 0;
+  const size_t lnw = dispatch::gemm_ln_fused((int64_t)rows, hidden, hidden, dt) ? xmli_gemm_ln_workspace_bytes((int64_t)rows, hidden) : 0;
   return align_up(rows * 3 * hidden * dt_size(dt), 256) + align_up(rows * hidden * dt_size(dt), 256) +
          (pre > lnw ? pre : lnw) + xmli_gemm_split_ws_bytes((int64_t)rows, hidden, dt);
 }
@@ -627,7 +606,7 @@ extern "C" int xml_attention_block(const void* x, const float* key_mask, const v
   XML_ENTER();
   if (!x || !key_mask || !wqkv || !bqkv || !wo || !bo || !ln_g || !ln_b || !y || !ws) return XML_ERR_BAD_ARG;
   if (n <= 0 || seq_len <= 0 || !xmli_model_dt_ok(dt)) return XML_ERR_BAD_ARG;
-  if (seq_len > 128 || hidden % 8) return XML_ERR_UNSUPPORTED;
+  if (seq_len > dispatch::ATTN_MAX_L || hidden % 8) return XML_ERR_UNSUPPORTED;
   if (ws_bytes < xml_attention_block_workspace_bytes(n, seq_len, hidden, dt)) return XML_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = n * seq_len;
@@ -643,7 +622,7 @@ extern "C" int xml_attention_block(const void* x, const float* key_mask, const v
   rc = xmli_attention_core(qkv, 3 * hidden, qkv + (size_t)hidden * es, 3 * hidden, qkv + (size_t)2 * hidden * es,
                            3 * hidden, nullptr, key_mask, att, 0, n, seq_len, seq_len, hidden, n_heads, adt, st);
   if (rc) return rc;
-  if (xmli_gemm_ln_eligible(rows, hidden, hidden, dt) && y != x &&   // BertSelfOutput: dense + residual + LayerNorm in one launch
+  if (dispatch::gemm_ln_fused(rows, hidden, hidden, dt) && y != x &&   // BertSelfOutput: dense + residual + LayerNorm in one launch
       xmli_gemm_ln(att, wo, bo, x, ln_g, ln_b, y, rows, hidden, hidden, 0, /*residual*/ 2, 1, dt, pre, st) == XML_OK)
     return XML_OK;
   rc = xmli_gemm(att, wo, bo, x, pre, rows, hidden, hidden, 0, /*residual*/ 2, 1, /*out_f32*/ 1, dt, st, sws);
@@ -661,12 +640,13 @@ extern "C" int xml_attention_block(const void* x, const float* key_mask, const v
 template <typename T, int DH>
 static int launch_attn_varlen(const char* qkv, int hidden, const int32_t* cu, void* att, int64_t n, int max_len,
                               int n_heads, int dt, hipStream_t st) {
-  const size_t lds_s = attn_small_lds_bytes(max_len, DH, dt);
-  if (lds_s > 160 * 1024) return XML_ERR_UNSUPPORTED;
-  if (lds_s > 64 * 1024 && !xml_lds_attr_once<attention_core_small_kernel<T, T, DH>>(160 * 1024)) return XML_ERR_LAUNCH;
+  const size_t lds_s = dispatch::attn_small_lds_bytes(max_len, DH, dt);
+  if (lds_s > (size_t)dispatch::LDS_BYTES) return XML_ERR_UNSUPPORTED;
+  if (lds_s > 64 * 1024 && !xml_lds_attr_once<attention_core_small_kernel<T, T, DH>>(dispatch::LDS_BYTES)) return XML_ERR_LAUNCH;
   const int64_t units = n * n_heads;
   const T* q = (const T*)qkv;
-  hipLaunchKernelGGL((attention_core_small_kernel<T, T, DH>), dim3((unsigned)((units + 3) / 4)), dim3(256), lds_s, st, q,
+  const dim3 grid((unsigned)((units + dispatch::ATTN_SMALL_UNITS - 1) / dispatch::ATTN_SMALL_UNITS));
+  hipLaunchKernelGGL((attention_core_small_kernel<T, T, DH>), grid, dim3(256), lds_s, st, q,
                      3 * hidden, q + hidden, 3 * hidden, q + 2 * hidden, 3 * hidden, (const float*)nullptr,
                      (const float*)nullptr, (T*)att, hidden, max_len, max_len, n_heads, units, sqrtf((float)DH), cu);
   XML_CHECK_LAUNCH();
@@ -675,7 +655,7 @@ static int launch_attn_varlen(const char* qkv, int hidden, const int32_t* cu, vo
 
 extern "C" size_t xml_attention_block_varlen_workspace_bytes(int64_t rows, int hidden, int dt) {
   const size_t pre = align_up((size_t)rows * hidden * 4, 256);
-  const size_t lnw = xmli_gemm_ln_eligible(rows, hidden, hidden, dt) ? xmli_gemm_ln_workspace_bytes(rows, hidden) : 0;
+  const size_t lnw = dispatch::gemm_ln_fused(rows, hidden, hidden, dt) ? xmli_gemm_ln_workspace_bytes(rows, hidden) : 0;
   return align_up((size_t)rows * 3 * hidden * dt_size(dt), 256) + align_up((size_t)rows * hidden * dt_size(dt), 256) +
          (pre > lnw ? pre : lnw) + xmli_gemm_split_ws_bytes(rows, hidden, dt);
 }
@@ -687,7 +667,7 @@ extern "C" int xml_attention_block_varlen(const void* x, const int32_t* cu_seqle
   XML_ENTER();
   if (!x || !cu_seqlens || !wqkv || !bqkv || !wo || !bo || !ln_g || !ln_b || !y || !ws) return XML_ERR_BAD_ARG;
   if (rows <= 0 || n <= 0 || max_len <= 0 || n_heads <= 0 || !xmli_model_dt_ok(dt)) return XML_ERR_BAD_ARG;
-  if (max_len > 32 || hidden % 8 || hidden % n_heads) return XML_ERR_UNSUPPORTED;
+  if (max_len > dispatch::ATTN_SMALL_MAX_L || hidden % 8 || hidden % n_heads) return XML_ERR_UNSUPPORTED;
   if (ws_bytes < xml_attention_block_varlen_workspace_bytes(rows, hidden, dt)) return XML_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int adt = xmli_act_dt(dt);
@@ -706,16 +686,12 @@ extern "C" int xml_attention_block_varlen(const void* x, const int32_t* cu_seqle
                         : launch_attn_varlen<bf16_t, D>(qkv, hidden, cu_seqlens, att, n, max_len, n_heads, adt, st);  \
     break;
   switch (dh) {
-    XML_VL_CASE(32)
-    XML_VL_CASE(64)
-    XML_VL_CASE(96)
-    XML_VL_CASE(128)
-    XML_VL_CASE(192)
+    XML_ATTN_HEAD_SIZES(XML_VL_CASE)
     default: break;
   }
 #undef XML_VL_CASE
   if (rc) return rc;
-  if (xmli_gemm_ln_eligible(rows, hidden, hidden, dt) && y != x &&
+  if (dispatch::gemm_ln_fused(rows, hidden, hidden, dt) && y != x &&
       xmli_gemm_ln(att, wo, bo, x, ln_g, ln_b, y, rows, hidden, hidden, 0, /*residual*/ 2, 1, dt, pre, st) == XML_OK)
     return XML_OK;
   rc = xmli_gemm(att, wo, bo, x, pre, rows, hidden, hidden, 0, /*residual*/ 2, 1, /*out_f32*/ 1, dt, st, sws);
@@ -741,7 +717,7 @@ extern "C" int xml_cross_attention(const void* main_x, const float* main_mask, c
   if (!main_x || !main_mask || !side_x || !side_mask || !wq || !bq || !wkv || !bkv || !ln_g || !ln_b || !y || !ws)
     return XML_ERR_BAD_ARG;
   if (n <= 0 || lq <= 0 || lk <= 0 || !xmli_model_dt_ok(dt)) return XML_ERR_BAD_ARG;
-  if (lq > 128 || lk > 128 || hidden % 8) return XML_ERR_UNSUPPORTED;
+  if (lq > dispatch::ATTN_MAX_L || lk > dispatch::ATTN_MAX_L || hidden % 8) return XML_ERR_UNSUPPORTED;
   if (ws_bytes < xml_cross_attention_workspace_bytes(n, lq, lk, hidden, dt)) return XML_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const size_t es = dt_size(dt);

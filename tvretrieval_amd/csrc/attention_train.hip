@@ -439,11 +439,11 @@ template <int DH>
 int at_launch(bool bwd, const AttnTrainArgs& a, int64_t n, int n_heads, hipStream_t st) {
   if (bwd) {
     const size_t lds = at_bwd_lds<DH>();
-    if (lds > 160 * 1024 || !xml_lds_attr_once<attn_train_bwd_kernel<DH>>(160 * 1024)) return XML_ERR_LAUNCH;
+    if (lds > (size_t)dispatch::LDS_BYTES || !xml_lds_attr_once<attn_train_bwd_kernel<DH>>(dispatch::LDS_BYTES)) return XML_ERR_LAUNCH;
     hipLaunchKernelGGL(attn_train_bwd_kernel<DH>, dim3(n_heads, (unsigned)n), dim3(256), lds, st, a);
   } else {
     const size_t lds = at_fwd_lds<DH>();
-    if (lds > 160 * 1024 || !xml_lds_attr_once<attn_train_fwd_kernel<DH>>(160 * 1024)) return XML_ERR_LAUNCH;
+    if (lds > (size_t)dispatch::LDS_BYTES || !xml_lds_attr_once<attn_train_fwd_kernel<DH>>(dispatch::LDS_BYTES)) return XML_ERR_LAUNCH;
     hipLaunchKernelGGL(attn_train_fwd_kernel<DH>, dim3(n_heads, (unsigned)n), dim3(256), lds, st, a);
   }
   XML_CHECK_LAUNCH();
@@ -454,7 +454,7 @@ int at_dispatch(bool bwd, AttnTrainArgs& a, int64_t n, int hidden, int n_heads, 
                 const uint64_t* seed_dev, hipStream_t st) {
   if (n <= 0 || a.lq <= 0 || a.lk <= 0 || n_heads <= 0 || hidden % n_heads || !(p_drop >= 0.f) || p_drop >= 1.f)
     return XML_ERR_BAD_ARG;
-  if (a.lq > 128 || a.lk > 128) return XML_ERR_UNSUPPORTED;
+  if (a.lq > dispatch::ATTN_MAX_L || a.lk > dispatch::ATTN_MAX_L) return XML_ERR_UNSUPPORTED;
   const int dh = hidden / n_heads;
   a.lq8 = (a.lq + 7) / 8 * 8; a.lk8 = (a.lk + 7) / 8 * 8;
   a.sqrt_dh = sqrtf((float)dh);
@@ -462,11 +462,9 @@ int at_dispatch(bool bwd, AttnTrainArgs& a, int64_t n, int hidden, int n_heads, 
   a.scale = 1.f / (1.f - p_drop);
   a.seed = seed; a.seed_dev = seed_dev;
   switch (dh) {
-    case 32: return at_launch<32>(bwd, a, n, n_heads, st);
-    case 64: return at_launch<64>(bwd, a, n, n_heads, st);
-    case 96: return at_launch<96>(bwd, a, n, n_heads, st);
-    case 128: return at_launch<128>(bwd, a, n, n_heads, st);
-    case 192: return at_launch<192>(bwd, a, n, n_heads, st);
+#define XML_AT_CASE(D) case D: return at_launch<D>(bwd, a, n, n_heads, st);
+    XML_ATTN_HEAD_SIZES(XML_AT_CASE)
+#undef XML_AT_CASE
     default: return XML_ERR_UNSUPPORTED;
   }
 }
@@ -474,9 +472,7 @@ int at_dispatch(bool bwd, AttnTrainArgs& a, int64_t n, int hidden, int n_heads, 
 }  // namespace
 
 extern "C" int xml_attention_train_supported(int lq, int lk, int hidden, int n_heads, int dt) {
-  if (dt != XML_BF16 || n_heads <= 0 || hidden % n_heads || lq <= 0 || lk <= 0 || lq > 128 || lk > 128) return 0;
-  const int dh = hidden / n_heads;
-  return dh == 32 || dh == 64 || dh == 96 || dh == 128 || dh == 192;
+  return dispatch::attn_train_ok(lq, lk, hidden, n_heads, dt);
 }
 
 extern "C" int xml_attention_train_fwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv,

@@ -23,7 +23,8 @@ build() {   # $1 = object dir, $2 = extra flags, $3 = output, $4.. = sources
     local o=$dir/${b%.hip}.o
     objs+=("$o")
     if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ gemm.h -nt "$o" ] || [ internal.h -nt "$o" ] \
-       || [ debug.h -nt "$o" ] || [ l2norm.h -nt "$o" ] || [ ../../include/xmlhip.h -nt "$o" ]; then
+       || [ debug.h -nt "$o" ] || [ l2norm.h -nt "$o" ] || [ dispatch.h -nt "$o" ] || [ ring256.h -nt "$o" ] \
+       || [ ../../include/xmlhip.h -nt "$o" ]; then
       $HIPCC $FLAGS $extra -I. -c "$s" -o "$o" &
       pids+=($!)
     fi

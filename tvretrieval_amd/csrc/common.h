@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/xmlhip.h"
 #include "debug.h"
+#include "dispatch.h"
 
 // hipGetLastError() also reports stale, non-sticky errors left by OTHER runtime users in this thread (e.g. the
 // caching allocator's hipErrorNotReady event polls), so every entry point clears the slot before launching.
@@ -276,6 +277,6 @@ static inline XmlDropSite xml_drop_site(float p, uint64_t seed) {
   return s;
 }
 
-static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+using dispatch::cdiv;
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-static inline size_t dt_size(int dt) { return (dt == XML_F32 || dt == XML_F16S) ? 4 : 2; }
+using dispatch::dt_size;

@@ -20,7 +20,7 @@ template <typename T, int BM_, int BN_, int WM_, int WN_>
 struct GemmCfg {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
   static constexpr int NTHREADS = WM * WN * 64;
-  static constexpr int ROWB = 128;                       // bytes of K per row per step
+  static constexpr int ROWB = dispatch::GEMM_SMALL_STEP_BYTES;      // bytes of K per row per step
   static constexpr int KSTEP = ROWB / (int)sizeof(T);    // elements of K per step
   static constexpr int MT = BM / WM / 16;                // 16x16 tiles per wave along M
   static constexpr int NT = BN / WN / 16;                // ... along N

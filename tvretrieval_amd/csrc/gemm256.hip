@@ -4,17 +4,9 @@
 // M >= 256; the 128 x 128 register-staged kernel (linear.hip) covers every other shape.
 #include <type_traits>
 
-#include "common.h"
 #include "internal.h"
+#include "ring256.h"
 
-__device__ __forceinline__ void g256_dma(uint32_t voff, const char* sbase, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
 // the four pieces of a slice in one statement, M0 advanced by immediates (see q2c_persist.hip: every scalar
 // instruction and branch in the per-slice path of a wave is issue time its partner wave's MFMAs do not fully cover)
 __device__ __forceinline__ void g256_dma4(uint32_t va0, uint32_t va1, uint32_t vb0, uint32_t vb1, const char* sa,
@@ -28,40 +20,6 @@ __device__ __forceinline__ void g256_dma4(uint32_t va0, uint32_t va1, uint32_t v
       : "v"(va0), "v"(va1), "v"(vb0), "v"(vb1), "s"(lds_dst), "s"(sa), "s"(sb)
       : "memory", "scc");
 }
-template <typename T> struct G256Init;      // first K chunk of the tile: C = 0 as an inline constant
-template <> struct G256Init<float> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-  }
-};
-template <> struct G256Init<bf16_t> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    union { uint4 u; bf16x8_v v; } ua, ub;
-    ua.u = a; ub.u = b;
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua.v, ub.v, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  }
-};
-template <> struct G256Init<f16_t> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    union { uint4 u; f16x8_v v; } ua, ub;
-    ua.u = a; ub.u = b;
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ua.v, ub.v, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  }
-};
-template <int CTRL>
-__device__ __forceinline__ uint4 g256_dpp_u4(const uint4& v) {
-  uint4 r;
-  r.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.x, CTRL, 0xf, 0xf, false);
-  r.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.y, CTRL, 0xf, 0xf, false);
-  r.z = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.z, CTRL, 0xf, 0xf, false);
-  r.w = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.w, CTRL, 0xf, 0xf, false);
-  return r;
-}
-__device__ __forceinline__ int g256_swz(int row) { return (0x78 >> (((row >> 2) & 3) << 1)) & 3; }
-
 // RAGGED_N: N % 8 != 0 -> per-element tail stores (kept out of the common instantiation: its 64-bit modulo and
 // per-element branches, unrolled 16 times, made the kernel 640 KB of code and the epilogue instruction-fetch bound)
 template <typename T, typename OutT, typename AddT, bool RAGGED_N = false>
@@ -73,9 +31,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   // T == f16_t: the split-f16 projection (split16.hip): A / W are the K-concatenated halves, K = 3 x the logical K, and
   // every accumulator row is multiplied by row_scale[m] = 1 / (S_row S_weights) before bias / activation
   constexpr bool SCALED = std::is_same<T, f16_t>::value;
-  constexpr int ROWB = 64;
-  constexpr int OPER_BYTES = 256 * ROWB;
-  constexpr int SLOT_BYTES = 2 * OPER_BYTES;
+  using namespace ring256;
+  constexpr int NSLOT = dispatch::RING_SLOTS;
+  static_assert((NSLOT & (NSLOT - 1)) == 0, "slots are addressed by masking the slice number");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   // XCD-aware tile order: 8 (M tiles) x 4 (N tiles) super-tiles per XCD
@@ -103,7 +61,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = (wave * 2 + i) * 16 + rsub;
-      const int slot = pslot ^ g256_swz(row);
+      const int slot = pslot ^ ring_swz(row);
       voff_a[i] = (uint32_t)((m0 + row < M) ? row : 0) * k_bytes + slot * 16;
       voff_b[i] = (uint32_t)((n0 + row < N) ? row : 0) * k_bytes + slot * 16;
     }
@@ -114,12 +72,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   int i_slice = 0;
   auto issue_slice = [&]() {        // callers guarantee i_slice < n_slices
     const int koff = i_slice * ROWB;
-    const uint32_t dst = lds_wave + (i_slice & 3) * SLOT_BYTES;
+    const uint32_t dst = lds_wave + (i_slice & (NSLOT - 1)) * SLOT_BYTES;
     g256_dma4(voff_a[0], voff_a[1], voff_b[0], voff_b[1], sbase_a + koff, sbase_b + koff, dst);
     ++i_slice;
   };
 
-  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ g256_swz(fr)) << 4);
+  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ ring_swz(fr)) << 4);
   // DIRECT epilogue (N % 8 == 0; see gemm256p.hip): swapped MFMA operands -> a lane's accumulator holds 4 consecutive
   // columns of ONE row; 2-byte outputs pair the accumulators (W row of fragment n, MFMA row index i:
   // (n >> 1) * 32 + (i >> 2) * 8 + (n & 1) * 4 + (i & 3)) so that a lane owns 8 consecutive columns.  Same products and
@@ -127,8 +85,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   constexpr bool DIRECT = !RAGGED_N;
   constexpr bool PAIRED = DIRECT && sizeof(OutT) == 2;
   const int rb_e = PAIRED ? (fr >> 2) * 8 + (fr & 3) : fr;
-  const int b_off = OPER_BYTES + (wn * 128 + rb_e) * ROWB + ((fg ^ g256_swz(rb_e)) << 4);
-  const int b_off_o = OPER_BYTES + (wn * 128 + rb_e + 4) * ROWB + ((fg ^ g256_swz(rb_e + 4)) << 4);   // PAIRED, odd n
+  const int b_off = OPER_BYTES + (wn * 128 + rb_e) * ROWB + ((fg ^ ring_swz(rb_e)) << 4);
+  const int b_off_o = OPER_BYTES + (wn * 128 + rb_e + 4) * ROWB + ((fg ^ ring_swz(rb_e + 4)) << 4);   // PAIRED, odd n
   auto b_frag = [&](const char* slot, int n) -> uint4 {
     if constexpr (PAIRED) return *reinterpret_cast<const uint4*>(slot + ((n & 1) ? b_off_o : b_off) + (n >> 1) * 32 * ROWB);
     else return *reinterpret_cast<const uint4*>(slot + b_off + n * 16 * ROWB);
@@ -138,7 +96,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  f32x4 acc[4][8];                  // written by the first slice (G256Init: C = 0)
+  f32x4 acc[4][8];                  // written by the first slice (RingInit: C = 0)
   uint4 faA[4], faB[4], fbL[4], fbH[4];
 #pragma unroll
   for (int m = 0; m < 4; ++m) faA[m] = *reinterpret_cast<const uint4*>(smem + a_off + m * 16 * ROWB);
@@ -156,7 +114,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
     auto slice_step = [&](uint4 (&fc)[4], uint4 (&fn)[4], auto mode_tag, auto init_tag) {
       constexpr int MODE = decltype(mode_tag)::value;
       constexpr bool INIT = decltype(init_tag)::value;
-      const char* slot = smem + (c_slice & 3) * SLOT_BYTES;
+      const char* slot = smem + (c_slice & (NSLOT - 1)) * SLOT_BYTES;
 #pragma unroll
       for (int n = 0; n < 4; ++n) fbH[n] = b_frag(slot, n + 4);
 #pragma unroll
@@ -164,10 +122,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
           if constexpr (DIRECT) {
-            if constexpr (INIT) G256Init<T>::chunk(acc[m][n], fbL[n], fc[m]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n], fbL[n], fc[m]);
             else Mma<T>::chunk(acc[m][n], fbL[n], fc[m]);
           } else {
-            if constexpr (INIT) G256Init<T>::chunk(acc[m][n], fc[m], fbL[n]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n], fc[m], fbL[n]);
             else Mma<T>::chunk(acc[m][n], fc[m], fbL[n]);
           }
         }
@@ -178,7 +136,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
       ++c_slice;
       auto preamble = [&]() {
         if constexpr (MODE <= 3) {
-          const char* nslot = smem + (c_slice & 3) * SLOT_BYTES;
+          const char* nslot = smem + (c_slice & (NSLOT - 1)) * SLOT_BYTES;
 #pragma unroll
           for (int m = 0; m < 4; ++m) fn[m] = *reinterpret_cast<const uint4*>(nslot + a_off + m * 16 * ROWB);
 #pragma unroll
@@ -193,10 +151,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
           if constexpr (DIRECT) {
-            if constexpr (INIT) G256Init<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
             else Mma<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
           } else {
-            if constexpr (INIT) G256Init<T>::chunk(acc[m][n + 4], fc[m], fbH[n]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n + 4], fc[m], fbH[n]);
             else Mma<T>::chunk(acc[m][n + 4], fc[m], fbH[n]);
           }
         }
@@ -302,8 +260,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
 #pragma unroll
       for (int pq = 0; pq < NGRP / 2; ++pq) {
         const uint4 own_e = pk[2 * pq], own_o = pk[2 * pq + 1];
-        const uint4 dn = g256_dpp_u4<0x111>(own_o);
-        const uint4 up = g256_dpp_u4<0x101>(own_e);
+        const uint4 dn = ring_dpp_u4<0x111>(own_o);
+        const uint4 up = ring_dpp_u4<0x101>(own_e);
         const uint4 d_even = make_uint4(odd ? dn.x : own_e.x, odd ? dn.y : own_e.y, odd ? dn.z : own_e.z, odd ? dn.w : own_e.w);
         const uint4 d_odd = make_uint4(odd ? own_o.x : up.x, odd ? own_o.y : up.y, odd ? own_o.z : up.z, odd ? own_o.w : up.w);
         if (pcol[pq] + GC <= N) {
@@ -428,15 +386,8 @@ static int launch_gemm256(const void* A, const void* W, const float* bias, const
   return XML_OK;
 }
 
-bool xmli_gemm256_eligible(int64_t M, int N, int K, int dt) {
-  const size_t kb = (size_t)K * dt_size(dt);
-  return M >= 256 && N >= 128 && kb % 128 == 0 && kb >= 256;
-}
-
+// (shapes: dispatch::gemm256_ok / gemm256_f16s_ok)
 // split-f16 projection: A' (M, K3) / W' (N, K3) f16, K3 = 3 x the logical K; out / addend f32
-bool xmli_gemm256_f16s_eligible(int64_t M, int N, int K3) {
-  return M >= 256 && N >= 128 && N % 8 == 0 && (K3 * 2) % 128 == 0 && K3 * 2 >= 256;
-}
 int xmli_gemm256_f16s(const void* A, const void* W, const float* bias, const void* addend, void* out,
                       const float* row_scale, int64_t M, int N, int K3, int relu, int add_mode, int seq_len,
                       hipStream_t st) {

@@ -26,8 +26,8 @@
 // Same MFMA sequence per accumulator as gemm256_kernel: bitwise the same results.
 #include <type_traits>
 
-#include "common.h"
 #include "internal.h"
+#include "ring256.h"
 
 struct G256pArgs {
   const void* A;
@@ -45,41 +45,6 @@ struct G256pArgs {
   int probe;            // debug build only: phase probe on
 };
 
-__device__ __forceinline__ void g256p_dma_pair(uint32_t v0, uint32_t v1, const char* sb, uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3"
-      :
-      : "v"(v0), "v"(v1), "s"(lds_dst), "s"(sb)
-      : "memory", "scc");
-}
-__device__ __forceinline__ void g256p_dma_quad(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, const char* sb,
-                                               uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5"
-      :
-      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(lds_dst), "s"(sb)
-      : "memory", "scc");
-}
-template <typename T> struct G256pInit;      // first K chunk of a tile: C = 0 as an inline constant
-template <> struct G256pInit<float> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-  }
-};
-template <> struct G256pInit<bf16_t> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    union { uint4 u; bf16x8_v v; } ua, ub;
-    ua.u = a; ub.u = b;
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua.v, ub.v, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  }
-};
 #ifdef XML_DEBUG_VARIANTS
 // phase probe (debug build, XML_ABL = 9): s_memtime ticks of workgroup 0, summed over its tiles, per wave:
 //   [0] K loop  [1] epilogue until the bias is in LDS (includes the vmcnt(0) drain)  [2] row blocks + stores
@@ -96,24 +61,6 @@ extern "C" int xml_debug_read_gemm_probe(unsigned long long* host_out) {
 #else
 #define G256P_T() 0ull
 #endif
-template <int CTRL>
-__device__ __forceinline__ uint4 dpp_u4(const uint4& v) {
-  uint4 r;
-  r.x = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.x, CTRL, 0xf, 0xf, false);
-  r.y = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.y, CTRL, 0xf, 0xf, false);
-  r.z = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.z, CTRL, 0xf, 0xf, false);
-  r.w = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.w, CTRL, 0xf, 0xf, false);
-  return r;
-}
-// lane id from the hardware, as a VOLATILE asm: neither hoisted out of the tile loop nor kept live across the K loop
-// (see lane_id_now in q2c_persist.hip: a spilled lane id returns through a scratch load and its s_waitcnt vmcnt(0))
-__device__ __forceinline__ int g256p_lane_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-__device__ __forceinline__ int g256p_swz(int row) { return (0x78 >> (((row >> 2) & 3) << 1)) & 3; }
-
 // LNE: LayerNorm fused into the epilogue (K2 behind K1, BertSelfOutput; xml/model_components.py:76-89,313-317).  A row of
 // the output spans tn = N / 256 column tiles (tn <= 3).  ONE workgroup computes all tn tiles of a row block, back to back:
 //   tiles 0 .. tn - 2: the pre-LayerNorm values (f32) go to the workgroup's private scratch, lane for lane as they sit in
@@ -136,10 +83,8 @@ __device__ __forceinline__ int g256p_swz(int row) { return (0x78 >> (((row >> 2)
 template <typename T, typename OutT, typename AddT, bool LNE = false, bool DIRECT = true>
 __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
   static_assert(!LNE || DIRECT, "the LayerNorm epilogue works on the DIRECT accumulator layout");
-  constexpr int ROWB = 64;
-  constexpr int OPER_BYTES = 256 * ROWB;
-  constexpr int SLOT_BYTES = 2 * OPER_BYTES;
-  constexpr int NSLOT = 4;
+  using namespace ring256;
+  constexpr int NSLOT = dispatch::RING_SLOTS;
   constexpr int RING_BYTES = NSLOT * SLOT_BYTES;      // 128 KiB; the eight 4 KiB epilogue patches follow
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -201,15 +146,15 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
     tile_mt_nt(i_k, mt, nt);
     const int64_t m0 = mt * 256;
     const int n0 = nt * 256;
-    const int lane_o = g256p_lane_now();           // re-derived here: nothing lane-dependent stays live across the MFMA loop
+    const int lane_o = ring_lane_now();           // re-derived here: nothing lane-dependent stays live across the MFMA loop
     const int rsub = lane_o >> 2, pslot = lane_o & 3;
     auto off_a = [&](int piece) -> uint32_t {
       const int row = piece * 16 + rsub;
-      return (uint32_t)((m0 + row < M) ? row : 0) * k_bytes + (pslot ^ g256p_swz(row)) * 16;
+      return (uint32_t)((m0 + row < M) ? row : 0) * k_bytes + (pslot ^ ring_swz(row)) * 16;
     };
     auto off_b = [&](int piece) -> uint32_t {
       const int row = piece * 16 + rsub;
-      return (uint32_t)((n0 + row < N) ? row : 0) * k_bytes + (pslot ^ g256p_swz(row)) * 16;
+      return (uint32_t)((n0 + row < N) ? row : 0) * k_bytes + (pslot ^ ring_swz(row)) * 16;
     };
     if (grp == 0) {     // uneven duty (see q2c_persist.hip): the group that parks at the barrier issues 6 of 8 pieces
       va[0] = off_a(wave * 4); va[1] = off_a(wave * 4 + 1); va[2] = off_a(wave * 4 + 2); va[3] = off_a(wave * 4 + 3);
@@ -224,10 +169,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
     const int koff = i_slice * ROWB;
     const uint32_t slot0 = lds0 + i_slot * SLOT_BYTES;
     if (grp == 0) {
-      g256p_dma_quad(va[0], va[1], va[2], va[3], sbase_a + koff, slot0 + wave * 4096);
-      g256p_dma_pair(vb[0], vb[1], sbase_b + koff, slot0 + OPER_BYTES + wave * 2048);
+      ring_dma_quad(va[0], va[1], va[2], va[3], sbase_a + koff, slot0 + wave * 4096);
+      ring_dma_pair(vb[0], vb[1], sbase_b + koff, slot0 + OPER_BYTES + wave * 2048);
     } else {
-      g256p_dma_pair(vb[0], vb[1], sbase_b + koff, slot0 + OPER_BYTES + 8192 + (wave - 4) * 2048);
+      ring_dma_pair(vb[0], vb[1], sbase_b + koff, slot0 + OPER_BYTES + 8192 + (wave - 4) * 2048);
     }
     if (++i_slot == NSLOT) i_slot = 0;
     i_slice += i_inc;
@@ -243,7 +188,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
   setup_issue_tile();
 
   // ---- compute side ---------------------------------------------------------------------------------------------
-  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ g256p_swz(fr)) << 4);
+  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ ring_swz(fr)) << 4);
   // B (= W) fragment n, MFMA row index i = fr  ->  row of the wave's 128 W rows:
   //   staged epilogue / f32 out:  n * 16 + i                                   (a lane's 4 columns: n * 16 + 4 fg + r)
   //   DIRECT, 2-byte out (PAIRED): (n >> 1) * 32 + (i >> 2) * 8 + (n & 1) * 4 + (i & 3)
@@ -251,8 +196,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
   // Either way the 16 lanes of a ds_read_b128 group hit 16 distinct (row mod 4, swizzled slot) pairs: no bank conflicts.
   constexpr bool PAIRED = DIRECT && sizeof(OutT) == 2;
   const int rb_e = PAIRED ? (fr >> 2) * 8 + (fr & 3) : fr;
-  const int b_off = OPER_BYTES + (wn * 128 + rb_e) * ROWB + ((fg ^ g256p_swz(rb_e)) << 4);
-  const int b_off_o = OPER_BYTES + (wn * 128 + rb_e + 4) * ROWB + ((fg ^ g256p_swz(rb_e + 4)) << 4);   // PAIRED, odd n
+  const int b_off = OPER_BYTES + (wn * 128 + rb_e) * ROWB + ((fg ^ ring_swz(rb_e)) << 4);
+  const int b_off_o = OPER_BYTES + (wn * 128 + rb_e + 4) * ROWB + ((fg ^ ring_swz(rb_e + 4)) << 4);   // PAIRED, odd n
   auto b_frag = [&](const char* slot, int n) -> uint4 {
     if constexpr (PAIRED) return *reinterpret_cast<const uint4*>(slot + ((n & 1) ? b_off_o : b_off) + (n >> 1) * 32 * ROWB);
     else return *reinterpret_cast<const uint4*>(slot + b_off + n * 16 * ROWB);
@@ -301,10 +246,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
           if constexpr (DIRECT) {
-            if constexpr (INIT) G256pInit<T>::chunk(acc[m][n], fbL[n], fc[m]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n], fbL[n], fc[m]);
             else Mma<T>::chunk(acc[m][n], fbL[n], fc[m]);
           } else {
-            if constexpr (INIT) G256pInit<T>::chunk(acc[m][n], fc[m], fbL[n]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n], fc[m], fbL[n]);
             else Mma<T>::chunk(acc[m][n], fc[m], fbL[n]);
           }
         }
@@ -326,10 +271,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
           if constexpr (DIRECT) {
-            if constexpr (INIT) G256pInit<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
             else Mma<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
           } else {
-            if constexpr (INIT) G256pInit<T>::chunk(acc[m][n + 4], fc[m], fbH[n]);
+            if constexpr (INIT) RingInit<T>::chunk(acc[m][n + 4], fc[m], fbH[n]);
             else Mma<T>::chunk(acc[m][n + 4], fc[m], fbH[n]);
           }
         }
@@ -357,7 +302,7 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
       const int64_t m0 = mt * 256;
       const int n0 = nt * 256;
       const uint32_t m0_mod = a.add_mode == 1 ? (uint32_t)(m0 % a.seq_len) : 0u;     // one 64-bit modulo per tile
-      const int lane_e = g256p_lane_now();
+      const int lane_e = ring_lane_now();
       const int fr_e = lane_e & 15, fg_e = lane_e >> 4;
       const int tid_e = wave * 64 + lane_e;
       float* patch = reinterpret_cast<float*>(smem + RING_BYTES) + wave * 1024;
@@ -395,8 +340,8 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(G256pArgs a) {
         const int64_t m_even = m0 + wm * 64 + m4 * 16 + (fr_e & ~1);
 #pragma unroll
         for (int pq = 0; pq < NGRP / 2; ++pq) {
-          const uint4 dn = dpp_u4<0x111>(pk[2 * pq + 1]);       // row_shr:1: lane i <- lane i - 1
-          const uint4 up = dpp_u4<0x101>(pk[2 * pq]);           // row_shl:1: lane i <- lane i + 1
+          const uint4 dn = ring_dpp_u4<0x111>(pk[2 * pq + 1]);       // row_shr:1: lane i <- lane i - 1
+          const uint4 up = ring_dpp_u4<0x101>(pk[2 * pq]);           // row_shl:1: lane i <- lane i + 1
           // (component-wise selects: `odd ? a : b` on the struct type becomes a select of stack ADDRESSES + a scratch load)
           const uint4 own_e = pk[2 * pq], own_o = pk[2 * pq + 1];
           const uint4 d_even = make_uint4(odd ? dn.x : own_e.x, odd ? dn.y : own_e.y, odd ? dn.z : own_e.z, odd ? dn.w : own_e.w);
@@ -726,7 +671,7 @@ static int launch_gemm256p(const void* A, const void* W, const float* bias, cons
   a.n_tiles = (int64_t)cdiv(M, 256) * a.tn;
   a.ln_scratch = (float*)ln_ws; a.ln_g = ln_g; a.ln_b = ln_b; a.ln_eps = 1e-5f;
   a.probe = g_q2c_ablation == 9 ? 1 : g_q2c_ablation == 21 ? 2 : g_q2c_ablation == 22 ? 4 : g_q2c_ablation == 23 ? 6 : g_q2c_ablation == 24 ? 8 : 0;
-  const int lds = 4 * 2 * 256 * 64 + 8 * 4096;          // ring + patches = 160 KiB
+  const int lds = dispatch::RING_SLOTS * ring256::SLOT_BYTES + 8 * 4096;          // ring + patches = 160 KiB
 #ifdef XML_DEBUG_VARIANTS
   if (!LNE && DIRECT && g_gemm_variant == 3)      // A/B: the LDS-staged epilogue
     return launch_gemm256p<T, OutT, AddT, false, false>(A, W, bias, addend, out, M, N, K, relu, add_mode, seq_len, st);
@@ -740,20 +685,13 @@ static int launch_gemm256p(const void* A, const void* W, const float* bias, cons
 
 // ---- GEMM with the LayerNorm in its epilogue --------------------------------------------------------------------
 // Taken for a SHAPE CLASS: rows that span 1-3 whole 256-column tiles (N = 256 / 512 / 768), K a whole number of 128-byte
-// steps, and at least LN_FUSED_MIN_ROWS rows.  Below the row threshold (a 50-query batch's 1 500 tokens, the 10-video tail
+// steps, and at least GEMM_LN_MIN_ROWS rows (dispatch::gemm_ln_fused).  Below the row threshold (a 50-query batch's 1 500 tokens, the 10-video tail
 // of a corpus) the callers run GEMM (f32 out) + xmli_gemm_ln_tail: small tiles fill the chip there, six row blocks would
 // not.  That LayerNorm has this epilogue's statistics, operation for operation, and the GEMM forms are bitwise alike, so a
 // row's bits do not depend on which side of the threshold its launch falls: the encoder's bits are the same for context
 // batches of 2 048, 200, 37 or 2 090 + 10 videos, and a 50-query batch gives its rows of a whole pass
 // (tests/test_gpu_row_invariance.py, tests/test_gpu_model.py::test_index_bits_do_not_depend_on_the_context_batch).
 // The fused kernel waits for nothing outside its workgroup, so it has no residency requirement and no failure path.
-static constexpr int64_t LN_FUSED_MIN_ROWS = 2048;
-
-bool xmli_gemm_ln_eligible(int64_t M, int N, int K, int dt) {
-  if (dt != XML_F32 && dt != XML_BF16) return false;      // (split-f16 projections take the three-launch path)
-  const size_t kb = (size_t)K * dt_size(dt);
-  return kb % 128 == 0 && kb >= 256 && N % 256 == 0 && N / 256 <= 3 && M >= LN_FUSED_MIN_ROWS;
-}
 // scratch of the fused kernel: per workgroup the f32 values of a row block's first tn - 1 tiles
 size_t xmli_gemm_ln_workspace_bytes(int64_t M, int N) {
   (void)M;
@@ -771,7 +709,7 @@ int xmli_gemm_ln(const void* A, const void* W, const float* bias, const void* ad
 }
 
 // ---- the LayerNorm of the three-launch path (GEMM with f32 out + LayerNorm), in the LNE epilogue's arithmetic -------------
-// Below LN_FUSED_MIN_ROWS (or when the fused launch is refused) the callers write the pre-LayerNorm rows in f32 and normalise
+// Below GEMM_LN_MIN_ROWS (or when the fused launch is refused) the callers write the pre-LayerNorm rows in f32 and normalise
 // them here.  For the shape class of the LNE kernel (N = 256 / 512 / 768, f32 / bf16) the row statistics are those of the
 // epilogue above, operation for operation, so that a row's output bits do not depend on which side of the row threshold its
 // launch falls:
@@ -886,12 +824,6 @@ int xmli_gemm_ln_tail(const float* pre, const float* ln_g, const float* ln_b, vo
 #undef XML_LNT
   XML_CHECK_LAUNCH();
   return XML_OK;
-}
-
-// worth it when every workgroup gets several tiles; below that the one-tile-per-workgroup kernel is as good
-bool xmli_gemm256p_eligible(int64_t M, int N, int K, int dt) {
-  const size_t kb = (size_t)K * dt_size(dt);
-  return kb % 128 == 0 && kb >= 256 && N >= 128 && N % 8 == 0 && (int64_t)cdiv(M, 256) * cdiv(N, 256) >= 3072;   // (2304 tiles: 2 % behind the one-tile kernel, 3516: 7 % ahead)
 }
 
 int xmli_gemm256p(const void* A, const void* W, const float* bias, const void* addend, void* out, int64_t M, int N,

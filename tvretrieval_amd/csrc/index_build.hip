@@ -33,9 +33,7 @@ __global__ __launch_bounds__(256) void tile_rows_l2norm_kernel(const T* __restri
 }  // namespace
 
 extern "C" int xml_q2c_tile_rows_l2norm_ok(int hidden, int dt) {
-  if (dt != XML_F32 && dt != XML_BF16) return 0;
-  const int vec = dt == XML_F32 ? 4 : 8;
-  return hidden > 0 && hidden % (4 * vec) == 0 && hidden / vec <= 32 * L2N_MAXJ;      // whole 64-byte slices
+  return dispatch::tile_rows_l2norm_ok(hidden, dt);
 }
 
 extern "C" int xml_q2c_tile_rows_l2norm(const void* src, const int32_t* row_map, void* dst, int64_t rows_src,

@@ -11,8 +11,7 @@ size_t xmli_gemm_split_ws_bytes(int64_t M, int K, int dt);
 static inline int xmli_act_dt(int dt) { return dt == XML_F16S ? XML_F32 : dt; }
 static inline bool xmli_model_dt_ok(int dt) { return dt == XML_F32 || dt == XML_BF16 || dt == XML_F16S; }
 // y = LN(act(A W^T + bias) + addend) * g + b with the LayerNorm in the GEMM epilogue (gemm256p.hip); callers check
-// xmli_gemm_ln_eligible and pass xmli_gemm_ln_workspace_bytes(M, N) bytes of scratch
-bool xmli_gemm_ln_eligible(int64_t M, int N, int K, int dt);
+// dispatch::gemm_ln_fused and pass xmli_gemm_ln_workspace_bytes(M, N) bytes of scratch
 size_t xmli_gemm_ln_workspace_bytes(int64_t M, int N);
 int xmli_gemm_ln(const void* A, const void* W, const float* bias, const void* addend, const float* ln_g, const float* ln_b,
                  void* y, int64_t M, int N, int K, int relu, int add_mode, int seq_len, int dt, void* ln_ws,

@@ -7,13 +7,7 @@
 #pragma once
 #include "common.h"
 
-constexpr int L2N_MAXJ = 8;      // chunks per lane: rows of up to 32 * 8 chunks = 4096 bytes
-
-template <typename T>
-__device__ __forceinline__ bool l2n_ok(int d) {
-  constexpr int VEC = 16 / (int)sizeof(T);
-  return d % VEC == 0 && d / VEC <= 32 * L2N_MAXJ;
-}
+using dispatch::L2N_MAXJ;      // chunks per lane; dispatch::l2n_vec_ok says which rows fit
 
 // loads the row's chunks of this lane into `v` (zeros beyond the row, or for a missing row) and returns 1 / max(norm, eps)
 // as the DIVISOR (the callers divide, like the reference)

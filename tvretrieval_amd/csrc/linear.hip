@@ -30,12 +30,12 @@ __global__ __launch_bounds__(256) void gemm_bias_act_kernel(const T* __restrict_
     const int n = n0 + r;
     return n < N ? reinterpret_cast<const char*>(W + (int64_t)n * K) : nullptr;
   };
-  if constexpr (BMN < 128 && !IsSplit16<T>::value && !std::is_same<T, f16_t>::value) {
+  if constexpr (dispatch::gemm_small_deep(BMN, IsSplit16<T>::value || std::is_same<T, f16_t>::value)) {
     // few rows: the K loop is a chain of memory round trips -- loads 3 (or 2) steps ahead (gemm_mainloop_deep)
-    const int nsteps = (K * (int)sizeof(T) + Cfg::ROWB - 1) / Cfg::ROWB;
-    if (nsteps % 3 == 0) gemm_mainloop_deep<T, Cfg, 3>(acc, a_row, b_row, K * (int)sizeof(T), smem);
-    else if (nsteps % 2 == 0) gemm_mainloop_deep<T, Cfg, 2>(acc, a_row, b_row, K * (int)sizeof(T), smem);
-    else gemm_mainloop<T, Cfg>(acc, a_row, b_row, K * (int)sizeof(T), smem);
+    dispatch::gemm_small_kloop_run(
+        K * (int)sizeof(T), [&] { gemm_mainloop_deep<T, Cfg, 3>(acc, a_row, b_row, K * (int)sizeof(T), smem); },
+        [&] { gemm_mainloop_deep<T, Cfg, 2>(acc, a_row, b_row, K * (int)sizeof(T), smem); },
+        [&] { gemm_mainloop<T, Cfg>(acc, a_row, b_row, K * (int)sizeof(T), smem); });
   } else {
     gemm_mainloop<T, Cfg>(acc, a_row, b_row, K * (int)sizeof(T), smem);
   }
@@ -70,12 +70,10 @@ static int launch_gemm(const void* A, const void* W, const float* bias, const vo
                        int N, int K, int relu, int add_mode, int seq_len, hipStream_t st,
                        const float* row_scale = nullptr) {
   // Few rows (the pooled-query linears of a 128-pair training batch, a 50-query batch's encoder): 128 x 128 tiles leave most
-  // of the chip idle behind a serial K loop (128 x 768 x 768: 6 workgroups, 32 us).  Smaller tiles of the SAME mainloop -- every
-  // output element sees the same MFMA sequence over K, the results are bit-identical -- until a few hundred workgroups exist
-  // (the small tiles also take the deep-prefetch K loop, gemm_mainloop_deep).  Every form here, gemm256 and gemm256p give
-  // the same bits for a row whatever M is: tests/test_gpu_row_invariance.py crosses each edge by one row.
-  const int64_t wg128 = (int64_t)cdiv(N, 128) * cdiv(M, 128);
-  const int bmn = wg128 >= 512 ? 128 : wg128 * 4 >= 192 ? 64 : 32;
+  // of the chip idle behind a serial K loop (128 x 768 x 768: 6 workgroups, 32 us).  Smaller tiles of the SAME mainloop give
+  // every output element the same MFMA sequence over K: every form here, gemm256 and gemm256p give the same bits for a row
+  // whatever M is (tests/test_gpu_row_invariance.py crosses each edge by one row).
+  const int bmn = dispatch::gemm_small_tile(M, N);
   dim3 grid(cdiv(N, bmn), cdiv(M, bmn));
   if (bmn == 128)
     hipLaunchKernelGGL((gemm_bias_act_kernel<T, OutT, AddT, 128>), grid, dim3(256), 0, st, (const T*)A, (const T*)W, bias,
@@ -90,10 +88,8 @@ static int launch_gemm(const void* A, const void* W, const float* bias, const vo
   return XML_OK;
 }
 
-bool xmli_gemm256_eligible(int64_t M, int N, int K, int dt);
 int xmli_gemm256(const void* A, const void* W, const float* bias, const void* addend, void* out, int64_t M, int N,
                  int K, int relu, int add_mode, int seq_len, int out_f32, int dt, hipStream_t st);
-bool xmli_gemm256p_eligible(int64_t M, int N, int K, int dt);
 int xmli_gemm256p(const void* A, const void* W, const float* bias, const void* addend, void* out, int64_t M, int N,
                   int K, int relu, int add_mode, int seq_len, int out_f32, int dt, hipStream_t st);
 #ifdef XML_DEBUG_VARIANTS
@@ -101,7 +97,6 @@ int g_gemm_variant = 0;
 extern "C" void xml_debug_set_gemm_variant(int v) { g_gemm_variant = v; }
 #endif
 
-bool xmli_gemm256_f16s_eligible(int64_t M, int N, int K3);
 int xmli_gemm256_f16s(const void* A, const void* W, const float* bias, const void* addend, void* out,
                       const float* row_scale, int64_t M, int N, int K3, int relu, int add_mode, int seq_len,
                       hipStream_t st);
@@ -130,18 +125,21 @@ int xmli_gemm(const void* A, const void* W, const float* bias, const void* adden
     const float* trailer = reinterpret_cast<const float*>((const char*)W + align_up((size_t)N * K * 6, 16));
     const int rc = xmli_split_f16_kcat((const float*)A, a_cat, rs, trailer, M, K, st);
     if (rc) return rc;
-    if (xmli_gemm256_f16s_eligible(M, N, 3 * K))
+    if (dispatch::gemm_kernel(M, N, K, dt) == XML_GEMM_256)
       return xmli_gemm256_f16s(a_cat, W, bias, addend, out, rs, M, N, 3 * K, relu, add_mode, seq_len, st);
     return launch_gemm<f16_t, float, float>(a_cat, W, bias, addend, out, M, N, 3 * K, relu, add_mode, seq_len, st, rs);
   }
   if (dt != XML_F32 && dt != XML_BF16) return XML_ERR_BAD_ARG;
-  // fewer than 64 tiles of 256 x 256 (a 50-query batch's encoder, the query branch of a training step): a quarter of the
-  // chip at best behind a serial K loop -- the small-tile, deep-prefetch form of the register-staged kernel instead
-  // (3 840 x 768 x 768: 28 -> 11 us)
-  const bool few = (int64_t)cdiv(M, 256) * cdiv(N, 256) < 64 && g_gemm_variant != 3;
-  if (!few && g_gemm_variant == 0 && xmli_gemm256p_eligible(M, N, K, dt))
+  // few tiles of 256 x 256 (a 50-query batch's encoder, the query branch of a training step) take the small-tile,
+  // deep-prefetch form of the register-staged kernel (3 840 x 768 x 768: 28 -> 11 us)
+  int kernel = dispatch::gemm_kernel(M, N, K, dt);
+  if (g_gemm_variant != 0) {      // (debug build) 1 - 3 never take the persistent kernel; 1: small tiles only; 3: no `few`
+    const bool few = dispatch::gemm_few(M, N) && g_gemm_variant != 3;
+    kernel = !few && g_gemm_variant != 1 && dispatch::gemm256_ok(M, N, K, dt) ? XML_GEMM_256 : XML_GEMM_SMALL;
+  }
+  if (kernel == XML_GEMM_256P)
     return xmli_gemm256p(A, W, bias, addend, out, M, N, K, relu, add_mode, seq_len, out_f32, dt, st);
-  if (!few && g_gemm_variant != 1 && xmli_gemm256_eligible(M, N, K, dt))
+  if (kernel == XML_GEMM_256)
     return xmli_gemm256(A, W, bias, addend, out, M, N, K, relu, add_mode, seq_len, out_f32, dt, st);
   if (dt == XML_F32) {
     if (K % 4) return XML_ERR_UNSUPPORTED;
@@ -433,9 +431,10 @@ extern "C" int xml_l2norm_rows(const void* x, void* y, int64_t rows, int d, int 
   XML_ENTER();
   if (!x || !y || rows <= 0 || d <= 0) return XML_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  if (dt == XML_F32 && d % 4 == 0 && d / 4 <= 32 * L2N_MAXJ)
+  const bool vec = dispatch::l2n_vec_ok(d, dt);
+  if (vec && dt == XML_F32)
     hipLaunchKernelGGL(l2norm_rows_vec_kernel<float>, dim3(cdiv(rows, 8)), dim3(256), 0, st, (const float*)x, (float*)y, rows, d);
-  else if (dt == XML_BF16 && d % 8 == 0 && d / 8 <= 32 * L2N_MAXJ)
+  else if (vec)
     hipLaunchKernelGGL(l2norm_rows_vec_kernel<bf16_t>, dim3(cdiv(rows, 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y, rows, d);
   else if (dt == XML_F32)
     hipLaunchKernelGGL(l2norm_rows_kernel<float>, dim3(cdiv(rows, 4)), dim3(256), 0, st, (const float*)x, (float*)y, rows, d);
@@ -518,7 +517,7 @@ static inline int k_pad8(int d_in) { return (d_in + 7) & ~7; }
 // its epilogue, that kernel's per-workgroup scratch -- the larger of the two is reserved)
 extern "C" size_t xml_linear_ln_relu_pos_workspace_bytes(int64_t rows, int d_in, int hidden, int dt) {
   const size_t pre = align_up((size_t)rows * hidden * 4, 256);
-  const size_t lnw = xmli_gemm_ln_eligible(rows, hidden, k_pad8(d_in), dt) ? xmli_gemm_ln_workspace_bytes(rows, hidden) : 0;
+  const size_t lnw = dispatch::gemm_ln_fused(rows, hidden, k_pad8(d_in), dt) ? xmli_gemm_ln_workspace_bytes(rows, hidden) : 0;
   return align_up((size_t)rows * k_pad8(d_in) * dt_size(dt), 256) + (pre > lnw ? pre : lnw) +
          xmli_gemm_split_ws_bytes(rows, k_pad8(d_in), dt);
 }
@@ -543,7 +542,7 @@ extern "C" int xml_linear_ln_relu_pos(const void* x, int x_dt, const float* ln_i
                                    xmli_gemm_split_ws_bytes(rows, d_pad, dt) : nullptr;
   int rc = xmli_add_layernorm(x, x_dt, nullptr, ln_in_g, ln_in_b, xn, rows, d_in, d_pad, adt, st);
   if (rc) return rc;
-  if (xmli_gemm_ln_eligible(rows, hidden, d_pad, dt) &&    // LN_pos in the GEMM epilogue: two launches, no f32 round trip
+  if (dispatch::gemm_ln_fused(rows, hidden, d_pad, dt) &&    // LN_pos in the GEMM epilogue: two launches, no f32 round trip
       xmli_gemm_ln(xn, w, b, pos, ln_pos_g, ln_pos_b, y, rows, hidden, d_pad, /*relu*/ 1, /*add_mode*/ 1, seq_len, dt, pre,
                    st) == XML_OK)
     return XML_OK;                                         // (a refused launch falls through to the 3-launch path)
@@ -662,7 +661,7 @@ extern "C" int xml_linear_ln_relu_pos_packed(const void* x, int x_dt, const int3
   int rc = add_layernorm_rows(x, x_dt, nullptr, ln_in_g, ln_in_b, xn, rows, d_in, d_in, adt, st, src_row);
   if (rc) return rc;
   // with seq_len = rows, "row % seq_len" addresses the gathered positional rows one to one
-  if (xmli_gemm_ln_eligible(rows, hidden, d_in, dt) &&
+  if (dispatch::gemm_ln_fused(rows, hidden, d_in, dt) &&
       xmli_gemm_ln(xn, w, b, pg, ln_pos_g, ln_pos_b, y, rows, hidden, d_in, /*relu*/ 1, /*add_mode*/ 1, (int)rows, dt, pre,
                    st) == XML_OK)
     return XML_OK;

@@ -114,39 +114,35 @@ int xmli_q2c_scores_ring(const void* qn, const void* cn, const float* mask, floa
 int xmli_q2c_scores_256(const void* qn, const void* cn, const float* mask, float* out, int64_t ld_out, int nq, int nv,
                         int lpad, int hidden, int combine, int dt, hipStream_t st);
 
+// one launch of a persistent kernel (the product's, or in the debug build the abandoned variants 5 / 6) over 1 or 2 modalities
+static int q2c_persist_launch(int n_mod, const void* qn0, const void* cn0, const float* mask0, const void* qn1,
+                              const void* cn1, const float* mask1, float* out, int64_t ld_out, int nq, int nv, int lpad,
+                              int hidden, int dt, hipStream_t st) {
+  const void* q[2] = {qn0, qn1};
+  const void* c[2] = {cn0, cn1};
+  const float* m[2] = {mask0, mask1};
+#ifdef XML_DEBUG_VARIANTS
+  if (g_q2c_variant == 6) return xmli_q2c_scores_persist32(n_mod, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, st);
+  if (g_q2c_variant == 5) return xmli_q2c_scores_persist4(n_mod, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, st);
+#endif
+  return xmli_q2c_scores_persist(n_mod, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, st);
+}
+// (debug build) does variant g_q2c_variant run the persistent launch where the product dispatch does?
+static bool q2c_variant_persists(int dt) {
+  return g_q2c_variant == 0 || g_q2c_variant == 4 || g_q2c_variant == 5 || (g_q2c_variant == 6 && dt == XML_BF16);
+}
+
 extern "C" int xml_q2c_scores(const void* qn, const void* cn, const float* mask, float* out, int64_t ld_out, int nq,
                               int nv, int lpad, int hidden, int combine, int dt, xml_stream_t stream) {
   XML_ENTER();
   if (!qn || !cn || !mask || !out || nq <= 0 || nv <= 0 || lpad <= 0 || hidden <= 0 || ld_out < nv)
     return XML_ERR_BAD_ARG;
-  if (lpad % 16 || lpad > 128 || hidden % 8) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::q2c_shape_ok(lpad, hidden)) return XML_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (dt != XML_F32 && dt != XML_BF16 && dt != XML_F16) return XML_ERR_BAD_ARG;
-  // (XML_F16 row-major operands -- corpora too small / hidden sizes too short for the tiled persistent kernel -- take the
-  // register-staged kernel below)
-  const bool dma_ok = dt != XML_F16 && ((size_t)hidden * dt_size(dt)) % 128 == 0;
-  const bool persist_ok = dt != XML_F16 && lpad == 128 && ((size_t)hidden * dt_size(dt)) % 128 == 0 &&
-                          (size_t)hidden * dt_size(dt) >= 384;
-  if ((g_q2c_variant == 0 || g_q2c_variant == 4) && persist_ok && !combine) {
-    const void* q[2] = {qn, qn};
-    const void* c[2] = {cn, cn};
-    const float* m[2] = {mask, mask};
-    return xmli_q2c_scores_persist(1, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, st);
-  }
-#ifdef XML_DEBUG_VARIANTS
-  if (g_q2c_variant == 6 && persist_ok && !combine && dt == XML_BF16) {
-    const void* q[2] = {qn, qn};
-    const void* c[2] = {cn, cn};
-    const float* m[2] = {mask, mask};
-    return xmli_q2c_scores_persist32(1, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, st);
-  }
-  if (g_q2c_variant == 5 && persist_ok && !combine) {
-    const void* q[2] = {qn, qn};
-    const void* c[2] = {cn, cn};
-    const float* m[2] = {mask, mask};
-    return xmli_q2c_scores_persist4(1, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, st);
-  }
-#endif
+  if (!dispatch::q2c_dt_ok(dt)) return XML_ERR_BAD_ARG;
+  if (dispatch::q2c_kernel(lpad, hidden, dt, combine != 0) == XML_Q2C_PERSIST && q2c_variant_persists(dt))
+    return q2c_persist_launch(1, qn, cn, mask, qn, cn, mask, out, ld_out, nq, nv, lpad, hidden, dt, st);
+  const bool dma_ok = dispatch::q2c_ring_ok(hidden, dt);
   if ((g_q2c_variant == 0 || g_q2c_variant == 3) && dma_ok)
     return xmli_q2c_scores_ring(qn, cn, mask, out, ld_out, nq, nv, lpad, hidden, combine, dt, st);
 #ifdef XML_DEBUG_VARIANTS
@@ -185,30 +181,11 @@ extern "C" int xml_q2c_scores_fused(int n_mod, const void* qn0, const void* cn0,
   if (n_mod < 1 || n_mod > 2 || !qn0 || !cn0 || !mask0 || !out) return XML_ERR_BAD_ARG;
   if (n_mod == 2 && (!qn1 || !cn1 || !mask1)) return XML_ERR_BAD_ARG;
   if (nq <= 0 || nv <= 0 || lpad <= 0 || hidden <= 0 || ld_out < nv) return XML_ERR_BAD_ARG;
-  if (dt != XML_F32 && dt != XML_BF16 && dt != XML_F16) return XML_ERR_BAD_ARG;
-  if (lpad % 16 || lpad > 128 || hidden % 8) return XML_ERR_UNSUPPORTED;
-  const size_t kb = (size_t)hidden * dt_size(dt);
-  const bool persist_ok = dt != XML_F16 && lpad == 128 && kb % 128 == 0 && kb >= 384;
-  if ((g_q2c_variant == 0 || g_q2c_variant == 4) && persist_ok) {
-    const void* q[2] = {qn0, qn1};
-    const void* c[2] = {cn0, cn1};
-    const float* m[2] = {mask0, mask1};
-    return xmli_q2c_scores_persist(n_mod, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, (hipStream_t)stream);
-  }
-#ifdef XML_DEBUG_VARIANTS
-  if (g_q2c_variant == 6 && persist_ok && dt == XML_BF16) {
-    const void* q[2] = {qn0, qn1};
-    const void* c[2] = {cn0, cn1};
-    const float* m[2] = {mask0, mask1};
-    return xmli_q2c_scores_persist32(n_mod, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, (hipStream_t)stream);
-  }
-  if (g_q2c_variant == 5 && persist_ok) {
-    const void* q[2] = {qn0, qn1};
-    const void* c[2] = {cn0, cn1};
-    const float* m[2] = {mask0, mask1};
-    return xmli_q2c_scores_persist4(n_mod, q, c, m, out, ld_out, nq, nv, lpad, hidden, dt, (hipStream_t)stream);
-  }
-#endif
+  if (!dispatch::q2c_dt_ok(dt)) return XML_ERR_BAD_ARG;
+  if (!dispatch::q2c_shape_ok(lpad, hidden)) return XML_ERR_UNSUPPORTED;
+  if (dispatch::q2c_fused_kernel(n_mod, lpad, hidden, dt, 0) == XML_Q2C_PERSIST && q2c_variant_persists(dt))
+    return q2c_persist_launch(n_mod, qn0, cn0, mask0, qn1, cn1, mask1, out, ld_out, nq, nv, lpad, hidden, dt,
+                              (hipStream_t)stream);
   int rc = xml_q2c_scores(qn0, cn0, mask0, out, ld_out, nq, nv, lpad, hidden, 0, dt, stream);
   if (rc || n_mod == 1) return rc;
   return xml_q2c_scores(qn1, cn1, mask1, out, ld_out, nq, nv, lpad, hidden, 1, dt, stream);

@@ -19,7 +19,7 @@
 // query operands stay in that XCD's 4 MiB L2 and only clip tiles stream in (6 % instead of 19 % line misses).
 #include <type_traits>
 
-#include "common.h"
+#include "ring256.h"
 
 struct Q2cPersistArgs {
   const void* qn[2];
@@ -39,62 +39,6 @@ struct Q2cPersistArgs {
                // passes 2..n over a chunk's clip tiles are served by the 256 MB Infinity Cache instead of HBM
 };
 
-__device__ __forceinline__ void dma16s(uint32_t voff, const char* sbase, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds_dst)
-      : "memory");
-}
-
-// two consecutive 1 KiB pieces of one operand
-__device__ __forceinline__ void dma_pair(uint32_t v0, uint32_t v1, const char* sb, uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3"
-      :
-      : "v"(v0), "v"(v1), "s"(lds_dst), "s"(sb)
-      : "memory", "scc");
-}
-// four consecutive 1 KiB pieces of one operand
-__device__ __forceinline__ void dma_quad(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, const char* sb,
-                                         uint32_t lds_dst) {
-  asm volatile(
-      "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %5\n\t"
-      "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %5"
-      :
-      : "v"(v0), "v"(v1), "v"(v2), "v"(v3), "s"(lds_dst), "s"(sb)
-      : "memory", "scc");
-}
-
-// first K chunk of a segment: C = 0 as an inline constant (no 128 v_mov per segment to clear the accumulators)
-template <typename T> struct MmaInit;
-template <> struct MmaInit<float> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
-  }
-};
-template <> struct MmaInit<bf16_t> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    union { uint4 u; bf16x8_v v; } ua, ub;
-    ua.u = a; ub.u = b;
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua.v, ub.v, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  }
-};
-
-template <> struct MmaInit<f16_t> {
-  __device__ static __forceinline__ void chunk(f32x4& acc, const uint4& a, const uint4& b) {
-    union { uint4 u; f16x8_v v; } ua, ub;
-    ua.u = a; ub.u = b;
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ua.v, ub.v, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  }
-};
 // XML_F16 operands are the hi planes of xml_split_f16_rows(fixed_log2 = XML_F16_UNIT_LOG2): unit-norm rows scaled by
 // 2^14 on both sides, so a score leaves the accumulators scaled by 2^28 (the exact-rank FILTER, inference.stage_exact_topk)
 static constexpr float K6_F16_OUT_SCALE = 1.f / (float)(1u << (2 * XML_F16_UNIT_LOG2));
@@ -126,17 +70,6 @@ __device__ __forceinline__ float dpp_read(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
-// lane id from the hardware (v_mbcnt), as a VOLATILE asm: hipcc can neither hoist it out of the segment loop nor keep a
-// copy of threadIdx live across the K loop (the persistent kernels sit at 246-256 VGPRs; a spilled lane id comes back
-// through a scratch load whose s_waitcnt vmcnt(0) would drain the hand-counted DMA stream once per segment)
-__device__ __forceinline__ int lane_id_now() {
-  int l;
-  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-  return l;
-}
-
-__device__ __forceinline__ int swz4p(int row) { return (0x78 >> (((row >> 2) & 3) << 1)) & 3; }
-
 // Specialised to lpad == 128 (one video per 128-column group -- the TVR shape): no per-column divisions, one
 // reduction per accumulator row.  Other clip paddings use the per-modality kernels (q2c_ring.hip).
 //
@@ -167,9 +100,7 @@ __device__ __forceinline__ int swz4p(int row) { return (0x78 >> (((row >> 2) & 3
 template <typename T, int ABL = 0, bool PHASED = true, bool TILED = false, bool NOMASK = false, bool BITMASK = false,
           bool PACKED = false>   // ABL (debug library only): 1 no DMA after the prologue, 2 no MFMA, 8 timing probe
 __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
-  constexpr int ROWB = 64;
-  constexpr int OPER_BYTES = 256 * ROWB;
-  constexpr int SLOT_BYTES = 2 * OPER_BYTES;
+  using namespace ring256;
   // Uneven DMA duty: the timing probe shows the first wave group parked at the barrier ~35 % of the time while the
   // second is on the critical path, so the first group issues 6 of the 8 pieces per SIMD pair -- its wave w loads A
   // pieces 4w..4w+3 and B pieces 2w, 2w+1; wave 4+w loads B pieces 8+2w, 9+2w (+1 % measured against the even 4 / 4
@@ -181,8 +112,8 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
   // three slices in flight behind the awaited one instead of two, +1.1-1.3 % measured.
   // BITMASK: ragged corpora get the fifth slot too -- binary clip masks packed 128 bits per video arrive through SCALAR
   // loads (lgkmcnt, invisible to the hand-counted vmcnt of the DMA stream), no mask DMA, no LDS patches.
-  constexpr bool FIVE = NOMASK || BITMASK;       // (PACKED: four slots, the patch area carries the straddle hand-off)
-  constexpr int NSLOT = FIVE ? 5 : 4;
+  constexpr int NSLOT = dispatch::q2c_ring_slots(TILED, NOMASK ? 1 : BITMASK ? 2 : PACKED ? 3 : 0);
+  constexpr bool FIVE = NSLOT == dispatch::RING_SLOTS_NOMASK;
   constexpr int RING_BYTES = NSLOT * SLOT_BYTES;
   constexpr int MASK_OFF = RING_BYTES;            // 2 x 1 KiB mask patches (256 columns x f32)
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -247,7 +178,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
 
   auto setup_issue_segment = [&](bool new_tile) {
     const int q0 = ((i_g << qsh) + qt_off) * 256, v0 = clip_tile(i_c) * 2;
-    const int lane_o = lane_id_now();               // re-derived here: nothing lane-dependent stays live across the MFMA loop
+    const int lane_o = ring_lane_now();               // re-derived here: nothing lane-dependent stays live across the MFMA loop
     if (new_tile) {
       const int rsub = lane_o >> 2, pslot = lane_o & 3;
       {
@@ -256,13 +187,13 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
         auto off_a = [&](int piece) -> uint32_t {
           const int row = piece * 16 + rsub;
           const int qrow = (row < q_left) ? row : 0;
-          return (uint32_t)qrow * row_stride + (pslot ^ swz4p(row)) * 16;
+          return (uint32_t)qrow * row_stride + (pslot ^ ring_swz(row)) * 16;
         };
         auto off_b = [&](int piece) -> uint32_t {
           const int row = piece * 16 + rsub;
           // (PACKED: nv = 2 * tc wave tiles, every tile of the image is complete)
           const int brow = (PACKED || v0 + (row >> 7) < a.nv) ? row : (row & 127);
-          return (uint32_t)brow * row_stride + (pslot ^ swz4p(row)) * 16;
+          return (uint32_t)brow * row_stride + (pslot ^ ring_swz(row)) * 16;
         };
         if (grp == 0) {
           voff_a0 = off_a(wave * 4); voff_a1 = off_a(wave * 4 + 1); voff_x[0] = off_a(wave * 4 + 2); voff_x[1] = off_a(wave * 4 + 3);
@@ -277,7 +208,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
     if (!FIVE && !PACKED && wave == 0) {   // mask patch of the segment: lane l carries columns 4 l .. 4 l + 3 of the tile's 256 columns
       const int mrow = (v0 + (lane_o >> 5) < a.nv) ? lane_o : (lane_o & 31);
       const char* sbase_m = reinterpret_cast<const char*>(a.mask[i_mod]) + (int64_t)v0 * 128 * 4;
-      dma16s((uint32_t)mrow * 16, sbase_m, lds0 + MASK_OFF + (i_seg & 1) * 1024);
+      ring_dma16((uint32_t)mrow * 16, sbase_m, lds0 + MASK_OFF + (i_seg & 1) * 1024);
     }
   };
   // 4 DMA instructions: this wave's 32 rows of A and of B.  The stream SATURATES: once the walk is exhausted it keeps
@@ -309,10 +240,10 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
     if (ABL != 1 || i_gs < 4) {
       const uint32_t slot0 = lds0 + i_slot * SLOT_BYTES;
       if (grp == 0) {
-        dma_quad(voff_a0, voff_a1, voff_x[0], voff_x[1], sbase_a + koff, slot0 + wave_4k);
-        dma_pair(voff_b0, voff_b1, sbase_b + koff, slot0 + OPER_BYTES + wave_2k);
+        ring_dma_quad(voff_a0, voff_a1, voff_x[0], voff_x[1], sbase_a + koff, slot0 + wave_4k);
+        ring_dma_pair(voff_b0, voff_b1, sbase_b + koff, slot0 + OPER_BYTES + wave_2k);
       } else {
-        dma_pair(voff_b0, voff_b1, sbase_b + koff, slot0 + OPER_BYTES + wave_2k);      // (8192 + (wave - 4) * 2048)
+        ring_dma_pair(voff_b0, voff_b1, sbase_b + koff, slot0 + OPER_BYTES + wave_2k);      // (8192 + (wave - 4) * 2048)
       }
     }
     issue_advance();
@@ -323,8 +254,8 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
   setup_issue_segment(true);
 
   // ---- compute side ---------------------------------------------------------------------------------------------
-  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ swz4p(fr)) << 4);
-  const int b_off = OPER_BYTES + (wn * 128 + fr) * ROWB + ((fg ^ swz4p(fr)) << 4);
+  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ ring_swz(fr)) << 4);
+  const int b_off = OPER_BYTES + (wn * 128 + fr) * ROWB + ((fg ^ ring_swz(fr)) << 4);
   int c_g = i_g, c_c = i_c, c_mod = 0, c_seg = 0;
   int c_slot = 0;                                  // its ring slot
 
@@ -359,7 +290,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
   unsigned long long probe_r0 = 0;
   if (ABL == 8) { probe_t0 = __builtin_amdgcn_s_memtime(); probe_r0 = __builtin_amdgcn_s_memrealtime(); }
   for (;;) {      // one iteration = one (tile, modality) segment
-    f32x4 acc[4][8];       // written by the first slice of the segment (MmaInit: C = 0)
+    f32x4 acc[4][8];       // written by the first slice of the segment (RingInit: C = 0)
 
     auto slice_step = [&](uint4 (&fc)[4], uint4 (&fn)[4], auto init_tag) {
       constexpr bool INIT = decltype(init_tag)::value;
@@ -373,7 +304,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
         for (int nn = 0; nn < 4; ++nn) {
           const int n = (K6Order<T>::snake && (m & 1)) ? 3 - nn : nn;
           if (ABL == 2) asm volatile("" ::"v"(fc[m].x), "v"(fbL[n].x), "v"(fc[m].w), "v"(fbL[n].w));
-          else if constexpr (INIT) MmaInit<T>::chunk(acc[m][n], fbL[n], fc[m]);      // clips as the A operand: see the epilogue
+          else if constexpr (INIT) RingInit<T>::chunk(acc[m][n], fbL[n], fc[m]);      // clips as the A operand: see the epilogue
           else Mma<T>::chunk(acc[m][n], fbL[n], fc[m]);
         }
       // ONE wait: vmcnt(8) -- my DMAs of slice c_gs + 1 have landed, the two younger slices stay in flight -- and
@@ -405,7 +336,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
           for (int nn = 0; nn < 4; ++nn) {
             const int n = (K6Order<T>::snake && (m & 1)) ? 3 - nn : nn;
             if (ABL == 2) asm volatile("" ::"v"(fc[m].x), "v"(fbH[n].x), "v"(fc[m].w), "v"(fbH[n].w));
-            else if constexpr (INIT) MmaInit<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
+            else if constexpr (INIT) RingInit<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
             else Mma<T>::chunk(acc[m][n + 4], fbH[n], fc[m]);
           }
       };
@@ -440,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
     if constexpr (PACKED) {
       // acc[m][n][r] = score of query (wm * 64 + m * 16 + fr) against packed clip column (n * 16 + fg * 4 + r) of this wave tile
       const int q0 = ((c_g << qsh) + qt_off) * 256, ct = clip_tile(c_c);
-      const int lane_e = lane_id_now(), fr_e = lane_e & 15, fg_e = lane_e >> 4;      // (see setup_issue_segment)
+      const int lane_e = ring_lane_now(), fr_e = lane_e & 15, fg_e = lane_e >> 4;      // (see setup_issue_segment)
       const bool last_mod = c_mod == a.n_mod - 1;
       const int wt_s = __builtin_amdgcn_readfirstlane(ct * 2 + wn);
       typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -522,7 +453,7 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
       // One video per wave tile.  acc[m][n][r] = score of query (wm * 64 + m * 16 + fr) against clip (n * 16 + fg * 4 + r):
       // the maximum over the clips is an in-lane v_max3 chain (64 ops) and two permlane swaps across the four row groups.
       const int q0 = ((c_g << qsh) + qt_off) * 256, vid = clip_tile(c_c) * 2 + wn;
-      const int lane_e = lane_id_now(), fr_e = lane_e & 15, fg_e = lane_e >> 4;      // (see setup_issue_segment)
+      const int lane_e = ring_lane_now(), fr_e = lane_e & 15, fg_e = lane_e >> 4;      // (see setup_issue_segment)
       const bool last_mod = c_mod == a.n_mod - 1;
       const bool vid_ok = vid < a.nv;
       float run[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -630,9 +561,10 @@ __global__ __launch_bounds__(512, 2) void q2c_persist_kernel(Q2cPersistArgs a) {
 
 template <typename T>
 static int launch_q2c_persist(const Q2cPersistArgs& a, hipStream_t st, bool tiled, int mask_mode) {
-  const bool five = tiled && (mask_mode == 1 || mask_mode == 2);     // mask_mode 3: PACKED (four slots + the straddle patch)
-  // ring + two mask patches; PACKED: + the straddle patch (1 KiB) and the modality-0 stash (8 waves x 9 x 256 B)
-  const int lds = five ? 5 * 2 * 256 * 64 : mask_mode == 3 ? 4 * 2 * 256 * 64 + 1024 + 8 * 9 * 256 : 4 * 2 * 256 * 64 + 2048;
+  const int slots = dispatch::q2c_ring_slots(tiled, mask_mode);
+  // ring; four slots: + two mask patches; PACKED: + the straddle patch (1 KiB) and the modality-0 stash (8 waves x 9 x 256 B)
+  const int lds = slots * ring256::SLOT_BYTES +
+                  (slots == dispatch::RING_SLOTS_NOMASK ? 0 : mask_mode == 3 ? 1024 + 8 * 9 * 256 : 2048);
   void (*kern)(Q2cPersistArgs) = nullptr;
   bool ok = false;
 #define XML_K6_PICK(...) do { kern = q2c_persist_kernel<__VA_ARGS__>; ok = xml_lds_attr_once<q2c_persist_kernel<__VA_ARGS__>>(lds); } while (0)
@@ -654,9 +586,7 @@ static int launch_q2c_persist(const Q2cPersistArgs& a, hipStream_t st, bool tile
   return XML_OK;
 }
 
-// Requirements (checked by the caller, which otherwise uses the per-modality kernels): lpad == 128,
-// hidden * sizeof(T) a multiple of 128 bytes (an even number of 64-byte slices) and at least 6 slices:
-// the mask patch of segment s+2 is fetched 4 slices ahead and must not land before the epilogue of segment s.
+// Requirements, checked by the callers (which otherwise use the per-modality kernels): dispatch::q2c_tiled_ok.
 int xmli_q2c_scores_persist(int n_mod, const void* const* qn, const void* const* cn, const float* const* mask,
                             float* out, int64_t ld_out, int nq, int nv, int lpad, int hidden, int dt, hipStream_t st,
                             bool tiled, int mask_mode, const uint32_t* const* mbits, const int32_t* slot_ids) {
@@ -672,19 +602,8 @@ int xmli_q2c_scores_persist(int n_mod, const void* const* qn, const void* const*
   if (mask_mode == 3 && (!slot_ids || !tiled || (nv & 1))) return XML_ERR_BAD_ARG;
   if (lpad != 128) return XML_ERR_UNSUPPORTED;
   a.out = out; a.ld_out = ld_out; a.nq = nq; a.nv = nv; a.hidden = hidden; a.n_mod = n_mod;
-  a.tq = cdiv(nq, 256); a.tc = cdiv(nv, 2);
-  a.qsh = a.tq >= 5 ? 3 : a.tq >= 3 ? 2 : a.tq == 2 ? 1 : 0;     // few queries: more workgroups share a query tile
-  if (a.qsh == 3) {
-    // The walk hands every workgroup ceil(tq / 2^qsh) x ceil(tc / (8 x 2^(5 - qsh))) tiles, valid or not: with 43 query
-    // tiles (TVR val, 10 895 queries) the 8 x 4 super-tile walks 48 x 576 slots for 43 x 573 tiles, the 4 x 8 one 44 x 576
-    // (-8 % of the kernel's time).  Take the 4 x 8 shape when it saves more than 3 % of the slots -- it fetches every clip
-    // tile for 4 instead of 8 query tiles per XCD, which is what the 8 x 4 shape is there to avoid when the two tie.
-    auto slots = [&](int qsh) -> int64_t {
-      const int64_t qg = (a.tq + (1 << qsh) - 1) >> qsh, per = 8ll << (5 - qsh);
-      return (qg << qsh) * ((a.tc + per - 1) / per * per);
-    };
-    if (slots(2) * 100 < slots(3) * 97) a.qsh = 2;
-  }
+  a.tq = dispatch::q2c_tq(nq); a.tc = dispatch::q2c_tc(nv);
+  a.qsh = dispatch::q2c_qsh(a.tq, a.tc);
   if (g_q2c_qsh >= 0 && g_q2c_qsh <= 4) a.qsh = g_q2c_qsh;       // (debug build: tools/k6_l2_ab.py)
   // Walk order: rsh = 20 is the straight order (every query group walks the whole corpus).  The chunked order
   // (2^rsh rounds per Infinity-Cache-sized chunk, all query groups per chunk; debug knob xml_debug_set_q2c_chunk) was
@@ -770,9 +689,7 @@ extern "C" int xml_q2c_scores_packed(int n_mod, const void* qt0, const void* ct0
 }
 
 extern "C" int xml_q2c_tiled_ok(int lpad, int hidden, int dt) {
-  if (dt != XML_F32 && dt != XML_BF16 && dt != XML_F16) return 0;
-  const size_t kb = (size_t)hidden * dt_size(dt);
-  return lpad == 128 && kb % 128 == 0 && kb >= 384;
+  return dispatch::q2c_tiled_ok(lpad, hidden, dt);
 }
 
 extern "C" int64_t xml_q2c_tiled_bytes(int64_t rows, int hidden, int dt) {

@@ -24,7 +24,7 @@
 //   LDS image: lane-linear per DMA instruction (16 rows x 64 B); 16-byte slot j of row r lives at j ^ g((r >> 2) & 3),
 //   g = {0,2,3,1}, which makes every ds_read_b128 lane group hit 16 distinct 16-byte bank slots; the permutation is
 //   applied on the per-lane SOURCE address of the DMA and again on the read (guide rule 21).
-#include "common.h"
+#include "ring256.h"
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void glb_void;
@@ -42,18 +42,16 @@ __device__ __forceinline__ void dma16(const char* gsrc, uint32_t lds_dst) {
       : "memory");
 }
 
-__device__ __forceinline__ int swz4(int row) { return (0x78 >> (((row >> 2) & 3) << 1)) & 3; }
-
 template <typename T, int ABL = 0>   // ABL (perf ablations only): 1 no DMA in the loop, 2 no MFMA, 3 no ds_read in the loop
 __global__ __launch_bounds__(512, 2) void q2c_scores_kernel_ring(const T* __restrict__ qn, const T* __restrict__ cn,
                                                                  const float* __restrict__ mask,
                                                                  float* __restrict__ out, int64_t ld_out, int nq,
                                                                  int nv, int lpad, int hidden, int combine, int tq,
                                                                  int tc) {
-  constexpr int ROWB = 64;                  // bytes of K per row per slice
-  constexpr int OPER_BYTES = 256 * ROWB;    // 16 KiB
-  constexpr int SLOT_BYTES = 2 * OPER_BYTES;
-  constexpr int LEAD = 5;                   // DMA units in front of the phase being computed
+  using namespace ring256;
+  constexpr int NSLOT = dispatch::RING_SLOTS;
+  constexpr int LEAD = dispatch::RING_LEAD;      // DMA units in front of the phase being computed
+  static_assert((NSLOT & (NSLOT - 1)) == 0, "slots are addressed by masking the slice number");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int b = blockIdx.x;
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(512, 2) void q2c_scores_kernel_ring(const T* __rest
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = (wave * 2 + i) * 16 + rsub;
-      const int slot = pslot ^ swz4(row);
+      const int slot = pslot ^ ring_swz(row);
       int qrow = q0 + row;
       qrow = qrow < nq ? qrow : nq - 1;
       a_src[i] = reinterpret_cast<const char*>(qn) + (int64_t)qrow * k_bytes + slot * 16;
@@ -98,7 +96,7 @@ __global__ __launch_bounds__(512, 2) void q2c_scores_kernel_ring(const T* __rest
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem + wave * 2048;
   auto issue_unit = [&](int u) {
     const int slice = u >> 1;
-    const uint32_t dst = lds_base + (slice & 3) * SLOT_BYTES + (u & 1) * OPER_BYTES;
+    const uint32_t dst = lds_base + (slice & (NSLOT - 1)) * SLOT_BYTES + (u & 1) * OPER_BYTES;
     const int koff = slice * ROWB;
     if (u & 1) {
       dma16(b_src[0] + koff, dst);
@@ -116,8 +114,8 @@ __global__ __launch_bounds__(512, 2) void q2c_scores_kernel_ring(const T* __rest
     for (int n = 0; n < 8; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // read offsets inside a slot: row = base + 16 t + fr -> swizzle depends on fr only
-  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ swz4(fr)) << 4);
-  const int b_off = OPER_BYTES + (wn * 128 + fr) * ROWB + ((fg ^ swz4(fr)) << 4);
+  const int a_off = (wm * 64 + fr) * ROWB + ((fg ^ ring_swz(fr)) << 4);
+  const int b_off = OPER_BYTES + (wn * 128 + fr) * ROWB + ((fg ^ ring_swz(fr)) << 4);
 
   // ---- prologue -------------------------------------------------------------------------------------------
 #pragma unroll
@@ -133,7 +131,7 @@ __global__ __launch_bounds__(512, 2) void q2c_scores_kernel_ring(const T* __rest
   uint4 fa[4], fb[4];
   const int n_phases = n_units;             // one phase per unit: 2 per slice
   for (int p = 0; p < n_phases; p += 2) {
-    const char* slot = smem + ((p >> 1) & 3) * SLOT_BYTES;
+    const char* slot = smem + ((p >> 1) & (NSLOT - 1)) * SLOT_BYTES;
     // ---------------- phase p (h = 0) ----------------
     if (ABL != 3 || p == 0) {
 #pragma unroll
@@ -222,7 +220,7 @@ static int launch_q2c_ring(const void* qn, const void* cn, const float* mask, fl
   const int tq = cdiv(nq, 256), tc = cdiv(nv, 2 * vpg);
   const int64_t nsup = (int64_t)((tq + 7) / 8) * ((tc + 3) / 4);
   const unsigned grid = (unsigned)(((nsup + 7) / 8) * 8 * 32);
-  const int lds = 4 * 2 * 256 * 64;
+  const int lds = dispatch::RING_SLOTS * ring256::SLOT_BYTES;
   auto kern = q2c_scores_kernel_ring<T, 0>;
   bool ok = xml_lds_attr_once<q2c_scores_kernel_ring<T, 0>>(lds);
 #ifdef XML_DEBUG_VARIANTS
