@@ -1,7 +1,8 @@
 """Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
 
-usage: python tools/bench_index_update.py [--legs put,e2e,c3,c3r] [--batch 200] [--reps 21] [--pass-reps 5] [--queries 10000]
-                                          [--videos 21793] [--suite-wall "..."] [--out profiles/index_update_timing.md]
+usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp] [--batch 200] [--reps 21] [--pass-reps 5]
+                                          [--queries 10000] [--videos 21793] [--suite-wall "..."]
+                                          [--out profiles/index_update_timing.md]
 
   put   xml_index_put_rows alone on a --batch-video batch at the headline shape (H = 768, lpad = 128, bf16, two modalities),
         next to the existing passes it replaces run on the same rows in the same process: the fused normalise-and-tile pass
@@ -10,6 +11,8 @@ usage: python tools/bench_index_update.py [--legs put,e2e,c3,c3r] [--batch 200] 
   c3    the full-length headline corpus: search on a mutable index at capacity = n_videos against the one-shot index (the
         price of mask-bit mode against the mask-free K6), the 10 000-query pass and the 50-query graph replay
   c3r   the same on the ragged corpus with the real TVR clip counts (the price of giving up the length-bucketed image)
+  putp  xml_index_put_rows_packed (the packed form, MutableCorpusIndex(tiles=N)) next to xml_index_put_rows on the same batch
+  c3rp  the ragged corpus on three forms in one process: one-shot packed index, mutable index, packed mutable index
 
 Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
 same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
@@ -26,7 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tvretrieval_amd import inference as inf, ops  # noqa: E402
-from tvretrieval_amd.index_update import MutableCorpusIndex  # noqa: E402
+from tvretrieval_amd.index_update import BlockTable, MutableCorpusIndex, blocks_of  # noqa: E402
 
 HBM_STREAM = 6.3e12       # bytes / s: the achievable HBM stream rate of an MI355X (8.0 TB/s is the specification)
 
@@ -201,9 +204,131 @@ def search_leg(name, args, lines):
     torch.cuda.empty_cache()
 
 
+def putp_leg(args, lines):
+    """xml_index_put_rows_packed next to xml_index_put_rows on the same batch (the put leg's shape), alternating."""
+    import bench
+    dev, dt, h, lpad, b = "cuda", torch.bfloat16, 768, 128, args.batch
+    cap = 2 * b
+    g = torch.Generator(device=dev).manual_seed(0)
+    enc = [(torch.randn((b, lpad, h), device=dev, generator=g).to(dt), torch.randn((b, lpad, h), device=dev, generator=g).to(dt),
+            torch.ones((b, lpad), device=dev)) for _ in range(2)]
+    f2 = [torch.zeros((cap, lpad, h), dtype=dt, device=dev) for _ in range(2)]
+    mk = [torch.zeros((cap, lpad), device=dev) for _ in range(2)]
+    vlen = torch.zeros(cap, dtype=torch.int32, device=dev)
+    sid = torch.zeros(cap, dtype=torch.int32, device=dev)
+    live = torch.zeros((cap + 31) // 32, dtype=torch.int32, device=dev)
+    slots = torch.from_numpy(np.random.default_rng(0).permutation(cap)[:b].astype(np.int32)).to(dev)
+    k6 = [ops.TiledRows(torch.zeros(ops.q2c_tiled_numel(cap * lpad, h, dt), dtype=dt, device=dev), cap * lpad, h, (cap, lpad, h))
+          for _ in range(2)]
+    bits = [torch.zeros((cap, 4), dtype=torch.int32, device=dev) for _ in range(2)]
+    tiles = cap // 2                                          # as many tiles as the plain image: room for any lengths
+    pk6 = [ops.TiledRows(torch.zeros(ops.q2c_tiled_numel(tiles * 256, h, dt), dtype=dt, device=dev), cap * lpad, h, (cap, lpad, h))
+           for _ in range(2)]
+    pbits = [torch.zeros((2 * tiles, 4), dtype=torch.int32, device=dev) for _ in range(2)]
+    codes = torch.full((2 * tiles, 8), -2, dtype=torch.int32, device=dev)
+
+    def runs_for(lens):
+        table = BlockTable(tiles)
+        nbs = [blocks_of(n) for n in lens]
+        runs, _ = table.check_put(list(range(b)), nbs)
+        return torch.tensor(runs, dtype=torch.int32, device=dev), max(nbs), sum(nbs)
+
+    full, tvr = runs_for([lpad] * b), runs_for(bench.real_clip_counts(b, lpad).tolist())
+
+    def plain():
+        ops.index_put_rows([e[0] for e in enc], [e[1] for e in enc], [e[2] for e in enc], slots, None, k6, f2, mk, bits, vlen,
+                           sid, live, lpad)
+
+    def packed(r):
+        ops.index_put_rows_packed([e[0] for e in enc], [e[1] for e in enc], [e[2] for e in enc], slots, None, r[0], r[1], pk6, f2,
+                                  mk, pbits, codes, vlen, sid, live, lpad)
+
+    row = 2 * b * lpad * h * 2                                  # bytes of one pass over the batch's rows, both modalities
+    res = []
+    for rnd in ("", ", again"):
+        res += [("xml_index_put_rows" + rnd, timed(plain, args.reps), 4 * row),
+                ("xml_index_put_rows_packed, 8-block runs (the same bytes)" + rnd, timed(lambda: packed(full), args.reps), 4 * row),
+                ("xml_index_put_rows_packed, TVR clip counts (%d blocks of %d)" % (tvr[2], 8 * b) + rnd,
+                 timed(lambda: packed(tvr), args.reps), 3 * row + row * tvr[2] // (8 * b))]
+    lines += ["", "## The packed put kernel next to xml_index_put_rows", "",
+              "The same %d-video batch (x %d clips x H = %d, bf16, two modalities, scattered slots, one process, alternating).  The "
+              "packed entry reads f1 and writes K6 rows only inside a video's run; feat2 is read and written whole." % (b, lpad, h),
+              "", "| what | time per call | bytes / s |", "|---|---|---|"]
+    lines += ["| %s | %s | %.2f TB/s |" % (n, fmt(t, "us"), nb / (t[0] * 1e-3) / 1e12) for n, t, nb in res]
+    for ln in lines[-10:]:
+        print(ln, flush=True)
+
+
+def tiles_in_corpus_order(lens, chunk):
+    """Tiles a BlockTable uses when the corpus is added in order, `chunk` videos per call (host arithmetic only)."""
+    table = BlockTable((len(lens) + 1) // 2)
+    for r in range(0, len(lens), chunk):
+        slots = list(range(r, min(r + chunk, len(lens))))
+        table.commit_put(slots, table.check_put(slots, [blocks_of(n) for n in lens[r:r + chunk]])[0])
+    return table.tiles_used(), table.stats()["straddles"]
+
+
+def packed_search_leg(args, lines):
+    """The ragged corpus on three forms in one process: one-shot packed index, mutable index (tiles=None), packed mutable
+    index at tiles = what the corpus order needs (>= the one-shot plan's n_tiles) and at the plan's n_tiles + 10 %."""
+    import bench
+    _, _, l, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3r"]
+    nv, nq = args.videos, args.queries
+    be = bench.HipBackend(0)
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), torch.bfloat16)
+    lens = bench.real_clip_counts(nv, l)
+    n_clips = [int(x) for x in lens.tolist()]
+    batches = lambda: bench.context_batches(0, nv, l, dv, ds, True, True, be.device, lens=lens)      # noqa: E731
+    need, straddles = tiles_in_corpus_order(n_clips, bench.CHUNK)
+    with torch.no_grad():
+        fixed = inf.build_corpus_index(model, batches(), l_ref=l, n_videos=nv)
+        plan = fixed.feat1n[fixed.modalities[0]].plan
+        t_plan = plan.n_tiles
+        forms = [("one-shot packed index, %d tiles" % t_plan, fixed, t_plan),
+                 ("mutable index, tiles=None (%d tiles)" % ((nv + 1) // 2), MutableCorpusIndex.from_batches(model, batches(), nv, l_ref=l),
+                  (nv + 1) // 2)]
+        for t in sorted({max(t_plan, need), max(-(-t_plan * 11 // 10), need)}):
+            forms.append(("packed mutable index, tiles=%d" % t,
+                          MutableCorpusIndex.from_batches(model, batches(), nv, l_ref=l, n_clips=n_clips, tiles=t), t))
+        qf, qm = bench.synth_queries(nq, dq, be.device)
+        kw = dict(n_valid_tokens=int(qm.sum().item()))
+        passes = [[], []]
+        for rnd in (0, 1):
+            for _, index, _ in forms:
+                passes[rnd].append(timed(lambda: inf.vcmr_search(model, index, qf, qm, **kw), args.pass_reps, 2))
+        want = inf.vcmr_search(model, fixed, qf[:512], qm[:512])
+        same = [all(bool(torch.equal(want[k], inf.vcmr_search(model, index, qf[:512], qm[:512])[k])) for k in
+                    ("top_indices", "top_scores", "flat_indices", "flat_scores")) for _, index, _ in forms]
+        graphs = [graph_ms(model, index, qf, qm) for _, index, _ in forms]
+    lines += ["", "## The ragged corpus (c3r) on three forms of index, one process", "",
+              "%d videos x %d clips, real TVR clip counts, hidden %d, bf16, %d queries.  The one-shot plan packs the corpus into %d "
+              "tiles (%d straddling videos); a BlockTable filled in corpus order, %d videos per call, needs %d tiles (%d straddling "
+              "videos), so `tiles=%d` is the smallest packed mutable index this order fills%s.  First 512 queries against the one-shot "
+              "index, video lists, scores, moments: %s."
+              % (nv, l, hidden, nq, t_plan, plan.n_straddles, bench.CHUNK, need, straddles, max(t_plan, need),
+                 "" if need <= t_plan else " (tiles=%d, the plan's own count, is refused)" % t_plan,
+                 ", ".join("%s: %s" % (n.split(",")[0], "identical" if s else "NOT identical") for (n, _, _), s in zip(forms, same))),
+              "", "| index | tiles / plan's | vcmr_search, %d queries | again | 50-query graph replay | index bytes |" % nq,
+              "|---|---|---|---|---|---|"]
+    for i, (name, index, t) in enumerate(forms):
+        lines.append("| %s | %.3f | %s | %s | %s | %.2f GB |" % (name, t / t_plan, fmt(passes[0][i]), fmt(passes[1][i]), fmt(graphs[i]),
+                                                               index.hbm_bytes() / 1e9))
+    med = [(passes[0][i][0] + passes[1][i][0]) / 2 for i in range(len(forms))]
+    for i in range(2, len(forms)):
+        lines += ["", "%s: %.1f ms per pass against %.1f ms on tiles=None (%+.1f %%) and %.1f ms one-shot (x %.3f at a tile ratio of "
+                  "%.3f); replay %.3f ms against %.3f ms and %.3f ms."
+                  % (forms[i][0], med[i], med[1], (med[i] / med[1] - 1) * 100, med[0], med[i] / med[0], forms[i][2] / t_plan,
+                     graphs[i][0], graphs[1][0], graphs[0][0])]
+    for ln in lines[-14:]:
+        print(ln, flush=True)
+    del forms, fixed
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", default="put,e2e,c3,c3r")
+    ap.add_argument("--legs", default="put,putp,e2e,c3,c3r,c3rp")
     ap.add_argument("--batch", type=int, default=200)
     ap.add_argument("--videos", type=int, default=21793)
     ap.add_argument("--queries", type=int, default=10000)
@@ -222,11 +347,15 @@ def main():
     legs = args.legs.split(",")
     if "put" in legs:
         put_leg(args, lines)
+    if "putp" in legs:
+        putp_leg(args, lines)
     if "e2e" in legs:
         e2e_leg(args, lines)
     for name in ("c3", "c3r"):
         if name in legs:
             search_leg(name, args, lines)
+    if "c3rp" in legs:
+        packed_search_leg(args, lines)
     if args.suite_wall:
         lines += ["", "## GPU test wall time", "", args.suite_wall]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

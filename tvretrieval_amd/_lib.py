@@ -242,12 +242,18 @@ SIGNATURES = {
     "xml_dispatch_l2norm": (c_int, [c_int, c_int]),
 }
 
+# the companion header include/xmlhip_index.h (tests/test_index_packed_capi.py checks): the packed form of the updatable index
+SIGNATURES_INDEX = {
+    "xml_index_put_rows_packed": (c_int, [c_int] + [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 12 + [c_int] * 6 + [c_void_p]),
+    "xml_index_clear_rows_packed": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
+}
+
 _lib = None
 
 
 def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -3,6 +3,9 @@
   SlotTable            the host side: which of the `capacity` slots are live, the caller's id of each (no GPU needed)
   MutableCorpusIndex   a CorpusIndex of `capacity` slots allocated once; every update is a stream-ordered launch
                        (ops.index_put_rows / ops.index_clear_rows) that reads nothing back and re-allocates nothing
+  BlockTable           the host side of the packed form (create(..., tiles=N)): which run of 16-row blocks of the packed K6
+                       image each live slot owns (ops.index_put_rows_packed / ops.index_clear_rows_packed keep the image,
+                       its code table and its mask words in step)
 
 Slot numbers are what top_indices, flat_indices, video_allow bits, svmr_video and explain_moments pairs mean on such an
 index.  A search sees `live AND video_allow` (inference.stage_video_topk), i.e. by the definition of a restricted search the
@@ -10,6 +13,7 @@ unrestricted search over the corpus of the live videos, in slot numbering.  What
 fixed here for the index's lifetime: K6 always reads mask bits (never the mask-free kernel, no length-bucketed image), K7 / K9
 always take the valid lengths (ragged = True), l_ref is set at creation -- so a GraphedVcmrSearch captured on the index stays
 valid across updates."""
+import bisect
 import heapq
 
 import torch
@@ -140,6 +144,200 @@ class SlotTable(object):
             heapq.heappush(self._free, s)
 
 
+def blocks_of(n_clips):
+    """Blocks of 16 clips a video of this valid length (last valid clip + 1 over the modalities' masks) occupies in the packed
+    K6 image: max(ceil(len / 16), 1), ops.PackPlan's rule."""
+    n = int(n_clips)
+    if not 0 <= n <= 128:
+        raise ValueError("a valid length of %d clips: the packed K6 image holds videos of 0..128 clips (1..8 blocks)" % n)
+    return max((n + 15) // 16, 1)
+
+
+class BlockTable(object):
+    """Host bookkeeping of the packed K6 image of a MutableCorpusIndex(tiles=N): n_tiles tiles of 16 blocks (16 clip rows
+    each).  A live slot owns one RUN of nb consecutive blocks inside one tile; a run may cross the boundary between blocks 7
+    and 8 of its tile (the two wave tiles: a straddle), never a tile boundary.  first = tile * 16 + block numbers the blocks.
+    Placement (deterministic): of the maximal free runs that hold nb blocks the SHORTEST; among those of that length one in
+    which the video does not straddle before one in which it does; then the lowest (tile, block).  The video sits at the
+    start of the chosen free run, so the run is never split in two.  (Moving a video that would straddle up to block 8 was
+    tried: no straddle among the TVR clip counts loaded in corpus order, but 5 448 tiles instead of 5 128 -- K6's time follows
+    the tiles, a straddle costs one barrier per tile and modality.)  The free runs are the maximal runs of free blocks of each
+    tile, so a freed run is one with its free neighbours at once.
+    The check_* methods validate a whole call and change nothing; the commit_* methods apply what a check returned, once the
+    device launches are enqueued."""
+
+    def __init__(self, n_tiles):
+        n_tiles = int(n_tiles)
+        if n_tiles <= 0:
+            raise ValueError("BlockTable: n_tiles must be positive, got %d" % n_tiles)
+        self.n_tiles = n_tiles
+        self._owner = [None] * (n_tiles * 16)                     # block -> slot, None = free
+        self._run = {}                                            # slot -> (first, nb)
+        self._free = [[] for _ in range(17)]                      # length -> sorted first blocks of the maximal free runs
+        self._free[16] = [t * 16 for t in range(n_tiles)]
+        self.free_blocks = n_tiles * 16
+
+    # ---- queries ----------------------------------------------------------------------------------------------------------
+    def run_of(self, slot):
+        """(first, nb) of a slot's run, None when it has none."""
+        return self._run.get(slot)
+
+    def runs(self):
+        """{slot: (first, nb)} of the live runs."""
+        return dict(self._run)
+
+    def free_runs(self):
+        """The maximal free runs as sorted (first, length) pairs."""
+        return sorted((f, n) for n in range(1, 17) for f in self._free[n])
+
+    def largest_free_run(self):
+        return max([n for n in range(1, 17) if self._free[n]] or [0])
+
+    def tiles_used(self):
+        """Tiles up to and including the last one that holds a block of a video."""
+        for b in range(self.n_tiles * 16 - 1, -1, -1):
+            if self._owner[b] is not None:
+                return b // 16 + 1
+        return 0
+
+    def stats(self):
+        """Free blocks, the largest free run per tile class (in an empty tile it is 16; `largest_free_run_partial`: in a tile
+        that holds a video), live runs, tiles by class, straddling videos."""
+        empty = len(self._free[16])
+        full = sum(1 for t in range(self.n_tiles) if all(o is not None for o in self._owner[t * 16:t * 16 + 16]))
+        return dict(n_tiles=self.n_tiles, free_blocks=self.free_blocks, live_runs=len(self._run),
+                    largest_free_run=self.largest_free_run(),
+                    largest_free_run_partial=max([n for n in range(1, 16) if self._free[n]] or [0]),
+                    tiles_empty=empty, tiles_full=full, tiles_partial=self.n_tiles - empty - full, tiles_used=self.tiles_used(),
+                    straddles=sum(1 for f, nb in self._run.values() if (f & 15) < 8 < (f & 15) + nb))
+
+    def row_map(self):
+        """(n_tiles * 256,) int32 CPU tensor: packed row -> slot * 128 + clip, -1 where no video lies -- what
+        ops.TiledRows.to_rows() needs (tests only: the search never reads it)."""
+        rows = torch.full((self.n_tiles * 256,), -1, dtype=torch.int32)
+        for slot, (first, nb) in self._run.items():
+            rows[first * 16:(first + nb) * 16] = torch.arange(slot * 128, slot * 128 + nb * 16, dtype=torch.int32)
+        return rows
+
+    # ---- the free runs ----------------------------------------------------------------------------------------------------
+    def _drop_free(self, first, n):
+        lst = self._free[n]
+        del lst[bisect.bisect_left(lst, first)]
+
+    def _take(self, first, nb, slot):
+        """Blocks [first, first + nb), all free, now belong to slot."""
+        lo, hi, t0 = first, first + nb, first & ~15
+        while lo > t0 and self._owner[lo - 1] is None:
+            lo -= 1
+        while hi < t0 + 16 and self._owner[hi] is None:
+            hi += 1
+        self._drop_free(lo, hi - lo)
+        if first > lo:
+            bisect.insort(self._free[first - lo], lo)
+        if hi > first + nb:
+            bisect.insort(self._free[hi - first - nb], first + nb)
+        self._owner[first:first + nb] = [slot] * nb
+        self._run[slot] = (first, nb)
+        self.free_blocks -= nb
+
+    def _release(self, slot):
+        """The exact inverse of _take: the slot's blocks are free again, one run with their free neighbours."""
+        first, nb = self._run.pop(slot)
+        lo, hi, t0 = first, first + nb, first & ~15
+        while lo > t0 and self._owner[lo - 1] is None:
+            lo -= 1
+        while hi < t0 + 16 and self._owner[hi] is None:
+            hi += 1
+        if first > lo:
+            self._drop_free(lo, first - lo)
+        if hi > first + nb:
+            self._drop_free(first + nb, hi - first - nb)
+        bisect.insort(self._free[hi - lo], lo)
+        self._owner[first:first + nb] = [None] * nb
+        self.free_blocks += nb
+
+    def _place(self, nb):
+        """First block for a run of nb blocks by the placement rule, None when no free run holds it."""
+        for n in range(nb, 17):
+            lst = self._free[n]
+            if not lst:
+                continue
+            for f in lst:
+                if (f & 15) >= 8 or (f & 15) + nb <= 8:
+                    return f
+            return lst[0]
+        return None
+
+    # ---- calls ------------------------------------------------------------------------------------------------------------
+    def check_put(self, slots, n_blocks, what="put"):
+        """Runs for the videos of one call: slots (distinct) and the block count of each.  A slot that has a run of that many
+        blocks keeps it; any other run of a named slot is freed first -- its blocks may serve the call -- and the videos are
+        placed in call order.  Returns (runs, clears): runs[i] = (first, nb) of slots[i], clears = the freed (first, nb) runs.
+        Nothing changes; ValueError when a video finds no room."""
+        n_blocks = [int(n) for n in n_blocks]
+        if len(n_blocks) != len(slots) or len(set(slots)) != len(slots):
+            raise ValueError("%s: %d block counts for %d distinct slots" % (what, len(n_blocks), len(set(slots))))
+        for nb in n_blocks:
+            if not 1 <= nb <= 8:
+                raise ValueError("%s: a run of %d blocks; a video occupies 1..8 blocks of 16 clips" % (what, nb))
+        moved = [(s, self._run[s]) for s, nb in zip(slots, n_blocks) if s in self._run and self._run[s][1] != nb]
+        for s, _ in moved:
+            self._release(s)
+        taken, runs, err = [], [], None
+        for s, nb in zip(slots, n_blocks):
+            if s in self._run:
+                runs.append(self._run[s])
+                continue
+            first = self._place(nb)
+            if first is None:
+                err = ("%s: no room for a video of %d blocks (%d clip rows) in the packed K6 image: %d free blocks of %d, the "
+                       "largest free run holds %d (tiles=%d; the image is not compacted and does not grow)"
+                       % (what, nb, nb * 16, self.free_blocks, self.n_tiles * 16, self.largest_free_run(), self.n_tiles))
+                break
+            self._take(first, nb, s)
+            taken.append(s)
+            runs.append((first, nb))
+        for s in reversed(taken):                                 # back to the state before the call
+            self._release(s)
+        for s, (first, nb) in reversed(moved):
+            self._take(first, nb, s)
+        if err is not None:
+            raise ValueError(err)
+        return runs, [r for _, r in moved]
+
+    def commit_put(self, slots, runs):
+        for s, r in zip(slots, runs):
+            if s in self._run and self._run[s] != r:
+                self._release(s)
+        for s, (first, nb) in zip(slots, runs):
+            if s not in self._run:
+                self._take(first, nb, s)
+
+    def check_remove(self, slots):
+        """The runs of the slots (each must have one)."""
+        for s in slots:
+            if s not in self._run:
+                raise ValueError("remove: slot %d has no run in the packed K6 image" % s)
+        return [self._run[s] for s in slots]
+
+    def commit_remove(self, slots):
+        for s in slots:
+            self._release(s)
+
+
+class _TablePlan(object):
+    """What ops.q2c_scores_fused and ops.TiledRows.to_rows ask of a PackPlan, for the packed image of a MutableCorpusIndex:
+    slot_ids = the device code table the update kernels maintain, n_tiles and n_videos fixed; row_map is made from the
+    host BlockTable when somebody asks (to_rows: tests)."""
+
+    def __init__(self, blocks, codes, n_videos):
+        self.blocks, self.slot_ids, self.n_tiles, self.n_videos = blocks, codes, blocks.n_tiles, int(n_videos)
+
+    @property
+    def row_map(self):
+        return self.blocks.row_map().to(self.slot_ids.device)
+
+
 class MutableCorpusIndex(CorpusIndex):
     """A CorpusIndex of `capacity` video slots whose rows are rewritten on the stream (module docstring).  Besides the
     CorpusIndex fields:
@@ -147,14 +345,29 @@ class MutableCorpusIndex(CorpusIndex):
       slot_ids   (capacity,) int32 device, slot -> the caller's id: the meta2vid of a search that passes none
       mask_bits  {modality: (capacity, 4) int32}: K6's mask-bit operand (on the tiled layout also feat1n[m].mask_bits)
       n_live     host counter; table: the SlotTable
-    n_videos == capacity: the kernels run over all slots."""
+    n_videos == capacity: the kernels run over all slots.
+
+    The packed form, create(..., tiles=N) (addendum): the K6 operand is the packed image of
+    xml_q2c_scores_packed over N tiles of 256 rows instead of capacity / 2, every video in a run of ceil(len / 16) blocks of
+    16 rows -- K6's time follows N, not capacity.  Then
+      blocks     the BlockTable: which run each live slot owns
+      codes      (2 N, 8) int32 device, K6's per-block code table (feat1n[m].plan.slot_ids); a video's code is its SLOT
+      mask_bits  {modality: (2 N, 4) int32}: the packed mask words (= feat1n[m].mask_bits)
+    feat2, mask, vlen, slot_ids and live stay per slot.  K6 then writes the score columns of the LIVE slots only: the columns
+    of free slots of stage_q2c's matrix (vcmr_search's out["q2c"]) are unspecified -- every search tests the live / allow bit
+    before the value (topk.hip); explain_moments' q2c of a pair that names a free slot is unspecified too.
+    Updates take the videos' valid lengths (last valid clip + 1 over the modalities) as n_clips=; without it they are read
+    from the masks with one small device -> host copy, the one synchronising path of an update.  Given up, beyond what the
+    plain form gives up: a fragmented image is not compacted, `tiles` does not grow (an update that finds no run is refused),
+    K6 costs N tiles whatever the occupancy."""
 
     def __init__(self, *a, **kw):
         raise TypeError("use MutableCorpusIndex.create(model, capacity) or MutableCorpusIndex.from_batches(...)")
 
     @classmethod
-    def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None):
-        """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l)."""
+    def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None):
+        """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l).
+        tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring)."""
         dt = getattr(model, "compute_dtype", torch.float32)
         if dt is hip_ops.F16S or exact_filter:
             raise ValueError("MutableCorpusIndex: no exact-rank mode (an ops.F16S model / exact_filter=True) -- its certificate "
@@ -175,16 +388,34 @@ class MutableCorpusIndex(CorpusIndex):
                 not _lib.load().xml_q2c_tile_rows_l2norm_ok(h, hip_ops.dt_of(act)):
             raise ValueError("MutableCorpusIndex: xml_index_put_rows takes f32 / bf16 rows of up to 128 clips and a hidden size "
                              "of whole 64-byte slices; got %s, lpad %d, hidden %d" % (act, lpad, h))
+        blocks = None
+        if tiles is not None:
+            if isinstance(tiles, bool) or int(tiles) != tiles or int(tiles) <= 0:
+                raise ValueError("MutableCorpusIndex: tiles must be a positive number of 256-row tiles, got %r" % (tiles,))
+            if lpad != 128 or not hip_ops.q2c_tiled_ok(lpad, h, act):
+                raise ValueError("MutableCorpusIndex: the packed form (tiles=%d) needs the tiled K6 operand -- 128-clip slots and "
+                                 "f32 / bf16 rows the tiled kernel takes; got %s, lpad %d, hidden %d.  Use tiles=None"
+                                 % (tiles, act, lpad, h))
+            blocks = BlockTable(tiles)
         dev = next(model.parameters()).device
         mods = [n for n, u in (("video", model.use_video), ("sub", model.use_sub)) if u]
         cap = table.capacity
         self = object.__new__(cls)
         feat2 = {m: torch.zeros((cap, lpad, h), dtype=act, device=dev) for m in mods}
         mask = {m: torch.zeros((cap, lpad), dtype=torch.float32, device=dev) for m in mods}
-        self.mask_bits = {m: torch.zeros((cap, 4), dtype=torch.int32, device=dev) for m in mods}
+        self.blocks, self.codes = blocks, None
+        n_words = cap if blocks is None else 2 * blocks.n_tiles
+        self.mask_bits = {m: torch.zeros((n_words, 4), dtype=torch.int32, device=dev) for m in mods}
         feat1n = {}
+        if blocks is not None:                          # the packed image: every block unused, K6 skips all of them
+            self.codes = torch.full((2 * blocks.n_tiles, 8), -2, dtype=torch.int32, device=dev)
+            plan = _TablePlan(blocks, self.codes, cap)
         for m in mods:
-            if hip_ops.q2c_tiled_ok(lpad, h, act):      # the plain two-slots-per-tile image; K6 in mask-bit mode, always
+            if blocks is not None:
+                data = torch.zeros(hip_ops.q2c_tiled_numel(blocks.n_tiles * 256, h, act), dtype=act, device=dev)
+                feat1n[m] = hip_ops.TiledRows(data, cap * lpad, h, (cap, lpad, h), all_valid=False)
+                feat1n[m].mask_bits, feat1n[m].plan = self.mask_bits[m], plan
+            elif hip_ops.q2c_tiled_ok(lpad, h, act):    # the plain two-slots-per-tile image; K6 in mask-bit mode, always
                 data = torch.zeros(hip_ops.q2c_tiled_numel(cap * lpad, h, act), dtype=act, device=dev)
                 feat1n[m] = hip_ops.TiledRows(data, cap * lpad, h, (cap, lpad, h), all_valid=False)
                 feat1n[m].mask_bits = self.mask_bits[m]
@@ -201,14 +432,16 @@ class MutableCorpusIndex(CorpusIndex):
         return self
 
     @classmethod
-    def from_batches(cls, model, context_batches, capacity, l_ref=None, ids=None, **kw):
-        """create + one add per (video_feat, video_mask, sub_feat, sub_mask) batch; ids: the videos' ids, in order."""
+    def from_batches(cls, model, context_batches, capacity, l_ref=None, ids=None, n_clips=None, **kw):
+        """create + one add per (video_feat, video_mask, sub_feat, sub_mask) batch; ids: the videos' ids, in order; n_clips:
+        their valid lengths, in order (the packed form, tiles=N; None: read from the masks, one host read per batch)."""
         self = cls.create(model, capacity, l_ref, **kw)
         ids = None if ids is None else _int_list(ids, "ids")
+        n_clips = None if n_clips is None else _int_list(n_clips, "n_clips")
         r = 0
         for vf, vm, sf, sm in context_batches:
             b = int((vf if vf is not None else sf).shape[0])
-            self.add(vf, vm, sf, sm, ids=None if ids is None else ids[r:r + b])
+            self.add(vf, vm, sf, sm, ids=None if ids is None else ids[r:r + b], n_clips=None if n_clips is None else n_clips[r:r + b])
             r += b
         return self
 
@@ -222,7 +455,7 @@ class MutableCorpusIndex(CorpusIndex):
         return self.table.slot_of(vid)
 
     def hbm_bytes(self):
-        extra = list(self.mask_bits.values()) + [self.vlen, self.live, self.slot_ids]
+        extra = list(self.mask_bits.values()) + [self.vlen, self.live, self.slot_ids] + ([] if self.codes is None else [self.codes])
         return CorpusIndex.hbm_bytes(self) + sum(t.numel() * t.element_size() for t in extra)
 
     # ---- updates --------------------------------------------------------------------------------------------------------
@@ -255,10 +488,32 @@ class MutableCorpusIndex(CorpusIndex):
         enc = dict(video=(v1, v2, video_mask), sub=(s1, s2, sub_mask))
         return {m: enc[m] for m in self.modalities}
 
-    def put(self, slots, enc, ids=None):
+    @staticmethod
+    def _valid_lengths(masks):
+        """(last valid clip + 1) over the modalities' (b, lb) masks as host integers: one small device -> host copy that waits
+        for the stream -- the one synchronising path of an update (pass n_clips= to avoid it)."""
+        pos = None
+        for mk in masks:
+            last = ((mk != 0).to(torch.int32) * torch.arange(1, mk.shape[1] + 1, device=mk.device, dtype=torch.int32)).amax(1)
+            pos = last if pos is None else torch.maximum(pos, last)
+        return pos.cpu().tolist()
+
+    @staticmethod
+    def _n_blocks(n_clips, b, what):
+        """Blocks per video of a batch in the packed image from its valid lengths (host integers)."""
+        n_clips = _int_list(n_clips, what + ": n_clips")
+        if len(n_clips) != b:
+            raise ValueError("%s: %d valid lengths (n_clips) for %d videos" % (what, len(n_clips), b))
+        try:
+            return [blocks_of(n) for n in n_clips]
+        except ValueError as e:
+            raise ValueError("%s: %s" % (what, e))
+
+    def put(self, slots, enc, ids=None, n_clips=None):
         """Write an ENCODED batch, enc[m] = (feat1, feat2, mask) of (b, lb <= l_ref) rows as model.encode_context returns them,
         into the b distinct slots; a live slot is replaced, a free one becomes live.  ids=None keeps / assigns ids as
-        SlotTable.check_put says.  Returns the slots."""
+        SlotTable.check_put says.  n_clips (the packed form; ignored by the plain one): the videos' valid lengths, class
+        docstring -- a mask that is longer than its n_clips rounded up to whole blocks is cut there.  Returns the slots."""
         slots, ids = self.table.check_put(slots, ids)
         mods = self.modalities
         if set(enc) != set(mods):
@@ -267,6 +522,31 @@ class MutableCorpusIndex(CorpusIndex):
             a1, a2, am = enc[m]
             if a1.shape[0] != len(slots) or a1.shape[1] > self.l_ref:
                 raise ValueError("put: %d slots and l_ref = %d for a batch of shape %s" % (len(slots), self.l_ref, tuple(a1.shape)))
+        if self.blocks is not None:
+            b = len(slots)
+            for m in mods:      # everything the put launch could refuse, before the clear launch of the moving videos
+                a1, a2, am = enc[m]
+                want = (b, a1.shape[1], self.feat2[m].shape[2])
+                if not (a1.is_cuda and a2.is_cuda and am.is_cuda) or a1.dtype != self.feat2[m].dtype or a2.dtype != a1.dtype or \
+                        tuple(a1.shape) != want or tuple(a2.shape) != want or tuple(am.shape) != want[:2]:
+                    raise ValueError("put: %s rows (b, lb, %d) of %s on the device and a (b, lb) mask expected"
+                                     % (m, want[2], self.feat2[m].dtype))
+            nbs = self._n_blocks(self._valid_lengths([enc[m][2] for m in mods]) if n_clips is None else n_clips, b, "put")
+            runs, clears = self.blocks.check_put(slots, nbs)
+            if clears:     # videos that move: their old runs become unused blocks BEFORE the put, whose runs may reuse them
+                hip_ops.index_clear_rows_packed(self._to_device([-1] * len(clears)), self._to_device(clears), 8,
+                                                [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], self.codes,
+                                                self.vlen, self.live.view(-1), self.l_ref)
+            rec = self._to_device(slots + ids + [x for r in runs for x in r])
+            hip_ops.index_put_rows_packed([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
+                                          [enc[m][2].float().contiguous() for m in mods], rec[:b], rec[b:2 * b],
+                                          rec[2 * b:].view(b, 2), max(nbs), [self.feat1n[m] for m in mods],
+                                          [self.feat2[m] for m in mods], [self.mask[m] for m in mods],
+                                          [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.slot_ids,
+                                          self.live.view(-1), self.l_ref)
+            self.blocks.commit_put(slots, runs)
+            self.table.commit_put(slots, ids)
+            return slots
         both = self._to_device([slots, ids])
         hip_ops.index_put_rows([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
                                [enc[m][2].float().contiguous() for m in mods], both[0], both[1],
@@ -275,26 +555,49 @@ class MutableCorpusIndex(CorpusIndex):
         self.table.commit_put(slots, ids)
         return slots
 
-    def add(self, video_feat, video_mask, sub_feat, sub_mask, ids=None):
-        """Encode a context batch and store its videos in the lowest free slots; returns the slots (a list, batch order)."""
+    def _room(self, slots, masks, n_clips, b, what):
+        """The packed form: refuse a batch that finds no runs BEFORE it is encoded; returns n_clips for put (the lengths read
+        from the masks, so that they are read once)."""
+        if self.blocks is None:
+            return None
+        if n_clips is None:
+            n_clips = self._valid_lengths([mk for m, mk in zip(("video", "sub"), masks) if m in self.modalities])
+        self.blocks.check_put(slots, self._n_blocks(n_clips, b, what), what)
+        return n_clips
+
+    def add(self, video_feat, video_mask, sub_feat, sub_mask, ids=None, n_clips=None):
+        """Encode a context batch and store its videos in the lowest free slots; returns the slots (a list, batch order).
+        n_clips: put."""
         b = self._check_batch(video_feat, video_mask, sub_feat, sub_mask, "add")
         slots, ids = self.table.check_add(b, ids)
-        return self.put(slots, self.encode(video_feat, video_mask, sub_feat, sub_mask), ids)
+        n_clips = self._room(slots, (video_mask, sub_mask), n_clips, b, "add")
+        return self.put(slots, self.encode(video_feat, video_mask, sub_feat, sub_mask), ids, n_clips)
 
-    def replace(self, slots, video_feat, video_mask, sub_feat, sub_mask, ids=None, new_ids=None):
+    def replace(self, slots, video_feat, video_mask, sub_feat, sub_mask, ids=None, new_ids=None, n_clips=None):
         """Encode a context batch over the LIVE slots named by `slots` (or, slots=None, by ids=); the videos keep their ids
-        unless new_ids gives others.  Returns the slots."""
+        unless new_ids gives others.  The packed form: a video whose block count does not change keeps its run, any other
+        moves (its old run is freed first).  n_clips: put.  Returns the slots."""
         slots = self.table.resolve(slots, ids, "replace")
         b = self._check_batch(video_feat, video_mask, sub_feat, sub_mask, "replace")
         if b != len(slots):
             raise ValueError("replace: %d slots for a batch of %d videos" % (len(slots), b))
         slots, new_ids = self.table.check_put(slots, new_ids, "replace")
-        return self.put(slots, self.encode(video_feat, video_mask, sub_feat, sub_mask), new_ids)
+        n_clips = self._room(slots, (video_mask, sub_mask), n_clips, b, "replace")
+        return self.put(slots, self.encode(video_feat, video_mask, sub_feat, sub_mask), new_ids, n_clips)
 
     def remove(self, slots=None, ids=None):
-        """Free the LIVE slots named by `slots` (or by ids=): searches enqueued afterwards no longer see them.  Returns them."""
+        """Free the LIVE slots named by `slots` (or by ids=): searches enqueued afterwards no longer see them.  Returns them.
+        The packed form frees their runs too."""
         slots = self.table.resolve(slots, ids, "remove")
-        if slots:
+        if slots and self.blocks is not None:
+            mods = self.modalities
+            runs = self.blocks.check_remove(slots)
+            hip_ops.index_clear_rows_packed(self._to_device(slots), self._to_device(runs), 8, [self.mask[m] for m in mods],
+                                            [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.live.view(-1),
+                                            self.l_ref)
+            self.blocks.commit_remove(slots)
+            self.table.commit_remove(slots)
+        elif slots:
             mods = self.modalities
             hip_ops.index_clear_rows(self._to_device(slots), [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods],
                                      self.vlen, self.live.view(-1), self.l_ref)

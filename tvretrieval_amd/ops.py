@@ -1421,3 +1421,79 @@ def index_clear_rows(slots, imask, bits, vlen, live, l_ref):
     check(_lib.load().xml_index_clear_rows(n_mod, _p(slots), int(slots.numel()), _p(imask[0]), _p(bits[0]), sec(imask), sec(bits),
                                            _p(vlen), _p(live), int(cap), int(lpad), int(l_ref), _stream()),
           "xml_index_clear_rows")
+
+
+# ---- the same on the packed K6 image (include/xmlhip_index.h; MutableCorpusIndex(tiles=N)) ------------------------------------
+def _packed_sides(k6, feat2, imask, bits, codes):
+    """Checks the index tensors of the two packed update entries; returns (capacity, hidden, n_tiles, k6 buffers or None)."""
+    n_mod = len(imask)
+    if n_mod not in (1, 2) or len(bits) != n_mod or (k6 is not None and not (len(k6) == len(feat2) == n_mod)):
+        raise _lib.XmlHipError("packed index update: 1 or 2 modalities, the same number of k6 / feat2 / mask / bits tensors")
+    _req(codes, "codes", torch.int32)
+    if codes.dim() != 2 or codes.shape[1] != 8 or codes.shape[0] % 2 or not codes.shape[0]:
+        raise _lib.XmlHipError("packed index update: codes (2 * n_tiles, 8) int32 expected")
+    n_tiles, cap = int(codes.shape[0]) // 2, int(imask[0].shape[0])
+    hidden, data = None, None
+    for m in range(n_mod):
+        _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
+        if tuple(imask[m].shape) != (cap, 128) or tuple(bits[m].shape) != (2 * n_tiles, 4):
+            raise _lib.XmlHipError("packed index update: mask (capacity, 128) and bits (2 * n_tiles, 4) expected")
+    if k6 is not None:
+        hidden, data = int(feat2[0].shape[2]), []
+        for m in range(n_mod):
+            _req(feat2[m], "feat2", feat2[0].dtype)
+            if tuple(feat2[m].shape) != (cap, 128, hidden) or not isinstance(k6[m], TiledRows):
+                raise _lib.XmlHipError("packed index update: feat2 (capacity, 128, H) and a TiledRows K6 operand expected")
+            d = k6[m].data
+            _req(d, "k6", feat2[0].dtype)
+            if not q2c_tiled_ok(128, hidden, d.dtype) or d.numel() != q2c_tiled_numel(n_tiles * 256, hidden, d.dtype):
+                raise _lib.XmlHipError("packed index update: the tile image does not hold n_tiles * 256 rows of H = %d" % hidden)
+            data.append(d)
+    return cap, hidden, n_tiles, data
+
+
+def _packed_records(slots, runs, what):
+    _req(slots, "slots", torch.int32); _req(runs, "runs", torch.int32)
+    n = int(slots.numel())
+    if tuple(runs.shape) != (n, 2) or not n:
+        raise _lib.XmlHipError("%s: one slot and one (first block, blocks) run per video" % what)
+    return n
+
+
+def index_put_rows_packed(f1, f2, masks, slots, ids, runs, nb_max, k6, feat2, imask, bits, codes, vlen, slot_ids, live, l_ref):
+    """xml_index_put_rows_packed: one encoded context batch into its slots AND its runs of the packed K6 image, one launch,
+    nothing read back.  f1 / f2 / masks, slots, ids as ops.index_put_rows; runs (b, 2) int32 device = (first block, blocks)
+    per video, handed out by index_update.BlockTable; nb_max: the longest run of the call (1..8).  k6: per-modality TiledRows
+    over n_tiles * 256 rows; bits: per-modality (2 * n_tiles, 4) packed mask words; codes (2 * n_tiles, 8) int32."""
+    cap, hidden, n_tiles, data = _packed_sides(k6, feat2, imask, bits, codes)
+    _index_state(vlen, live, cap, slot_ids)
+    n_mod = len(feat2)
+    if not (len(f1) == len(f2) == len(masks) == n_mod):
+        raise _lib.XmlHipError("index_put_rows_packed: the batch holds %d modalities, the index %d" % (len(f1), n_mod))
+    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
+    for m in range(n_mod):
+        _req(f1[m], "f1", feat2[0].dtype); _req(f2[m], "f2", feat2[0].dtype); _req(masks[m], "mask", torch.float32)
+        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
+            raise _lib.XmlHipError("index_put_rows_packed: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected")
+    if _packed_records(slots, runs, "index_put_rows_packed") != b or (ids is not None and _req(ids, "ids", torch.int32).numel() != b):
+        raise _lib.XmlHipError("index_put_rows_packed: one slot, run (and id) per video of the batch")
+    j = n_mod - 1
+    sec = (lambda t: _p(t[j])) if n_mod == 2 else (lambda t: None)
+    check(_lib.load().xml_index_put_rows_packed(
+        n_mod, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), _p(runs), b, lb, int(nb_max),
+        _p(data[0]), _p(feat2[0]), _p(imask[0]), _p(bits[0]), sec(data), sec(feat2), sec(imask), sec(bits), _p(codes),
+        _p(vlen), _p(slot_ids), _p(live), cap, n_tiles, 128, int(l_ref), hidden, dt_of(feat2[0]), _stream()),
+        "xml_index_put_rows_packed")
+
+
+def index_clear_rows_packed(slots, runs, nb_max, imask, bits, codes, vlen, live, l_ref):
+    """xml_index_clear_rows_packed: n records (slot, run): the run's codes become -2 and its mask bits 0; the slot is freed as
+    ops.index_clear_rows frees it, unless it is -1 (the run alone: a replace that moves its video).  One launch."""
+    cap, _, n_tiles, _ = _packed_sides(None, None, imask, bits, codes)
+    _index_state(vlen, live, cap)
+    n = _packed_records(slots, runs, "index_clear_rows_packed")
+    sec = (lambda t: _p(t[1])) if len(imask) == 2 else (lambda t: None)
+    check(_lib.load().xml_index_clear_rows_packed(len(imask), _p(slots), _p(runs), n, int(nb_max), _p(imask[0]), _p(bits[0]),
+                                                  sec(imask), sec(bits), _p(codes), _p(vlen), _p(live), cap, n_tiles, 128,
+                                                  int(l_ref), _stream()),
+          "xml_index_clear_rows_packed")
