@@ -1,6 +1,6 @@
 """Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
 
-usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp] [--batch 200] [--reps 21] [--pass-reps 5]
+usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact] [--batch 200] [--reps 21] [--pass-reps 5]
                                           [--queries 10000] [--videos 21793] [--suite-wall "..."]
                                           [--out profiles/index_update_timing.md]
 
@@ -13,6 +13,10 @@ usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp] [--b
   c3r   the same on the ragged corpus with the real TVR clip counts (the price of giving up the length-bucketed image)
   putp  xml_index_put_rows_packed (the packed form, MutableCorpusIndex(tiles=N)) next to xml_index_put_rows on the same batch
   c3rp  the ragged corpus on three forms in one process: one-shot packed index, mutable index, packed mutable index
+  compact  (not in the default set) the packed mutable index on the ragged corpus at tiles = plan + 10 %, churned -- a random
+        10 % removed and re-added with freshly drawn TVR lengths until an add is refused or 20 rounds have passed -- then
+        compact(): the launches alone between HIP events, the whole call on the host clock, bytes moved, stats() and the
+        10 000-query pass before and after.  Run it together with putp to have the put kernel's rate from the same run
 
 Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
 same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
@@ -326,6 +330,138 @@ def packed_search_leg(args, lines):
     torch.cuda.empty_cache()
 
 
+def compact_leg(args, lines):
+    """Churn a packed mutable index on the ragged corpus until it is fragmented, then compact it (module docstring)."""
+    import bench
+    _, _, l, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3r"]
+    nv, nq = args.videos, args.queries
+    be = bench.HipBackend(0)
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), torch.bfloat16)
+    lens = bench.real_clip_counts(nv, l)
+    n_clips = [int(x) for x in lens.tolist()]
+    t_plan = ops.PackPlan([(torch.arange(l)[None] < lens[:, None]).float()]).n_tiles
+    need, _ = tiles_in_corpus_order(n_clips, bench.CHUNK)
+    tiles = max(-(-t_plan * 11 // 10), need)
+    rng = np.random.default_rng(20)
+    with torch.no_grad():
+        index = MutableCorpusIndex.from_batches(model, bench.context_batches(0, nv, l, dv, ds, True, True, be.device, lens=lens),
+                                                nv, l_ref=l, n_clips=n_clips, tiles=tiles)
+        qf, qm = bench.synth_queries(nq, dq, be.device)
+        kw = dict(n_valid_tokens=int(qm.sum().item()))
+        search = lambda: inf.vcmr_search(model, index, qf, qm, **kw)      # noqa: E731
+        keys = ("top_indices", "top_scores", "flat_indices", "flat_scores")
+        k = nv // 10
+
+        def churn(max_rounds):
+            """-> (rounds done, the refusal or None)"""
+            for rnd in range(max_rounds):
+                index.remove([int(s) for s in rng.choice(index.table.live_slots(), k, replace=False)])
+                new = torch.from_numpy(rng.choice(lens.numpy(), k))
+                try:
+                    at = 0
+                    for batch in bench.context_batches(0, k, l, dv, ds, True, True, be.device, lens=new):
+                        b = int(batch[0].shape[0])
+                        index.add(*batch, n_clips=[int(x) for x in new[at:at + b].tolist()])
+                        at += b
+                except ValueError as e:
+                    return rnd + 1, str(e)
+            return max_rounds, None
+
+        fresh = index.blocks.stats()
+        t_fresh = timed(search, args.pass_reps, 2)
+        # ---- first fragmentation: the launches of compact() alone, between HIP events (records uploaded beforehand)
+        rounds1, refusal1 = churn(20)
+        st_before = index.blocks.stats()
+        t_before = timed(search, args.pass_reps, 2)
+        want = {key: v.clone() for key, v in inf.vcmr_search(model, index, qf[:512], qm[:512]).items() if key in keys}
+        mods = index.modalities
+        t0 = time.perf_counter()
+        plan = index.blocks.check_compact()
+        plan_s = time.perf_counter() - t0
+        staged = []
+        for rnd in plan:
+            recs, clears = rnd["records"], rnd["clears"]
+            dev = index._to_device([x for r in recs for x in r] + [-1] * len(clears) + [x for r in clears for x in r])
+            staged.append((dev, 17 * len(recs), len(clears)))
+        # warm-up: a record that keeps every block of tile 0 (the first launch of a kernel is not its steady state)
+        ops.index_move_blocks_packed(index._to_device([0] + [-1] * 16).view(1, 17), [index.feat1n[m] for m in mods],
+                                     [index.mask_bits[m] for m in mods], index.codes)
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * len(staged) + 1)]
+        ev[0].record()
+        for i, (dev, n, c) in enumerate(staged):
+            ops.index_move_blocks_packed(dev[:n].view(-1, 17), [index.feat1n[m] for m in mods], [index.mask_bits[m] for m in mods],
+                                         index.codes)
+            ev[2 * i + 1].record()
+            if c:
+                ops.index_clear_rows_packed(dev[n:n + c], dev[n + c:].view(c, 2), 8, [index.mask[m] for m in mods],
+                                            [index.mask_bits[m] for m in mods], index.codes, index.vlen, index.live.view(-1), l)
+            ev[2 * i + 2].record()
+        torch.cuda.synchronize()
+        index.blocks.commit_compact(plan)
+        per_round = [ev[2 * i].elapsed_time(ev[2 * i + 2]) for i in range(len(staged))]
+        move_only = [ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(len(staged))]
+        moved = [sum(nb for (_, nb), _ in rnd["moves"].values()) for rnd in plan]
+        row_bytes = sum(index.feat2[m].shape[2] * index.feat2[m].element_size() for m in mods)
+        nbytes = [mv * 16 * row_bytes for mv in moved]
+        st_after = index.blocks.stats()
+        t_after = timed(search, args.pass_reps, 2)
+        got = inf.vcmr_search(model, index, qf[:512], qm[:512])
+        same = all(bool(torch.equal(want[key], got[key])) for key in keys)
+        # ---- second fragmentation: the whole compact() call as a caller sees it
+        rounds2, refusal2 = churn(20)
+        st2_before = index.blocks.stats()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        res = index.compact()
+        e1.record()
+        torch.cuda.synchronize()
+        call_ms, call_ev = (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1)
+        st2_after = index.blocks.stats()
+    tot_ms, tot_b = sum(per_round), sum(nbytes)
+    show = lambda st: ", ".join("%s %d" % (key, st[key]) for key in      # noqa: E731
+                                ("free_blocks", "largest_free_run", "largest_free_run_partial", "tiles_empty", "tiles_partial",
+                                 "tiles_full", "tiles_used", "straddles"))
+    lines += ["", "## Compaction of the packed mutable index (compact leg)", "",
+              "%d videos, real TVR clip counts, hidden %d, bf16, two modalities; the one-shot plan needs %d tiles, the index has "
+              "`tiles=%d` (plan + 10 %%; filling in corpus order needs %d).  Churn: a random 10 %% (%d videos) removed and re-added "
+              "with lengths drawn afresh from the TVR counts, until an add is refused or 20 rounds have passed."
+              % (nv, hidden, t_plan, tiles, need, k), "",
+              "First churn: %d rounds, %s.  Then the launches of `compact()` alone, records uploaded beforehand, between HIP events "
+              "(host planning, `check_compact`: %.1f ms):" % (rounds1, "refused: `%s`" % refusal1 if refusal1 else "no add refused", plan_s * 1e3),
+              "", "| round | records (tiles touched) | runs cleared | blocks moved | image bytes moved | move launch | move + clear launches | payload rate | read + written |",
+              "|---|---|---|---|---|---|---|---|---|"]
+    for i, rnd in enumerate(plan):
+        rate = nbytes[i] / (move_only[i] * 1e-3) / 1e12 if move_only[i] > 0 else 0.0      # of the move launch alone
+        lines.append("| %d | %d | %d | %d | %.1f MB | %.1f us | %.1f us | %.2f TB/s | %.2f TB/s |"
+                     % (i + 1, len(rnd["records"]), len(rnd["clears"]), moved[i], nbytes[i] / 1e6, move_only[i] * 1e3,
+                        per_round[i] * 1e3, rate, 2 * rate))
+    if plan:
+        mv_ms = sum(move_only)
+        lines.append("| all | | | %d | %.1f MB | %.1f us | %.1f us | %.2f TB/s | %.2f TB/s |"
+                     % (sum(moved), tot_b / 1e6, mv_ms * 1e3, tot_ms * 1e3, tot_b / (mv_ms * 1e-3) / 1e12,
+                        2 * tot_b / (mv_ms * 1e-3) / 1e12))
+    lines += ["", "The rates are image bytes over the move launch alone (one event pair around a single launch: a single sample, "
+              "event resolution included); `read + written` counts every moved byte twice, as the put kernel's rows above do."]
+    lines += ["", "`stats()` freshly filled: %s." % show(fresh), "", "`stats()` before: %s." % show(st_before), "",
+              "`stats()` after: %s." % show(st_after), "",
+              "| %d-query pass (vcmr_search) | time |" % nq, "|---|---|", "| freshly filled | %s |" % fmt(t_fresh),
+              "| churned, before compaction | %s |" % fmt(t_before), "| after compaction | %s |" % fmt(t_after), "",
+              "First 512 queries before against after compaction (video lists, scores, moments): %s."
+              % ("identical" if same else "NOT identical"), "",
+              "Second churn: %d rounds, %s.  The whole `index.compact()` call: %.1f ms on the host clock around a device synchronise, "
+              "%.1f ms between HIP events around the call (planning and enqueueing included); it returned %s.  `stats()` before: "
+              "%s; after: %s." % (rounds2, "refused: `%s`" % refusal2 if refusal2 else "no add refused", call_ms, call_ev,
+                                  ", ".join("%s %s" % kv for kv in sorted(res.items())), show(st2_before), show(st2_after))]
+    for ln in lines[-26:]:
+        print(ln, flush=True)
+    del index
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="put,putp,e2e,c3,c3r,c3rp")
@@ -356,6 +492,8 @@ def main():
             search_leg(name, args, lines)
     if "c3rp" in legs:
         packed_search_leg(args, lines)
+    if "compact" in legs:
+        compact_leg(args, lines)
     if args.suite_wall:
         lines += ["", "## GPU test wall time", "", args.suite_wall]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -248,12 +248,17 @@ SIGNATURES_INDEX = {
     "xml_index_clear_rows_packed": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
 }
 
+# the companion header include/xmlhip_index_compact.h (tests/test_index_compact_capi.py checks): compaction of the packed image
+SIGNATURES_COMPACT = {
+    "xml_index_move_blocks_packed": (c_int, [c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+}
+
 _lib = None
 
 
 def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -5,7 +5,8 @@
                        (ops.index_put_rows / ops.index_clear_rows) that reads nothing back and re-allocates nothing
   BlockTable           the host side of the packed form (create(..., tiles=N)): which run of 16-row blocks of the packed K6
                        image each live slot owns (ops.index_put_rows_packed / ops.index_clear_rows_packed keep the image,
-                       its code table and its mask words in step)
+                       its code table and its mask words in step); check_compact / commit_compact plan the moves that
+                       MutableCorpusIndex.compact() enqueues (ops.index_move_blocks_packed)
 
 Slot numbers are what top_indices, flat_indices, video_allow bits, svmr_video and explain_moments pairs mean on such an
 index.  A search sees `live AND video_allow` (inference.stage_video_topk), i.e. by the definition of a restricted search the
@@ -153,6 +154,16 @@ def blocks_of(n_clips):
     return max((n + 15) // 16, 1)
 
 
+class NoRunError(ValueError):
+    """BlockTable.check_put found no free run for a video.  blocks_asked: the blocks of the call's videos that need a run;
+    blocks_free: the free blocks once the call's moving videos have left theirs -- when blocks_free >= blocks_asked the space
+    may exist without being contiguous, and compaction can help."""
+
+    def __init__(self, message, blocks_asked, blocks_free):
+        ValueError.__init__(self, message)
+        self.blocks_asked, self.blocks_free = int(blocks_asked), int(blocks_free)
+
+
 class BlockTable(object):
     """Host bookkeeping of the packed K6 image of a MutableCorpusIndex(tiles=N): n_tiles tiles of 16 blocks (16 clip rows
     each).  A live slot owns one RUN of nb consecutive blocks inside one tile; a run may cross the boundary between blocks 7
@@ -291,8 +302,12 @@ class BlockTable(object):
             first = self._place(nb)
             if first is None:
                 err = ("%s: no room for a video of %d blocks (%d clip rows) in the packed K6 image: %d free blocks of %d, the "
-                       "largest free run holds %d (tiles=%d; the image is not compacted and does not grow)"
+                       "largest free run holds %d (tiles=%d; compact() gathers the free blocks of the tiles, the image does "
+                       "not grow)"
                        % (what, nb, nb * 16, self.free_blocks, self.n_tiles * 16, self.largest_free_run(), self.n_tiles))
+                # what the call asks for against what is free once its moving videos have left their runs
+                asked = sum(n for s2, n in zip(slots, n_blocks) if s2 not in self._run or s2 in taken)
+                free = self.free_blocks + sum(self._run[s2][1] for s2 in taken)
                 break
             self._take(first, nb, s)
             taken.append(s)
@@ -302,7 +317,7 @@ class BlockTable(object):
         for s, (first, nb) in reversed(moved):
             self._take(first, nb, s)
         if err is not None:
-            raise ValueError(err)
+            raise NoRunError(err, asked, free)
         return runs, [r for _, r in moved]
 
     def commit_put(self, slots, runs):
@@ -323,6 +338,111 @@ class BlockTable(object):
     def commit_remove(self, slots):
         for s in slots:
             self._release(s)
+
+    # ---- compaction ---------------------------------------------------------------------------------
+    def check_compact(self):
+        """A plan that makes the free blocks of every partial tile one run at its end and empties the tiles whose videos fit
+        into the ends of others; changes nothing.  The plan is a list of ROUNDS, each a dict
+          records  one [tile, src[0..15]] per touched tile: the operand of ONE xml_index_move_blocks_packed launch
+                   (src >= 0: the block received, -1: stays, -2: becomes unused); its launch contract holds
+          clears   the (first, nb) runs vacated in OTHER tiles: ONE xml_index_clear_rows_packed launch (slot -1) behind it
+          moves    {slot: ((first, nb) before, (first, nb) after)} of the round, for commit_compact
+        Policy per round (deterministic).  Donors: the partial tiles in order of fewest used blocks, ties to the highest tile;
+        all runs of a tile, largest first (ties: lowest slot), are placed tentatively into the space other partial tiles have
+        at their END once slid -- best fit: the smallest such tail that holds the run, ties to the lowest tile; never into an
+        empty tile, a donor or the tile itself; if every run fits the tile is a donor and the moves are taken, else none of
+        them.  A receiver is never a donor of the same round.  Slide: every other partial tile whose runs are not packed at
+        its start gets them slid left in block order, received runs behind them; one record per touched tile, none for a
+        donor (its blocks are sources).  Rounds repeat on the resulting state until one finds no donor and nothing to slide;
+        a round with a donor empties a tile and nothing is ever placed into an empty tile, so this ends.  An empty plan is []."""
+        tiles = {}                                                # tile -> [(first, nb, slot)] in block order
+        for slot, (first, nb) in self._run.items():
+            tiles.setdefault(first >> 4, []).append((first, nb, slot))
+        for runs in tiles.values():
+            runs.sort()
+        plan = []
+        while True:
+            used = {t: sum(nb for _, nb, _ in runs) for t, runs in tiles.items()}
+            partial = [t for t in tiles if 0 < used[t] < 16]
+            tail = {t: 16 - used[t] for t in partial}             # free blocks at the end of a tile once it is slid
+            donors, received = set(), {}                          # received: tile -> [(first, nb, slot)] in order of placement
+            by_size = [[] for _ in range(16)]                     # tail length -> sorted tiles that have it (0: no target)
+            for t in sorted(partial):
+                by_size[tail[t]].append(t)
+
+            def resize(u, size):                                  # tile u's tail is `size` blocks from now on
+                del by_size[tail[u]][bisect.bisect_left(by_size[tail[u]], u)]
+                bisect.insort(by_size[size], u)
+                tail[u] = size
+
+            for t in sorted(partial, key=lambda t: (used[t], -t)):
+                if t in received:
+                    continue
+                own = tail[t]
+                resize(t, 0)                                      # not a target of its own runs; of nobody's once a donor
+                got = []
+                for first, nb, slot in sorted(tiles[t], key=lambda r: (-r[1], r[2])):
+                    size = next((n for n in range(nb, 16) if by_size[n]), None)      # best fit, then the lowest tile
+                    if size is None:
+                        break
+                    u = by_size[size][0]
+                    resize(u, size - nb)
+                    got.append((u, (first, nb, slot)))
+                if len(got) < len(tiles[t]):                      # not all of it fits: nothing of it is taken
+                    for u, (_, nb, _) in reversed(got):
+                        resize(u, tail[u] + nb)
+                    resize(t, own)
+                    continue
+                donors.add(t)
+                for u, run in got:
+                    received.setdefault(u, []).append(run)
+            records, moves = [], {}
+            for t in sorted(partial):
+                if t in donors:
+                    continue
+                src, at = [-1] * 16, 0
+                for first, nb, slot in tiles[t] + received.get(t, []):
+                    new = t * 16 + at
+                    if new != first:
+                        src[at:at + nb] = range(first, first + nb)
+                        moves[slot] = ((first, nb), (new, nb))
+                    at += nb
+                if all(s == -1 for s in src):
+                    continue                                      # packed at its start already, and receives nothing
+                for b in range(at, 16):                           # blocks of its own runs behind the new end: unused now
+                    if self._owner_in(tiles[t], t * 16 + b):
+                        src[b] = -2
+                records.append([t] + src)
+            if not records:
+                break
+            clears = [(first, nb) for t in sorted(donors) for first, nb, _ in tiles[t]]
+            plan.append(dict(records=records, clears=clears, moves=moves))
+            for t in donors:
+                del tiles[t]
+            for t in list(tiles):
+                if 0 < used[t] < 16:
+                    at, out = 0, []
+                    for first, nb, slot in tiles[t] + received.get(t, []):
+                        out.append((t * 16 + at, nb, slot))
+                        at += nb
+                    tiles[t] = out
+        return plan
+
+    @staticmethod
+    def _owner_in(runs, block):
+        return any(first <= block < first + nb for first, nb, _ in runs)
+
+    def commit_compact(self, plan):
+        """Apply what check_compact returned (the table must be the one it was computed on)."""
+        for rnd in plan:
+            moves = rnd["moves"]
+            for slot, (old, _) in moves.items():
+                if self._run.get(slot) != old:
+                    raise ValueError("commit_compact: the table changed since check_compact (slot %d)" % slot)
+            for slot in moves:
+                self._release(slot)
+            for slot, (_, (first, nb)) in moves.items():
+                self._take(first, nb, slot)
 
 
 class _TablePlan(object):
@@ -358,16 +478,19 @@ class MutableCorpusIndex(CorpusIndex):
     before the value (topk.hip); explain_moments' q2c of a pair that names a free slot is unspecified too.
     Updates take the videos' valid lengths (last valid clip + 1 over the modalities) as n_clips=; without it they are read
     from the masks with one small device -> host copy, the one synchronising path of an update.  Given up, beyond what the
-    plain form gives up: a fragmented image is not compacted, `tiles` does not grow (an update that finds no run is refused),
-    K6 costs N tiles whatever the occupancy."""
+    plain form gives up: `tiles` does not grow (an update that finds no run is refused; compact() -- or auto_compact=True -- makes the free blocks
+    of the tiles contiguous first), K6 costs N tiles whatever the occupancy."""
 
     def __init__(self, *a, **kw):
         raise TypeError("use MutableCorpusIndex.create(model, capacity) or MutableCorpusIndex.from_batches(...)")
 
     @classmethod
-    def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None):
+    def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None,
+               auto_compact=False):
         """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l).
-        tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring)."""
+        tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring).
+        auto_compact (the packed form): an add / put / replace that finds no run although enough blocks are free runs
+        compact() once and tries again."""
         dt = getattr(model, "compute_dtype", torch.float32)
         if dt is hip_ops.F16S or exact_filter:
             raise ValueError("MutableCorpusIndex: no exact-rank mode (an ops.F16S model / exact_filter=True) -- its certificate "
@@ -403,7 +526,7 @@ class MutableCorpusIndex(CorpusIndex):
         self = object.__new__(cls)
         feat2 = {m: torch.zeros((cap, lpad, h), dtype=act, device=dev) for m in mods}
         mask = {m: torch.zeros((cap, lpad), dtype=torch.float32, device=dev) for m in mods}
-        self.blocks, self.codes = blocks, None
+        self.blocks, self.codes, self.auto_compact = blocks, None, bool(auto_compact) and blocks is not None
         n_words = cap if blocks is None else 2 * blocks.n_tiles
         self.mask_bits = {m: torch.zeros((n_words, 4), dtype=torch.int32, device=dev) for m in mods}
         feat1n = {}
@@ -532,7 +655,7 @@ class MutableCorpusIndex(CorpusIndex):
                     raise ValueError("put: %s rows (b, lb, %d) of %s on the device and a (b, lb) mask expected"
                                      % (m, want[2], self.feat2[m].dtype))
             nbs = self._n_blocks(self._valid_lengths([enc[m][2] for m in mods]) if n_clips is None else n_clips, b, "put")
-            runs, clears = self.blocks.check_put(slots, nbs)
+            runs, clears = self._find_runs(slots, nbs, "put")
             if clears:     # videos that move: their old runs become unused blocks BEFORE the put, whose runs may reuse them
                 hip_ops.index_clear_rows_packed(self._to_device([-1] * len(clears)), self._to_device(clears), 8,
                                                 [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], self.codes,
@@ -562,8 +685,58 @@ class MutableCorpusIndex(CorpusIndex):
             return None
         if n_clips is None:
             n_clips = self._valid_lengths([mk for m, mk in zip(("video", "sub"), masks) if m in self.modalities])
-        self.blocks.check_put(slots, self._n_blocks(n_clips, b, what), what)
+        self._find_runs(slots, self._n_blocks(n_clips, b, what), what)
         return n_clips
+
+    def _find_runs(self, slots, n_blocks, what):
+        """BlockTable.check_put; with auto_compact a refusal for lack of a RUN while enough blocks are free is answered by one
+        compact() and one more try."""
+        try:
+            return self.blocks.check_put(slots, n_blocks, what)
+        except NoRunError as e:
+            if not self.auto_compact or e.blocks_free < e.blocks_asked:
+                raise
+        self.compact()
+        try:
+            return self.blocks.check_put(slots, n_blocks, what)
+        except NoRunError as e:
+            raise NoRunError(str(e) + " after compaction", e.blocks_asked, e.blocks_free)
+
+    def compact(self):
+        """The packed form: move runs inside the image so that the free blocks of every partial tile are one run at its end,
+        and empty the tiles whose videos fit into the ends of others (BlockTable.check_compact).  Per
+        round one xml_index_move_blocks_packed launch and, when runs crossed tiles, one xml_index_clear_rows_packed launch
+        (slot -1) over the vacated runs, on the current stream; nothing is read back, no tensor is re-allocated, slots keep
+        their numbers, n_tiles and every pointer stay -- a captured GraphedVcmrSearch stays valid.  Returns what was done."""
+        if self.blocks is None:
+            raise ValueError("compact: the plain form (tiles=None) has nothing to compact -- every slot owns its 128 rows; "
+                             "only the packed form (create(..., tiles=N)) hands out runs of blocks")
+        mods = self.modalities
+        before = self.blocks.stats()
+        plan = self.blocks.check_compact()
+        for rnd in plan:
+            recs, clears = rnd["records"], rnd["clears"]
+            flat = [x for r in recs for x in r] + [-1] * len(clears) + [x for r in clears for x in r]
+            dev = self._to_device(flat)
+            n, c = 17 * len(recs), len(clears)
+            records, runs = dev[:n].view(-1, 17), dev[n + c:].view(c, 2)
+            # an entry takes 65535 records; a part of a launch that keeps the contract keeps it too (tiles are independent,
+            # cross-tile sources lie in donor tiles, which no record writes)
+            for i in range(0, len(recs), 65535):
+                hip_ops.index_move_blocks_packed(records[i:i + 65535], [self.feat1n[m] for m in mods],
+                                                 [self.mask_bits[m] for m in mods], self.codes)
+            for i in range(0, c, 65535):     # the runs vacated in other tiles: until here their slots' codes stood twice
+                hip_ops.index_clear_rows_packed(dev[n + i:n + min(i + 65535, c)], runs[i:i + 65535], 8,
+                                                [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], self.codes,
+                                                self.vlen, self.live.view(-1), self.l_ref)
+        self.blocks.commit_compact(plan)
+        after = self.blocks.stats()
+        moved = sum(nb for rnd in plan for (_, nb), _ in rnd["moves"].values())
+        row_bytes = sum(self.feat2[m].shape[2] * self.feat2[m].element_size() for m in mods)
+        return dict(rounds=len(plan), blocks_moved=moved, tiles_touched=len({r[0] for rnd in plan for r in rnd["records"]}),
+                    tiles_emptied=after["tiles_empty"] - before["tiles_empty"],
+                    largest_free_run_before=before["largest_free_run"], largest_free_run_after=after["largest_free_run"],
+                    bytes_moved=moved * 16 * row_bytes)
 
     def add(self, video_feat, video_mask, sub_feat, sub_mask, ids=None, n_clips=None):
         """Encode a context batch and store its videos in the lowest free slots; returns the slots (a list, batch order).

@@ -1497,3 +1497,36 @@ def index_clear_rows_packed(slots, runs, nb_max, imask, bits, codes, vlen, live,
                                                   sec(imask), sec(bits), _p(codes), _p(vlen), _p(live), cap, n_tiles, 128,
                                                   int(l_ref), _stream()),
           "xml_index_clear_rows_packed")
+
+
+def index_move_blocks_packed(records, k6, bits, codes):
+    """xml_index_move_blocks_packed (include/xmlhip_index_compact.h): n records (n, 17) int32 device = {tile, src[16]} -- block
+    b of the tile receives block src[b] (>= 0, any tile), stays (-1) or becomes unused (-2); image rows, codes and mask bits
+    move together, the per-slot state is no operand.  k6: per-modality TiledRows over n_tiles * 256 rows; bits: per-modality
+    (2 * n_tiles, 4) packed mask words; codes (2 * n_tiles, 8) int32.  One launch, nothing read back; the launch contract is
+    the caller's (index_update.BlockTable.check_compact)."""
+    n_mod = len(k6)
+    if n_mod not in (1, 2) or len(bits) != n_mod:
+        raise _lib.XmlHipError("index_move_blocks_packed: 1 or 2 modalities, one k6 image and one bits tensor each")
+    _req(codes, "codes", torch.int32)
+    if codes.dim() != 2 or codes.shape[1] != 8 or codes.shape[0] % 2 or not codes.shape[0]:
+        raise _lib.XmlHipError("index_move_blocks_packed: codes (2 * n_tiles, 8) int32 expected")
+    n_tiles = int(codes.shape[0]) // 2
+    _req(records, "records", torch.int32)
+    if records.dim() != 2 or records.shape[1] != 17 or not records.shape[0]:
+        raise _lib.XmlHipError("index_move_blocks_packed: records (n, 17) int32 = {tile, src[16]} expected")
+    data = []
+    for m in range(n_mod):
+        if not isinstance(k6[m], TiledRows) or not isinstance(k6[0], TiledRows):
+            raise _lib.XmlHipError("index_move_blocks_packed: a TiledRows K6 operand per modality expected")
+        d, hidden = k6[m].data, k6[0].hidden
+        _req(d, "k6", k6[0].data.dtype); _req(bits[m], "bits", torch.int32)
+        if k6[m].hidden != hidden or not q2c_tiled_ok(128, hidden, d.dtype) or \
+                d.numel() != q2c_tiled_numel(n_tiles * 256, hidden, d.dtype) or tuple(bits[m].shape) != (2 * n_tiles, 4):
+            raise _lib.XmlHipError("index_move_blocks_packed: tile images of n_tiles * 256 = %d rows of one hidden size and bits "
+                                   "(2 * n_tiles, 4) expected -- the same n_tiles as codes" % (n_tiles * 256))
+        data.append(d)
+    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    check(_lib.load().xml_index_move_blocks_packed(n_mod, _p(records), int(records.shape[0]), _p(data[0]), _p(bits[0]), sec(data),
+                                                   sec(bits), _p(codes), n_tiles, int(k6[0].hidden), dt_of(data[0]), _stream()),
+          "xml_index_move_blocks_packed")
