@@ -1,6 +1,6 @@
 """Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
 
-usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact] [--batch 200] [--reps 21] [--pass-reps 5]
+usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains] [--batch 200] [--reps 21] [--pass-reps 5]
                                           [--queries 10000] [--videos 21793] [--suite-wall "..."]
                                           [--out profiles/index_update_timing.md]
 
@@ -17,6 +17,12 @@ usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compa
         10 % removed and re-added with freshly drawn TVR lengths until an add is refused or 20 rounds have passed -- then
         compact(): the launches alone between HIP events, the whole call on the host clock, bytes moved, stats() and the
         10 000-query pass before and after.  Run it together with putp to have the put kernel's rate from the same run
+  chains  (not in the default set) the ragged corpus with the TVR clip counts, the fixture's last bin
+        (clipped at 128) spread over 128 .. 182 clips, at l_ref = --chains-l (128: 6 long videos; 100, the shape of
+        profiles/parts_timing.md: 121), overlap 16: the packed mutable index with part_overlap (long videos as chains of slots) next to the one without (the
+        videos cut at 128 clips), the 10 000-query pass on both; xml_chain_best_allow alone for 10 000 and 50 queries next to
+        xml_group_best_allow on the part table of the same videos and the same score matrix (capacity = parts, filled in
+        corpus order: slot p holds part p), and on the same chains over a random permutation of the slots
 
 Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
 same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
@@ -462,6 +468,128 @@ def compact_leg(args, lines):
     torch.cuda.empty_cache()
 
 
+def full_clip_counts(nv):
+    """bench.real_clip_counts with the histogram's last bin undone: the fixture is clipped at 128 clips and records the longest
+    video (182 clips), so the videos of that bin get lengths spread evenly over 128 .. 182."""
+    import bench
+    import json
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "tvr_clip_count_hist.json")))
+    lens = bench.real_clip_counts(nv, rec["clipped_at"]).clone()
+    last = torch.nonzero(lens == rec["clipped_at"]).view(-1)
+    lens[last] = torch.linspace(rec["clipped_at"], rec["max_unclipped"], last.numel()).round().to(lens.dtype)
+    return lens
+
+
+def chains_leg(args, lines):
+    """Long videos as chains of slots on the packed mutable index (module docstring)."""
+    import bench
+    from tvretrieval_amd.ingest import plan_parts
+    _, _, _, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3r"]
+    nv, nq, ov, l = args.videos, args.queries, 16, args.chains_l
+    be = bench.HipBackend(0)
+    dev = be.device
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), torch.bfloat16)
+    full = full_clip_counts(nv)
+    cut = torch.clamp(full, max=l)
+    table = plan_parts(full.numpy(), l, ov)
+    n_parts = table.n_parts
+    counts = np.diff(table.group_start)
+    part_len = torch.from_numpy(table.part_len.astype(np.int64))
+    tiles = max(tiles_in_corpus_order([int(x) for x in table.part_len], bench.CHUNK)[0],
+                tiles_in_corpus_order([int(x) for x in cut.tolist()], bench.CHUNK)[0])
+
+    def part_batches():
+        """(batch, its part table) for groups of ~bench.CHUNK - 64 videos; rows [r0, r1) of the synthetic corpus of parts"""
+        v0 = 0
+        while v0 < nv:
+            v1 = min(v0 + bench.CHUNK - 64, nv)
+            t = plan_parts(full[v0:v1].numpy(), l, ov)
+            r0 = int(table.group_start[v0])
+            pieces = list(bench.context_batches(r0, r0 + t.n_parts, l, dv, ds, True, True, dev, lens=part_len))
+            yield tuple(torch.cat([p[i] for p in pieces]) for i in range(4)), t
+            v0 = v1
+
+    with torch.no_grad():
+        t0 = time.perf_counter()
+        chained = MutableCorpusIndex.create(model, n_parts, l_ref=l, tiles=tiles, part_overlap=ov)
+        for batch, t in part_batches():
+            chained.add(*batch, parts=t)
+        torch.cuda.synchronize()
+        fill_s = time.perf_counter() - t0
+        plain = MutableCorpusIndex.from_batches(model, bench.context_batches(0, nv, l, dv, ds, True, True, dev, lens=cut), n_parts,
+                                                l_ref=l, n_clips=[int(x) for x in cut.tolist()], tiles=tiles)
+        assert chained.n_live == n_parts and chained.n_videos_live == nv == plain.n_live
+        assert chained.table.heads() == [int(x) for x in table.group_start[:-1]]           # slot p holds part p
+        qf, qm = bench.synth_queries(nq, dq, dev)
+        kw = dict(n_valid_tokens=int(qm.sum().item()))
+        passes = []
+        for rnd in ("", ", again"):
+            passes.append(("packed mutable index, videos cut at %d clips (no part_overlap)%s" % (l, rnd),
+                           timed(lambda: inf.vcmr_search(model, plain, qf, qm, **kw), args.pass_reps, 2)))
+            passes.append(("packed mutable index, part_overlap=%d%s" % (ov, rnd),
+                           timed(lambda: inf.vcmr_search(model, chained, qf, qm, **kw), args.pass_reps, 2)))
+        q2c = inf.vcmr_search(model, chained, qf, qm, **kw)["q2c"]
+        parts_dev = table.to(dev)
+        live = chained.live
+        # the same chains over a random permutation of the slots (what an index looks like after many updates)
+        perm = np.random.default_rng(0).permutation(n_parts)
+        head, nxt = np.arange(n_parts, dtype=np.int32), np.full(n_parts, -1, dtype=np.int32)
+        gs = table.group_start
+        for v in np.nonzero(counts > 1)[0]:
+            ch = perm[gs[v]:gs[v + 1]]
+            head[ch] = ch[0]
+            nxt[ch[:-1]] = ch[1:]
+        import types
+        scattered = types.SimpleNamespace(chain_head=torch.from_numpy(head).to(dev), chain_next=torch.from_numpy(nxt).to(dev),
+                                          max_parts=chained.max_parts)
+        all_videos = torch.full((1, (nv + 31) // 32), -1, dtype=torch.int32, device=dev)
+        want = ops.group_best_allow(q2c[:512], parts_dev, None)
+        same = bool(torch.equal(want, ops.chain_best_allow(q2c[:512], chained, live)))
+        folds = []
+        for rows in (nq, 50):
+            s = q2c[:rows]
+            for rnd in ("", ", again"):
+                folds += [(rows, "xml_group_best_allow, fixed part table (the yardstick)" + rnd,
+                           timed(lambda: ops.group_best_allow(s, parts_dev, None), args.reps)),
+                          (rows, "xml_group_best_allow with allow words over the videos" + rnd,
+                           timed(lambda: ops.group_best_allow(s, parts_dev, all_videos), args.reps)),
+                          (rows, "xml_chain_best_allow, slots in corpus order" + rnd,
+                           timed(lambda: ops.chain_best_allow(s, chained, live), args.reps)),
+                          (rows, "xml_chain_best_allow, the same chains over permuted slots" + rnd,
+                           timed(lambda: ops.chain_best_allow(s, scattered, live), args.reps))]
+    lines += ["", "## Long videos as chains of slots (chains leg)", "",
+              "%d videos with the TVR clip counts (the clipped last bin spread up to %d clips), l_ref = %d, part_overlap = %d: %d videos of more than %d "
+              "clips, %d parts = slots (capacity = parts, filled in corpus order in %.1f s, so slot p holds part p of the fixed part "
+              "table), hidden %d, bf16, %d queries, both packed indexes at tiles = %d.  Fold of the first 512 score rows, chain fold "
+              "against xml_group_best_allow: %s."
+              % (nv, int(full.max()), l, ov, int((counts > 1).sum()), l, n_parts, fill_s, hidden, nq, tiles,
+                 "identical" if same else "NOT identical"),
+              "", "| index | vcmr_search, %d queries |" % nq, "|---|---|"]
+    lines += ["| %s | %s |" % (n, fmt(t)) for n, t in passes]
+    a, b = (passes[0][1][0] + passes[2][1][0]) / 2, (passes[1][1][0] + passes[3][1][0]) / 2
+    lines += ["", "Price of the chains on this corpus (medians, mean of both rounds): %.2f ms -> %.2f ms per %d-query pass (%+.2f %%)."
+              % (a, b, nq, (b / a - 1) * 100), "", "| score rows | fold | time per call |", "|---|---|---|"]
+    lines += ["| %d | %s | %s |" % (r, n, fmt(t, "us")) for r, n, t in folds]
+    for rows in (nq, 50):
+        med = {}
+        for r, n, t in folds:
+            if r == rows:
+                med.setdefault(n.replace(", again", ""), []).append(t[0])
+        m = {k: sum(v) / len(v) for k, v in med.items()}
+        base = m["xml_group_best_allow, fixed part table (the yardstick)"]
+        lines += ["", "%d rows: chain fold over contiguous fold %.2f (corpus order), %.2f (permuted slots); %.1f us against %.1f us; "
+                  "the score matrix is %.1f MB, %.1f us at the %.1f TB/s stream rate."
+                  % (rows, m["xml_chain_best_allow, slots in corpus order"] / base,
+                     m["xml_chain_best_allow, the same chains over permuted slots"] / base,
+                     m["xml_chain_best_allow, slots in corpus order"] * 1e3, base * 1e3, rows * n_parts * 4 / 1e6,
+                     rows * n_parts * 4 / HBM_STREAM * 1e6, HBM_STREAM / 1e12)]
+    for ln in lines[-34:]:
+        print(ln, flush=True)
+    del chained, plain
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="put,putp,e2e,c3,c3r,c3rp")
@@ -470,6 +598,7 @@ def main():
     ap.add_argument("--queries", type=int, default=10000)
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--pass-reps", type=int, default=5)
+    ap.add_argument("--chains-l", type=int, default=128)
     ap.add_argument("--suite-wall", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_update_timing.md"))
     args = ap.parse_args()
@@ -494,6 +623,8 @@ def main():
         packed_search_leg(args, lines)
     if "compact" in legs:
         compact_leg(args, lines)
+    if "chains" in legs:
+        chains_leg(args, lines)
     if args.suite_wall:
         lines += ["", "## GPU test wall time", "", args.suite_wall]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -253,12 +253,21 @@ SIGNATURES_COMPACT = {
     "xml_index_move_blocks_packed": (c_int, [c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
 }
 
+# the companion header include/xmlhip_index_parts.h (tests/test_index_parts_capi.py checks): long videos as chains of slots
+SIGNATURES_PARTS = {
+    "xml_index_set_chains": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "xml_chain_best_allow": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int,
+                                     c_void_p, c_int64, c_void_p]),
+    "xml_chain_best_rows": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
 def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
+            list(SIGNATURES_PARTS.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

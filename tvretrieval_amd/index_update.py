@@ -3,6 +3,9 @@
   SlotTable            the host side: which of the `capacity` slots are live, the caller's id of each (no GPU needed)
   MutableCorpusIndex   a CorpusIndex of `capacity` slots allocated once; every update is a stream-ordered launch
                        (ops.index_put_rows / ops.index_clear_rows) that reads nothing back and re-allocates nothing
+  ChainTable           the SlotTable of an index created with part_overlap=O: a video longer than l_ref clips is a CHAIN of
+                       slots, one overlapping part each (ops.index_set_chains keeps the device tables chain_head / chain_next /
+                       chain_offset in step; searches fold a chain to its best part, ops.chain_best_allow)
   BlockTable           the host side of the packed form (create(..., tiles=N)): which run of 16-row blocks of the packed K6
                        image each live slot owns (ops.index_put_rows_packed / ops.index_clear_rows_packed keep the image,
                        its code table and its mask words in step); check_compact / commit_compact plan the moves that
@@ -143,6 +146,175 @@ class SlotTable(object):
             del self._slot[self._id[s]]
             self._id[s] = None
             heapq.heappush(self._free, s)
+
+
+class ChainTable(SlotTable):
+    """SlotTable of an index whose long videos are CHAINS of slots (MutableCorpusIndex.create(..., part_overlap=O); DESIGN.md
+    section 20c): a video of several parts takes one slot per part, every slot of it carries the video's id, and an id maps
+    to the HEAD slot (the part at offset 0), which is the video's number in results and in a caller's video_allow.  The table
+    mirrors the device tables chain_head / chain_next / chain_offset: a free slot and a video of one part are in the SINGLE
+    state (head = itself, next = -1, offset = 0).  A chain is added, replaced and removed whole; chains are built here from
+    free slots only, each slot once, so the tables never hold a cycle.
+    check_chains / check_remove_chains validate a whole call, change nothing and return a plan; commit_chains applies it once
+    the launches are enqueued.  plan["records"] is the operand of xml_index_set_chains: {slot, head, next, offset} of every
+    touched slot whose state changes.  SlotTable's own calls keep working for videos of one part and refuse a slot that is
+    a part of a longer video."""
+
+    def __init__(self, capacity, max_parts=32):
+        SlotTable.__init__(self, capacity)
+        max_parts = int(max_parts)
+        if max_parts < 1:
+            raise ValueError("ChainTable: max_parts must be >= 1, got %d" % max_parts)
+        self.max_parts = max_parts
+        self._head = list(range(self.capacity))       # the mirror of the device tables
+        self._next = [-1] * self.capacity
+        self._off = [0] * self.capacity
+
+    n_live = property(lambda self: self.capacity - len(self._free))
+    n_videos_live = property(lambda self: len(self._slot))
+
+    def state(self, slot):
+        """(head, next, offset) of a slot as the device tables hold it."""
+        return self._head[slot], self._next[slot], self._off[slot]
+
+    def head_of(self, slot):
+        if not self.is_live(slot):
+            raise ValueError("slot %r is free (or outside [0, %d))" % (slot, self.capacity))
+        return self._head[slot]
+
+    def chain_of(self, slot):
+        """The slots of the video that `slot` (any of its parts) belongs to, in offset order."""
+        s, out = self.head_of(slot), []
+        while s != -1:
+            out.append(s)
+            s = self._next[s]
+        return out
+
+    def heads(self):
+        return sorted(self._slot.values())
+
+    def resolve_videos(self, slots=None, ids=None, what="slots"):
+        """The head slots of the videos a call names, by any slot of each or by id: validated, one entry per video."""
+        if (slots is None) == (ids is None):
+            raise ValueError("%s: name the videos by slots or by ids=, not both" % what)
+        if ids is not None:
+            slots = [self.slot_of(v) for v in _int_list(ids, what)]
+        else:
+            slots = _int_list(slots, what)
+        self._check_slots(slots, what)
+        for s in slots:
+            if self._id[s] is None:
+                raise ValueError("%s: slot %d is free" % (what, s))
+        heads = [self._head[s] for s in slots]
+        if len(set(heads)) != len(heads):
+            raise ValueError("%s: a video is named twice in one call (head slots %s)"
+                             % (what, sorted(h for h in set(heads) if heads.count(h) > 1)))
+        return heads
+
+    # ---- SlotTable's calls: videos of one part only --------------------------------------------------------------------------
+    def check_put(self, slots, ids=None, what="put"):
+        slots = _int_list(slots, what)
+        self._check_slots(slots, what)
+        for s in slots:
+            if self._head[s] != s or self._next[s] != -1:
+                raise ValueError("%s: slot %d is a part of the video at head slot %d; replace or remove the whole video"
+                                 % (what, s, self._head[s]))
+        return SlotTable.check_put(self, slots, ids, what)
+
+    # ---- chains ------------------------------------------------------------------------------------------------------------
+    def check_chains(self, counts, offsets, ids=None, old_heads=None, what="add"):
+        """Slots for the videos of one call: counts[i] parts for video i, offsets[i] their first clips (rising from 0).
+        old_heads=None (add): every part takes a free slot, lowest first, videos in call order.  old_heads (replace): video i
+        takes over the slots of the video at old_heads[i], in order -- the head keeps its number --, the slots it does not
+        need are freed, and the parts it has beyond them take the lowest free slots, those just freed included.
+        ids: one per video (None: add gives a video its head slot's number, replace keeps the id).  Returns the plan
+          heads, ids          per video
+          chains              per video the slots of its parts, in offset order
+          put_slots, put_ids  per PART, in batch order: where each row of the batch goes and the id it carries
+          surplus             the slots a replace frees and no video of the call takes
+          records             [[slot, head, next, offset], ...] for xml_index_set_chains
+        Nothing changes; ValueError when the call does not fit."""
+        counts = [int(c) for c in counts]
+        n = len(counts)
+        if len(offsets) != n or any(len(o) != c for o, c in zip(offsets, counts)):
+            raise ValueError("%s: one offset per part expected" % what)
+        for c in counts:
+            if c < 1:
+                raise ValueError("%s: a video of %d parts" % (what, c))
+            if c > self.max_parts:
+                raise ValueError("%s: a video of %d parts; the index was created with max_parts = %d (the fold walks a chain "
+                                 "per slot: its cost grows with the square of the parts)" % (what, c, self.max_parts))
+        old = [[] for _ in range(n)]
+        if old_heads is not None:
+            if len(old_heads) != n:
+                raise ValueError("%s: %d slots for a batch of %d videos" % (what, len(old_heads), n))
+            old = [self.chain_of(h) for h in old_heads]
+        keep = [o[:c] for o, c in zip(old, counts)]
+        freed = sorted(s for o, c in zip(old, counts) for s in o[c:])
+        need = sum(c - len(k) for c, k in zip(counts, keep))
+        if need > len(self._free) + len(freed):
+            raise ValueError("%s: %d parts of %d videos into an index with %d free slots of %d (the index is full)"
+                             % (what, need, n, len(self._free) + len(freed), self.capacity))
+        pool = sorted(heapq.nsmallest(need, self._free) + freed)[:need]
+        chains, at = [], 0
+        for c, k in zip(counts, keep):
+            chains.append(k + pool[at:at + c - len(k)])
+            at += c - len(k)
+        heads = [ch[0] for ch in chains]
+        if ids is None:
+            ids = [self._id[h] if self._id[h] is not None else h for h in heads]
+        else:
+            ids = _int_list(ids, what)
+        if len(ids) != n:
+            raise ValueError("%s: %d ids for %d videos" % (what, len(ids), n))
+        if len(set(ids)) != len(ids):
+            raise ValueError("%s: duplicate video ids in one call" % what)
+        leaving = set(s for o in old for s in o)
+        for v in ids:
+            if not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s: video id %d does not fit int32" % (what, v))
+            held = self._slot.get(v)
+            if held is not None and held not in leaving:
+                raise ValueError("%s: video id %d is already held by slot %d" % (what, v, held))
+        taken = set(s for ch in chains for s in ch)
+        surplus = [s for s in freed if s not in taken]
+        want = {s: (s, -1, 0) for s in surplus}
+        for ch, offs in zip(chains, offsets):
+            for j, s in enumerate(ch):
+                want[s] = (ch[0], ch[j + 1] if j + 1 < len(ch) else -1, int(offs[j]))
+        records = [[s] + list(w) for s, w in sorted(want.items()) if w != self.state(s)]
+        return dict(heads=heads, ids=ids, chains=chains, put_slots=[s for ch in chains for s in ch],
+                    put_ids=[v for v, ch in zip(ids, chains) for _ in ch], surplus=surplus, records=records,
+                    old=[s for o in old for s in o])
+
+    def check_remove_chains(self, heads):
+        """The plan that frees the whole videos at `heads` (resolve_videos): slots = every slot of them, records = the single
+        state for each of those that is not in it."""
+        slots = [s for h in heads for s in self.chain_of(h)]
+        return dict(heads=list(heads), slots=slots, records=[[s, s, -1, 0] for s in sorted(slots) if self.state(s) != (s, -1, 0)])
+
+    def _free_slot(self, s):
+        self._slot.pop(self._id[s], None)
+        self._id[s] = None
+        heapq.heappush(self._free, s)
+
+    def commit_remove_chains(self, plan):
+        for s in plan["slots"]:
+            self._free_slot(s)
+            self._head[s], self._next[s], self._off[s] = s, -1, 0
+
+    def commit_chains(self, plan):
+        for s in plan["old"]:
+            self._free_slot(s)
+        for s in plan["put_slots"]:
+            self._free.remove(s)
+        heapq.heapify(self._free)
+        for v, ch in zip(plan["ids"], plan["chains"]):
+            for s in ch:
+                self._id[s] = v
+            self._slot[v] = ch[0]
+        for s, h, nx, off in plan["records"]:
+            self._head[s], self._next[s], self._off[s] = h, nx, off
 
 
 def blocks_of(n_clips):
@@ -479,18 +651,28 @@ class MutableCorpusIndex(CorpusIndex):
     Updates take the videos' valid lengths (last valid clip + 1 over the modalities) as n_clips=; without it they are read
     from the masks with one small device -> host copy, the one synchronising path of an update.  Given up, beyond what the
     plain form gives up: `tiles` does not grow (an update that finds no run is refused; compact() -- or auto_compact=True -- makes the free blocks
-    of the tiles contiguous first), K6 costs N tiles whatever the occupancy."""
+    of the tiles contiguous first), K6 costs N tiles whatever the occupancy.
+
+    Long videos, create(..., part_overlap=O): a video of more than l_ref clips is stored as the
+    overlapping parts of ingest.plan_parts(n_clips, l_ref, overlap=O), one slot (and, packed, one run) per part; then
+      chain_head / chain_next / chain_offset  (capacity,) int32 device: slot -> the slot of its video's first part, the slot
+                 of the next part (-1), the part's first clip in the video; a free slot and a one-part video: (itself, -1, 0)
+      table      a ChainTable; n_videos_live counts videos, n_live slots
+    A video is numbered by its HEAD slot: add(..., parts=) returns it, slot_of(id) gives it, a caller's video_allow bit for
+    the video is the head's bit, out["top_videos"] lists it.  Chains are added, replaced and removed whole."""
 
     def __init__(self, *a, **kw):
         raise TypeError("use MutableCorpusIndex.create(model, capacity) or MutableCorpusIndex.from_batches(...)")
 
     @classmethod
     def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None,
-               auto_compact=False):
+               auto_compact=False, part_overlap=None, max_parts=32):
         """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l).
         tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring).
         auto_compact (the packed form): an add / put / replace that finds no run although enough blocks are free runs
-        compact() once and tries again."""
+        compact() once and tries again.
+        part_overlap=O (None: off, nothing changes): videos longer than l_ref clips are taken as CHAINS of slots (class
+        docstring), cut by ingest.plan_parts(n_clips, l_ref, overlap=O); max_parts bounds the parts of one video."""
         dt = getattr(model, "compute_dtype", torch.float32)
         if dt is hip_ops.F16S or exact_filter:
             raise ValueError("MutableCorpusIndex: no exact-rank mode (an ops.F16S model / exact_filter=True) -- its certificate "
@@ -500,10 +682,16 @@ class MutableCorpusIndex(CorpusIndex):
         if video_offset or n_total is not None:
             raise ValueError("MutableCorpusIndex: not a corpus shard (video_offset / n_total): the sharded drivers number "
                              "videos by position in a fixed global corpus")
-        table = SlotTable(capacity)
         l_ref = int(model.config.max_ctx_l if l_ref is None else l_ref)
         if l_ref <= 0:
             raise ValueError("MutableCorpusIndex: l_ref must be positive, got %d" % l_ref)
+        if part_overlap is None:
+            table = SlotTable(capacity)
+        else:
+            if isinstance(part_overlap, bool) or int(part_overlap) != part_overlap or not 0 <= int(part_overlap) < l_ref:
+                raise ValueError("MutableCorpusIndex: part_overlap must be a number of clips in [0, l_ref = %d), got %r"
+                                 % (l_ref, part_overlap))
+            table = ChainTable(capacity, max_parts)
         act = getattr(model, "act_dtype", dt)
         h = int(model.config.hidden_size)
         lpad = index_lpad(l_ref, model, hip_ops)
@@ -552,24 +740,40 @@ class MutableCorpusIndex(CorpusIndex):
         self.slot_ids = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         self.table = table
         self.model = model
+        if part_overlap is not None:         # every slot in the single state: an add of short videos never touches these
+            self.part_overlap, self.max_parts = int(part_overlap), table.max_parts
+            self.chain_head = torch.arange(cap, dtype=torch.int32, device=dev)
+            self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+            self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
         return self
 
     @classmethod
-    def from_batches(cls, model, context_batches, capacity, l_ref=None, ids=None, n_clips=None, **kw):
+    def from_batches(cls, model, context_batches, capacity, l_ref=None, ids=None, n_clips=None, parts=None, **kw):
         """create + one add per (video_feat, video_mask, sub_feat, sub_mask) batch; ids: the videos' ids, in order; n_clips:
-        their valid lengths, in order (the packed form, tiles=N; None: read from the masks, one host read per batch)."""
+        their valid lengths, in order (the packed form, tiles=N; None: read from the masks, one host read per batch).
+        parts (an index created with part_overlap=): the ingest.PartTable of the batch, or a list of them, one per batch --
+        the batch rows are then parts, ids one per SOURCE video, n_clips one per part."""
         self = cls.create(model, capacity, l_ref, **kw)
         ids = None if ids is None else _int_list(ids, "ids")
         n_clips = None if n_clips is None else _int_list(n_clips, "n_clips")
-        r = 0
-        for vf, vm, sf, sm in context_batches:
+        tables = None if parts is None else (list(parts) if isinstance(parts, (list, tuple)) else [parts])
+        r = v = 0
+        for i, (vf, vm, sf, sm) in enumerate(context_batches):
             b = int((vf if vf is not None else sf).shape[0])
-            self.add(vf, vm, sf, sm, ids=None if ids is None else ids[r:r + b], n_clips=None if n_clips is None else n_clips[r:r + b])
+            kw_add, nv = {}, b
+            if tables is not None:
+                if i >= len(tables):
+                    raise ValueError("from_batches: %d part tables for more batches (parts= takes one table per batch)" % len(tables))
+                kw_add, nv = dict(parts=tables[i]), int(tables[i].n_videos)
+            self.add(vf, vm, sf, sm, ids=None if ids is None else ids[v:v + nv], n_clips=None if n_clips is None else n_clips[r:r + b],
+                     **kw_add)
             r += b
+            v += nv
         return self
 
     capacity = property(lambda self: self.table.capacity)
     n_live = property(lambda self: self.table.n_live)
+    n_videos_live = property(lambda self: getattr(self.table, "n_videos_live", self.table.n_live))
 
     def set_valid_lengths(self):
         return self                           # vlen is maintained per slot by the update kernels; ragged stays True
@@ -579,6 +783,8 @@ class MutableCorpusIndex(CorpusIndex):
 
     def hbm_bytes(self):
         extra = list(self.mask_bits.values()) + [self.vlen, self.live, self.slot_ids] + ([] if self.codes is None else [self.codes])
+        if self.chain_head is not None:
+            extra += [self.chain_head, self.chain_next, self.chain_offset]
         return CorpusIndex.hbm_bytes(self) + sum(t.numel() * t.element_size() for t in extra)
 
     # ---- updates --------------------------------------------------------------------------------------------------------
@@ -636,8 +842,21 @@ class MutableCorpusIndex(CorpusIndex):
         """Write an ENCODED batch, enc[m] = (feat1, feat2, mask) of (b, lb <= l_ref) rows as model.encode_context returns them,
         into the b distinct slots; a live slot is replaced, a free one becomes live.  ids=None keeps / assigns ids as
         SlotTable.check_put says.  n_clips (the packed form; ignored by the plain one): the videos' valid lengths, class
-        docstring -- a mask that is longer than its n_clips rounded up to whole blocks is cut there.  Returns the slots."""
+        docstring -- a mask that is longer than its n_clips rounded up to whole blocks is cut there.  Returns the slots.
+        (An index with chains: videos of one part only; a slot of a longer video is refused.)"""
         slots, ids = self.table.check_put(slots, ids)
+        self._check_enc(slots, enc)
+        nbs = runs = clears = None
+        if self.blocks is not None:
+            nbs = self._n_blocks(self._valid_lengths([enc[m][2] for m in self.modalities]) if n_clips is None else n_clips,
+                                 len(slots), "put")
+            runs, clears = self._find_runs(slots, nbs, "put")
+        self._launch_put(slots, ids, enc, nbs, runs, clears)
+        self.table.commit_put(slots, ids)
+        return slots
+
+    def _check_enc(self, slots, enc):
+        """Everything a put launch could refuse about an encoded batch, before anything is enqueued."""
         mods = self.modalities
         if set(enc) != set(mods):
             raise ValueError("put: the batch holds modalities %s, the index %s" % (sorted(enc), mods))
@@ -654,8 +873,13 @@ class MutableCorpusIndex(CorpusIndex):
                         tuple(a1.shape) != want or tuple(a2.shape) != want or tuple(am.shape) != want[:2]:
                     raise ValueError("put: %s rows (b, lb, %d) of %s on the device and a (b, lb) mask expected"
                                      % (m, want[2], self.feat2[m].dtype))
-            nbs = self._n_blocks(self._valid_lengths([enc[m][2] for m in mods]) if n_clips is None else n_clips, b, "put")
-            runs, clears = self._find_runs(slots, nbs, "put")
+
+    def _launch_put(self, slots, ids, enc, nbs, runs, clears):
+        """The launches of a validated put (the packed form: with the runs _find_runs returned, committed to the BlockTable
+        here); the slot table is the caller's to commit."""
+        mods = self.modalities
+        b = len(slots)
+        if self.blocks is not None:
             if clears:     # videos that move: their old runs become unused blocks BEFORE the put, whose runs may reuse them
                 hip_ops.index_clear_rows_packed(self._to_device([-1] * len(clears)), self._to_device(clears), 8,
                                                 [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], self.codes,
@@ -668,15 +892,12 @@ class MutableCorpusIndex(CorpusIndex):
                                           [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.slot_ids,
                                           self.live.view(-1), self.l_ref)
             self.blocks.commit_put(slots, runs)
-            self.table.commit_put(slots, ids)
-            return slots
+            return
         both = self._to_device([slots, ids])
         hip_ops.index_put_rows([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
                                [enc[m][2].float().contiguous() for m in mods], both[0], both[1],
                                [self.feat1n[m] for m in mods], [self.feat2[m] for m in mods], [self.mask[m] for m in mods],
                                [self.mask_bits[m] for m in mods], self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
-        self.table.commit_put(slots, ids)
-        return slots
 
     def _room(self, slots, masks, n_clips, b, what):
         """The packed form: refuse a batch that finds no runs BEFORE it is encoded; returns n_clips for put (the lengths read
@@ -688,17 +909,26 @@ class MutableCorpusIndex(CorpusIndex):
         self._find_runs(slots, self._n_blocks(n_clips, b, what), what)
         return n_clips
 
-    def _find_runs(self, slots, n_blocks, what):
+    def _find_runs(self, slots, n_blocks, what, freed=()):
         """BlockTable.check_put; with auto_compact a refusal for lack of a RUN while enough blocks are free is answered by one
-        compact() and one more try."""
+        compact() and one more try.  freed: slots the same call frees first (the surplus parts of a replaced chain) -- their
+        runs count as room; the table is back in its state when this returns."""
+        def attempt():
+            gone = self.blocks.check_remove(freed) if freed else []
+            self.blocks.commit_remove(freed)
+            try:
+                return self.blocks.check_put(slots, n_blocks, what)
+            finally:
+                for s, (first, nb) in reversed(list(zip(freed, gone))):
+                    self.blocks._take(first, nb, s)
         try:
-            return self.blocks.check_put(slots, n_blocks, what)
+            return attempt()
         except NoRunError as e:
             if not self.auto_compact or e.blocks_free < e.blocks_asked:
                 raise
         self.compact()
         try:
-            return self.blocks.check_put(slots, n_blocks, what)
+            return attempt()
         except NoRunError as e:
             raise NoRunError(str(e) + " after compaction", e.blocks_asked, e.blocks_free)
 
@@ -738,18 +968,32 @@ class MutableCorpusIndex(CorpusIndex):
                     largest_free_run_before=before["largest_free_run"], largest_free_run_after=after["largest_free_run"],
                     bytes_moved=moved * 16 * row_bytes)
 
-    def add(self, video_feat, video_mask, sub_feat, sub_mask, ids=None, n_clips=None):
+    def add(self, video_feat, video_mask, sub_feat, sub_mask, ids=None, n_clips=None, parts=None):
         """Encode a context batch and store its videos in the lowest free slots; returns the slots (a list, batch order).
-        n_clips: put."""
+        n_clips: put.  parts (an index created with part_overlap=O): the ingest.PartTable of THIS batch,
+        ingest.plan_parts(clip counts, index.l_ref, overlap=O) -- the batch rows are its parts in table order (what
+        ingest.ContextFeeder(parts=table) yields), ids has one entry per source video, n_clips (default: the table's part
+        lengths) one per part; returns the HEAD slots, one per video."""
+        if parts is not None:
+            return self._put_chains(None, video_feat, video_mask, sub_feat, sub_mask, ids, n_clips, parts, "add")
         b = self._check_batch(video_feat, video_mask, sub_feat, sub_mask, "add")
         slots, ids = self.table.check_add(b, ids)
         n_clips = self._room(slots, (video_mask, sub_mask), n_clips, b, "add")
         return self.put(slots, self.encode(video_feat, video_mask, sub_feat, sub_mask), ids, n_clips)
 
-    def replace(self, slots, video_feat, video_mask, sub_feat, sub_mask, ids=None, new_ids=None, n_clips=None):
+    def replace(self, slots, video_feat, video_mask, sub_feat, sub_mask, ids=None, new_ids=None, n_clips=None, parts=None):
         """Encode a context batch over the LIVE slots named by `slots` (or, slots=None, by ids=); the videos keep their ids
         unless new_ids gives others.  The packed form: a video whose block count does not change keeps its run, any other
-        moves (its old run is freed first).  n_clips: put.  Returns the slots."""
+        moves (its old run is freed first).  n_clips: put.  Returns the slots.
+        An index created with part_overlap=: the slots name VIDEOS (by any slot of each); the old chains are freed and the new
+        ones placed in one validated call -- a new video takes over its predecessor's slots in order (the head keeps its
+        number), frees those it does not need and takes the lowest free slots for further parts; parts as in add (None: every
+        row of the batch is a whole video).  Returns the head slots."""
+        if self.chain_head is not None:
+            heads = self.table.resolve_videos(slots, ids, "replace")
+            return self._put_chains(heads, video_feat, video_mask, sub_feat, sub_mask, new_ids, n_clips, parts, "replace")
+        if parts is not None:
+            self._part_lists(parts, 0, "replace")
         slots = self.table.resolve(slots, ids, "replace")
         b = self._check_batch(video_feat, video_mask, sub_feat, sub_mask, "replace")
         if b != len(slots):
@@ -760,19 +1004,91 @@ class MutableCorpusIndex(CorpusIndex):
 
     def remove(self, slots=None, ids=None):
         """Free the LIVE slots named by `slots` (or by ids=): searches enqueued afterwards no longer see them.  Returns them.
-        The packed form frees their runs too."""
-        slots = self.table.resolve(slots, ids, "remove")
+        The packed form frees their runs too.  An index created with part_overlap=: a video is named by any of its slots or by
+        its id and its whole chain is freed (all its slots are returned); one xml_index_set_chains launch puts every freed
+        slot of a longer video back into the single state."""
+        plan = None
+        if self.chain_head is not None:
+            plan = self.table.check_remove_chains(self.table.resolve_videos(slots, ids, "remove"))
+            slots = plan["slots"]
+        else:
+            slots = self.table.resolve(slots, ids, "remove")
+        mods = self.modalities
         if slots and self.blocks is not None:
-            mods = self.modalities
             runs = self.blocks.check_remove(slots)
             hip_ops.index_clear_rows_packed(self._to_device(slots), self._to_device(runs), 8, [self.mask[m] for m in mods],
                                             [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.live.view(-1),
                                             self.l_ref)
             self.blocks.commit_remove(slots)
-            self.table.commit_remove(slots)
         elif slots:
-            mods = self.modalities
             hip_ops.index_clear_rows(self._to_device(slots), [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods],
                                      self.vlen, self.live.view(-1), self.l_ref)
+        if plan is not None:
+            self._set_chains(plan["records"])
+            self.table.commit_remove_chains(plan)
+        elif slots:
             self.table.commit_remove(slots)
         return slots
+
+    # ---- long videos: chains of slots (DESIGN.md section 20c) ---------------------------------------------------------------
+    def _set_chains(self, records):
+        if records:
+            hip_ops.index_set_chains(self._to_device(records).view(-1, 4), self.chain_head, self.chain_next, self.chain_offset)
+
+    def _part_lists(self, table, b, what):
+        """A batch's part table against this index: (parts per video, their offsets per video, clips per part) as host lists.
+        table=None: every row of the batch is a whole video."""
+        if table is None:
+            return [1] * b, [[0]] * b, None
+        if self.chain_head is None:
+            raise ValueError("%s: parts= on an index created without part_overlap= -- it holds videos of up to l_ref = %d clips "
+                             "only (MutableCorpusIndex.create(..., part_overlap=O))" % (what, self.l_ref))
+        for name in ("max_ctx_len", "overlap", "n_parts", "n_videos", "group_start", "part_offset", "part_len"):
+            if not hasattr(table, name):
+                raise ValueError("%s: parts must be the ingest.PartTable of the batch (ingest.plan_parts), got %s"
+                                 % (what, type(table).__name__))
+        if int(table.max_ctx_len) != self.l_ref:
+            raise ValueError("%s: the part table was planned for parts of %d clips, the index holds l_ref = %d "
+                             "(ingest.plan_parts(n_clips, index.l_ref, overlap=%d))"
+                             % (what, table.max_ctx_len, self.l_ref, self.part_overlap))
+        if int(table.overlap) != self.part_overlap:
+            raise ValueError("%s: the part table overlaps its parts by %d clips, the index was created with part_overlap = %d "
+                             "(searches rely on it: a moment of up to part_overlap clips lies inside one part)"
+                             % (what, table.overlap, self.part_overlap))
+        if int(table.n_parts) != b:
+            raise ValueError("%s: the batch holds %d rows, the part table has %d parts" % (what, b, table.n_parts))
+        gs, po, pl = (_int_list(t.cpu() if torch.is_tensor(t) else t, what)
+                      for t in (table.group_start, table.part_offset, table.part_len))
+        counts = [gs[i + 1] - gs[i] for i in range(len(gs) - 1)]
+        return counts, [po[gs[i]:gs[i + 1]] for i in range(len(counts))], pl
+
+    def _put_chains(self, old_heads, video_feat, video_mask, sub_feat, sub_mask, ids, n_clips, parts, what):
+        """add (old_heads=None) / replace of whole videos on an index with chains: one validated call -- ChainTable.check_chains,
+        in the packed form the runs of every part with the freed slots' runs counted as room -- then the launches: clear of the
+        surplus slots, put of all parts, xml_index_set_chains over the slots whose link state changes."""
+        b = self._check_batch(video_feat, video_mask, sub_feat, sub_mask, what)
+        counts, offsets, part_len = self._part_lists(parts, b, what)
+        plan = self.table.check_chains(counts, offsets, ids, old_heads, what)
+        slots, surplus, mods = plan["put_slots"], plan["surplus"], self.modalities
+        nbs = runs = clears = None
+        if self.blocks is not None:
+            if n_clips is None:
+                n_clips = part_len if part_len is not None else \
+                    self._valid_lengths([mk for m, mk in zip(("video", "sub"), (video_mask, sub_mask)) if m in mods])
+            nbs = self._n_blocks(n_clips, b, what)
+            runs, clears = self._find_runs(slots, nbs, what, freed=surplus)
+        enc = self.encode(video_feat, video_mask, sub_feat, sub_mask)
+        self._check_enc(slots, enc)
+        if surplus and self.blocks is not None:
+            gone = self.blocks.check_remove(surplus)
+            hip_ops.index_clear_rows_packed(self._to_device(surplus), self._to_device(gone), 8, [self.mask[m] for m in mods],
+                                            [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.live.view(-1),
+                                            self.l_ref)
+            self.blocks.commit_remove(surplus)
+        elif surplus:
+            hip_ops.index_clear_rows(self._to_device(surplus), [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods],
+                                     self.vlen, self.live.view(-1), self.l_ref)
+        self._launch_put(slots, plan["put_ids"], enc, nbs, runs, clears)
+        self._set_chains(plan["records"])
+        self.table.commit_chains(plan)
+        return plan["heads"]

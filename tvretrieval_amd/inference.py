@@ -30,8 +30,9 @@ and the sharded drivers call:
 The split-f16 exact mode (split_f16_rows, SplitRows, F16_UNIT_LOG2), explain_moments (span_evidence), the device-side result
 records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and searches on an index of parts (group_best_allow,
 best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
-index_clear_rows) call further entries of tvretrieval_amd.ops; a backend without them serves every search that does not ask
-for those.
+index_clear_rows) and the searches and updates of one with chains of slots for long videos (index_set_chains,
+chain_best_allow, chain_best_rows) call further entries of tvretrieval_amd.ops; a backend without them serves every search
+that does not ask for those.
 """
 import numpy as np
 import torch
@@ -82,6 +83,11 @@ class CorpusIndex(object):
         # (1, ceil(n_videos / 32)) int32 words of the occupied ones -- every search sees live AND video_allow -- and slot_ids
         # the slot -> caller's id table (the meta2vid of a search that passes none).  None on every other index.
         self.live = self.slot_ids = None
+        # long videos on such an index (MutableCorpusIndex.create(..., part_overlap=O)): a video is a
+        # CHAIN of slots, one part each; (n_videos,) int32 device tables slot -> head slot / next slot (-1) / first clip of the
+        # slot's part in its video.  A video's number -- in top_videos, in a caller's video_allow -- is its HEAD slot.
+        self.chain_head = self.chain_next = self.chain_offset = None
+        self.part_overlap = self.max_parts = None
 
     def set_valid_lengths(self):
         """Per-video valid length from the masks (one small device pass + one host read at build time)."""
@@ -486,16 +492,17 @@ def _parts_meta2vid(index, meta2vid):
 
 
 def _check_parts_search(index, max_pred_l, external_top=None, pad_tail=False):
-    """What a search on a parts index cannot do, each with its reason."""
+    """What a search on a parts index cannot do, each with its reason (an index with chains of slots: the same)."""
+    overlap = index.parts.overlap if index.parts is not None else index.part_overlap
     if external_top is not None:
         raise ValueError("external_top on a parts index: a caller's lists name index rows and would bypass the fold that lets "
                          "only the best part of a video compete (rank the source videos with the index instead)")
     if index.exact is not None:
         raise ValueError("a parts index cannot be an exact-rank index (exact_filter=True): no f32 score matrix exists to "
                          "take the best part of a video from")
-    if int(max_pred_l) > index.parts.overlap:
+    if int(max_pred_l) > overlap:
         raise ValueError("max_pred_l = %d exceeds the part overlap of %d clips: a moment of that length need not lie inside "
-                         "one part (plan_parts(overlap=) must be >= max_pred_l)" % (max_pred_l, index.parts.overlap))
+                         "one part (plan_parts(overlap=) must be >= max_pred_l)" % (max_pred_l, overlap))
     if pad_tail:
         raise ValueError("pad_tail=True on a parts index: the reference-shaped tail would have to invent rows in the video "
                          "slots that stay empty once every video is counted once")
@@ -783,7 +790,9 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
     A parts index: K6, then ops.group_best_allow (each video's best part AND the caller's mask over source videos), then K8 under
     those bits -- top_i are index rows, one per video; slots beyond the number of allowed videos are empty.
     An index that takes updates (index.live): the allow words are ANDed with the live words -- one small (rows, words) int32
-    pass, part of a captured search -- so the lists are those of the corpus of the live videos, in slot numbering."""
+    pass, part of a captured search -- so the lists are those of the corpus of the live videos, in slot numbering.
+    One with chains (index.chain_head): K6, then ops.chain_best_allow under those words (each video's best part; a caller's
+    video_allow bit for a video is the bit of its HEAD slot), then K8 under the fold's bits -- top_i are slots, one per video."""
     exact = None
     if video_allow is not None:
         if external_top is not None:
@@ -792,6 +801,12 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
         _check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0])
     if index.live is not None and external_top is None:
         video_allow = index.live if video_allow is None else video_allow[:, :index.live.shape[1]] & index.live
+    if index.chain_head is not None:
+        _check_parts_search(index, 0, external_top)
+        q2c = stage_q2c(index, qvec, ops)
+        best = ops.chain_best_allow(q2c, index, video_allow)
+        top_w, top_i = ops.topk_rows(q2c, min(max_vcmr_video, index.n_videos), alpha=q2c_alpha, allow=best)
+        return q2c, top_w, top_i, None
     if index.parts is not None:
         # long videos in parts: K6 scores every part, the fold keeps each video's best part (and the caller's mask, which
         # numbers source videos), K8 ranks those -- the restricted search over the index rows, one row per video
@@ -865,7 +880,12 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     (K7, K9 and explain_moments need them); out["top_videos"] (Nq, K) int32 names the source videos; records carry the source
     video's id (meta2vid: source video -> id) and whole-video times (the part's clip offset is added in K10); svmr_video names
     source videos, out["svmr_rows"] the index rows that stood for them.  Refused with a ValueError: external_top, pad_tail=True,
-    an exact-rank index, max_pred_l > parts.overlap (such a moment need not lie inside one part)."""
+    an exact-rank index, max_pred_l > parts.overlap (such a moment need not lie inside one part).
+    An index that takes updates with chains of slots (MutableCorpusIndex.create(..., part_overlap=O)): the same with slots for
+    index rows -- the fold walks the chain tables (ops.chain_best_allow), top_videos names each listed slot's HEAD slot, which
+    is also the bit a caller's video_allow carries for the video; svmr_video names a video by any of its slots; records carry
+    the video's id (slot_ids) and whole-video times (chain_offset).  Refused alike: external_top, pad_tail=True, max_pred_l >
+    part_overlap."""
     if video_allow is not None and pad_tail:
         raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
                          "rows in the empty video slots of a restricted list")
@@ -877,6 +897,10 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
                              "in the video slots that stay empty when fewer than K videos are live")
         if meta2vid is None:
             meta2vid = index.slot_ids
+    chains = index.chain_head is not None
+    if chains:      # (meta2vid: slot -> id, the same for every slot of a chain -- slot_ids unless the caller has a table)
+        _check_parts_search(index, max_pred_l, external_top, pad_tail)
+        pkw = dict(part_offset=index.chain_offset)
     if parts is not None:
         _check_parts_search(index, max_pred_l, external_top, pad_tail)
         meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=parts.part_offset)
@@ -894,6 +918,8 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         out["exact"] = exact
     if parts is not None:       # (index plumbing: the source video of every listed row, -1 in the empty slots)
         out["top_videos"] = torch.where(top_i >= 0, parts.part_video[top_i.clamp_min(0).long()], top_i)
+    if chains:                  # (the head slot of every listed slot, -1 in the empty slots)
+        out["top_videos"] = torch.where(top_i >= 0, index.chain_head[top_i.clamp_min(0).long()], top_i)
     if nms_thd is not None:
         rec, cnt = ops.moments_decode(fs, flat=fi, top_idx=top_i, meta2vid=meta2vid, l_ref=index.l_ref,
                                       clip_length=clip_length, seconds=True, **pkw)
@@ -903,6 +929,9 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         pv = svmr_video.to(torch.int32).reshape(-1).contiguous()
         if parts is not None:       # a SOURCE video per query: its best part for that query stands for it (-1: unknown id)
             pv = ops.best_part_rows(q2c, parts, pv)
+            out["svmr_rows"] = pv
+        if chains:                  # any slot of a video: the slot of its best part for that query (-1: outside the index)
+            pv = ops.chain_best_rows(q2c, index, pv)
             out["svmr_rows"] = pv
         pv = pv.reshape(-1, 1)
         st1, ed1 = stage_span_probs(model, index, qvec, pv, ops, q_lin=q_lin)
@@ -1113,7 +1142,7 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     dev = next(model.parameters()).device
     ragged = row_start is not None
     nq = (row_start.numel() - 1) if ragged else query_feat.shape[0]
-    if index.parts is not None:
+    if index.parts is not None or index.chain_head is not None:
         _check_parts_search(index, max_pred_l, None, pad_tail)
     if index.live is not None and pad_tail:
         raise ValueError("pad_tail=True on an index that takes updates (see vcmr_search)")
@@ -1153,6 +1182,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
         meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=index.parts.part_offset)
     elif meta2vid is None:       # (an index that takes updates: the records carry the caller's ids of the slots)
         meta2vid = index.slot_ids if index.slot_ids is not None else torch.arange(index.n_videos, dtype=torch.int32, device=dev)
+    if index.chain_head is not None:     # chains of slots: whole-video times (every slot of a chain carries the video's id)
+        pkw = dict(part_offset=index.chain_offset)
     copied, freed = [None, None], buffers.freed
     ev_h2d = []
 
@@ -1269,7 +1300,7 @@ class GraphedVcmrSearch(object):
             raise ValueError("GraphedVcmrSearch: video_allow_rows must be None, 1 or nq = %d, got %r" % (nq, video_allow_rows))
         if "video_allow" in search_kwargs:
             raise ValueError("GraphedVcmrSearch: pass video_allow_rows= here and the mask itself to every call")
-        if getattr(index, "parts", None) is not None:
+        if getattr(index, "parts", None) is not None or getattr(index, "chain_head", None) is not None:
             raise ValueError("GraphedVcmrSearch: a parts index (build_corpus_index(parts=)) is not captured yet -- the fold and "
                              "K10 with offsets need no host round trip, but the captured pass has not been verified; use "
                              "vcmr_search or vcmr_search_host")

@@ -6,6 +6,7 @@ GPU tensor is missing -- there is no eager/CPU fallback.
 """
 import collections
 import ctypes
+import types
 
 import numpy as np
 
@@ -1530,3 +1531,86 @@ def index_move_blocks_packed(records, k6, bits, codes):
     check(_lib.load().xml_index_move_blocks_packed(n_mod, _p(records), int(records.shape[0]), _p(data[0]), _p(bits[0]), sec(data),
                                                    sec(bits), _p(codes), n_tiles, int(k6[0].hidden), dt_of(data[0]), _stream()),
           "xml_index_move_blocks_packed")
+
+
+# ---- long videos as chains of slots (include/xmlhip_index_parts.h; MutableCorpusIndex(part_overlap=O)) ------------------------
+def _chain_tables(tables, names, what):
+    """The (capacity,) int32 chain tables `names` of an index (or of any object that carries them) and its max_parts."""
+    out, cap = [], None
+    for name in names:
+        t = getattr(tables, name, None)
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise _lib.XmlHipError("%s: %s must be a contiguous (capacity,) int32 tensor on the GPU "
+                                   "(MutableCorpusIndex.create(..., part_overlap=))" % (what, name))
+        if cap is not None and t.numel() != cap:
+            raise _lib.XmlHipError("%s: the chain tables hold %d and %d slots" % (what, cap, t.numel()))
+        cap = int(t.numel())
+        out.append(t)
+    if not cap:
+        raise _lib.XmlHipError("%s: empty chain tables" % what)
+    return out, cap
+
+
+def _chain_scores(scores, cap, device, what):
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise _lib.XmlHipError("%s: scores must be a tensor on the GPU; the HIP path has no CPU fallback" % what)
+    if scores.dtype != torch.float32:
+        raise _lib.XmlHipError("%s: scores: expected dtype torch.float32, got %s" % (what, scores.dtype))
+    if scores.dim() != 2 or scores.shape[1] != cap or (cap > 1 and scores.stride(1) != 1) or \
+            (scores.shape[0] and scores.stride(0) < cap):
+        raise ValueError("%s: scores must be a (rows, %d slots) f32 matrix with unit column stride, got %s strides %s"
+                         % (what, cap, tuple(scores.shape), tuple(scores.stride())))
+    if scores.device != device:
+        raise ValueError("%s: the scores are on %s, the chain tables on %s" % (what, scores.device, device))
+
+
+def index_set_chains(records, chain_head, chain_next, chain_offset):
+    """xml_index_set_chains: records (n, 4) int32 device = {slot, head, next, offset} scattered into the three (capacity,)
+    int32 chain tables -- links a new chain, or puts freed slots back into the single state {s, s, -1, 0}.  The slots of a call
+    are distinct (the caller's, index_update.ChainTable); a slot outside [0, capacity) writes nothing.  One launch."""
+    t = types.SimpleNamespace(chain_head=chain_head, chain_next=chain_next, chain_offset=chain_offset)
+    (head, nxt, off), cap = _chain_tables(t,("chain_head", "chain_next", "chain_offset"), "index_set_chains")
+    _req(records, "records", torch.int32)
+    if records.dim() != 2 or records.shape[1] != 4:
+        raise _lib.XmlHipError("index_set_chains: records (n, 4) int32 = {slot, head, next, offset} expected")
+    if not records.shape[0]:          # (an empty tensor has no address to pass; the entry launches nothing for n == 0 either)
+        return
+    check(_lib.load().xml_index_set_chains(_p(records), int(records.shape[0]), _p(head), _p(nxt), _p(off), cap, _stream()),
+          "xml_index_set_chains")
+
+
+def chain_best_allow(scores, chains, video_allow):
+    """The fold of an updatable index with chains between K6 and K8 (xml_chain_best_allow).  scores (rows, capacity) f32 (row
+    stride >= capacity); chains: the index (chain_head / chain_next (capacity,) int32 device, max_parts); video_allow
+    (1 | rows, >= ceil(capacity / 32)) int32 words, required -- the caller's mask ANDed with the live words, or the live words.
+    -> (rows, ceil(capacity / 32)) int32 words: bit s set iff the allow bit of s's HEAD is set and s is the best part of its
+    chain for that row (maximum, ties to the lowest offset, NaN never wins; the score of a one-slot chain is not read)."""
+    (head, nxt), cap = _chain_tables(chains, ("chain_head", "chain_next"), "chain_best_allow")
+    _chain_scores(scores, cap, head.device, "chain_best_allow")
+    rows = scores.shape[0]
+    if video_allow is None:
+        raise ValueError("chain_best_allow: video_allow is required (the live words of the index at least)")
+    video_allow, _ = _allow_args(video_allow, 0, rows, cap, scores.device, "chain_best_allow")
+    out = torch.empty((rows, (cap + 31) // 32), dtype=torch.int32, device=scores.device)
+    check(_lib.load().xml_chain_best_allow(_p(scores), scores.stride(0) if rows else cap, rows, cap, _p(head), _p(nxt),
+                                           int(chains.max_parts), _p(video_allow), video_allow.stride(0),
+                                           video_allow.shape[0], _p(out), out.stride(0), _stream()), "xml_chain_best_allow")
+    return out
+
+
+def chain_best_rows(scores, chains, video):
+    """scores (rows, capacity) f32, video (rows,) int32: ANY slot of one video per row -> (rows,) int32 slot of that video's
+    best part (chain_best_allow's rule), -1 for a slot outside [0, capacity)  (xml_chain_best_rows)."""
+    (head, nxt), cap = _chain_tables(chains, ("chain_head", "chain_next"), "chain_best_rows")
+    _chain_scores(scores, cap, head.device, "chain_best_rows")
+    rows = scores.shape[0]
+    if not torch.is_tensor(video) or video.dtype != torch.int32 or video.dim() != 1 or video.numel() != rows:
+        raise ValueError("chain_best_rows: video must be a (%d,) int32 tensor of slots, got %s %s"
+                         % (rows, getattr(video, "dtype", type(video).__name__), tuple(getattr(video, "shape", ()))))
+    if video.device != scores.device:
+        raise ValueError("chain_best_rows: video is on %s, the scores are on %s" % (video.device, scores.device))
+    video = video.contiguous()
+    out = torch.empty((rows,), dtype=torch.int32, device=scores.device)
+    check(_lib.load().xml_chain_best_rows(_p(scores), scores.stride(0) if rows else cap, rows, cap, _p(head), _p(nxt),
+                                          int(chains.max_parts), _p(video), _p(out), _stream()), "xml_chain_best_rows")
+    return out
