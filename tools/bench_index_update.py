@@ -1,8 +1,8 @@
 """Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
 
-usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains] [--batch 200] [--reps 21] [--pass-reps 5]
-                                          [--queries 10000] [--videos 21793] [--suite-wall "..."]
-                                          [--out profiles/index_update_timing.md]
+usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains,exact] [--batch 200] [--reps 21]
+                                          [--pass-reps 5] [--queries 10000] [--videos 21793] [--suite-wall "..."]
+                                          [--out profiles/index_update_timing.md; --legs exact: profiles/index_exact_timing.md]
 
   put   xml_index_put_rows alone on a --batch-video batch at the headline shape (H = 768, lpad = 128, bf16, two modalities),
         next to the existing passes it replaces run on the same rows in the same process: the fused normalise-and-tile pass
@@ -23,6 +23,11 @@ usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compa
         videos cut at 128 clips), the 10 000-query pass on both; xml_chain_best_allow alone for 10 000 and 50 queries next to
         xml_group_best_allow on the part table of the same videos and the same score matrix (capacity = parts, filled in
         corpus order: slot p holds part p), and on the same chains over a random permutation of the slots
+  exact   (not in the default set) exact-rank mode on a mutable index at the headline shape (ops.F16S
+        model, tiles=None): xml_index_put_rows_exact on batches of 256 and 2 048 videos next to xml_index_put_rows on a plain
+        f32 index and to the one-shot chain over the same rows; the 10 000-query pass and the 50-query replay next to the
+        one-shot exact index of the same videos; certificate failures per pass under the running bound, after removing 10 % of
+        the slots, and after tighten_error_bound(); hbm_bytes()
 
 Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
 same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
@@ -590,6 +595,137 @@ def chains_leg(args, lines):
     torch.cuda.empty_cache()
 
 
+def exact_put_leg(args, lines, b):
+    """(a) xml_index_put_rows_exact on a b-video f32 batch, next to xml_index_put_rows on a plain f32 index fed the same rows and
+    to the one-shot exact-rank chain over the same rows."""
+    dev, h, lpad, bf16 = "cuda", 768, 128, torch.bfloat16
+    cap = 2 * b
+    g = torch.Generator(device=dev).manual_seed(0)
+    enc = [(torch.randn((b, lpad, h), device=dev, generator=g), torch.randn((b, lpad, h), device=dev, generator=g),
+            torch.ones((b, lpad), device=dev)) for _ in range(2)]
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)        # noqa: E731
+    split = lambda: ops.SplitRows(z(cap, lpad, h, dt=torch.int32), z(cap, lpad))   # noqa: E731
+    k6 = [ops.TiledRows(z(ops.q2c_tiled_numel(cap * lpad, h, bf16), dt=bf16), cap * lpad, h, (cap, lpad, h)) for _ in range(2)]
+    resc, f2, err = [split() for _ in range(2)], [split() for _ in range(2)], [z(cap, lpad) for _ in range(2)]
+    mk, bits = [z(cap, lpad) for _ in range(2)], [z(cap, 4, dt=torch.int32) for _ in range(2)]
+    ec, vlen, sid, live = z(2), z(cap, dt=torch.int32), z(cap, dt=torch.int32), z((cap + 31) // 32, dt=torch.int32)
+    pk6 = [ops.TiledRows(z(ops.q2c_tiled_numel(cap * lpad, h, torch.float32)), cap * lpad, h, (cap, lpad, h)) for _ in range(2)]
+    pf2 = [z(cap, lpad, h) for _ in range(2)]
+    scattered = torch.from_numpy(np.random.default_rng(0).permutation(cap)[:b].astype(np.int32)).to(dev)
+    cols = lambda i: [e[i] for e in enc]                                           # noqa: E731
+
+    def put_exact():
+        ops.index_put_rows_exact(cols(0), cols(1), cols(2), scattered, None, k6, resc, f2, err, mk, bits, ec, vlen, sid, live, lpad)
+
+    def put_plain():
+        ops.index_put_rows(cols(0), cols(1), cols(2), scattered, None, pk6, pf2, mk, bits, vlen, sid, live, lpad)
+
+    def chain():        # inference._exact_filter_operands + _finish_index; no mask handed over: no host read of it
+        for m in range(2):
+            fn = ops.l2norm_rows(enc[m][0])
+            fb, _ = ops.round_bf16_rows_err(fn)
+            ops.split_f16_rows(fn, ops.F16_UNIT_LOG2)
+            ops.split_f16_rows(enc[m][1])
+            ops.pack_q2c_corpus(fb)
+
+    per = b * lpad * h
+    by_exact = 2 * (per * (4 + 4 + 2 + 4 + 4) + b * lpad * 4 * 5 + b * 16)        # f1, f2 read; filter, re-score, feat2 written
+    by_plain = 2 * (per * 16 + b * lpad * 4 * 2 + b * 16)
+    res = []
+    for rnd in ("", ", again"):
+        res += [("xml_index_put_rows_exact (mode f16s), scattered slots" + rnd, timed(put_exact, args.reps), by_exact),
+                ("xml_index_put_rows, plain f32 index, the same rows" + rnd, timed(put_plain, args.reps), by_plain),
+                ("one-shot chain: l2norm_rows + round_bf16_rows_err + split_f16_rows x 2 + pack_q2c_corpus, per modality (10 launches)" + rnd,
+                 timed(chain, args.reps), by_exact)]
+    lines += ["", "### Batches of %d videos" % b, "",
+              "%d videos x %d clips x H = %d, f32 rows, two modalities into an index of %d slots.  Bytes counted from the shapes: "
+              "%.1f MB per exact-rank put (f1 and f2 read once; bf16 filter rows, split-f16 re-score rows and split-f16 feat2 written "
+              "once; norms, scales, masks), %.1f us at the %.1f TB/s HBM stream rate; %.1f MB per plain f32 put.  The chain is "
+              "charged the exact-rank put's bytes: its temporaries are its own cost."
+              % (b, lpad, h, cap, by_exact / 1e6, by_exact / HBM_STREAM * 1e6, HBM_STREAM / 1e12, by_plain / 1e6),
+              "", "| what | time per call | videos / s | bytes / s |", "|---|---|---|---|"]
+    for name, t, moved in res:
+        lines.append("| %s | %s | %.3g | %.2f TB/s |" % (name, fmt(t, "us"), b / (t[0] * 1e-3), moved / (t[0] * 1e-3) / 1e12))
+    med = lambda i: (res[i][1][0] + res[i + 3][1][0]) / 2                         # noqa: E731
+    lines += ["", "Medians, mean of both rounds: exact-rank put %.1f us, plain f32 put %.1f us (x %.2f), one-shot chain %.1f us "
+              "(x %.2f of the exact-rank put)." % (med(0) * 1e3, med(1) * 1e3, med(0) / med(1), med(2) * 1e3, med(2) / med(0))]
+    for ln in lines[-12:]:
+        print(ln, flush=True)
+    torch.cuda.empty_cache()
+
+
+def exact_leg(args, lines):
+    """Exact-rank mode on a mutable index at the headline shape (capacity 21 793, H = 768, ops.F16S model, tiles=None)."""
+    import bench
+    lines += ["## Exact-rank mode on an index that takes updates (create(..., exact_rank=True), mode f16s)", "",
+              "## (a) The put kernel alone"]
+    for b in (256, 2048):
+        exact_put_leg(args, lines, b)
+    _, _, l, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3"]
+    nv, nq = args.videos, args.queries
+    be = bench.HipBackend(0)
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), ops.F16S)
+    batches = lambda: bench.context_batches(0, nv, l, dv, ds, True, True, be.device)      # noqa: E731
+    with torch.no_grad():
+        fixed = inf.build_corpus_index(model, batches(), l_ref=l, n_videos=nv, exact_filter=True, length_buckets=False)
+        t0 = time.perf_counter()
+        mut = MutableCorpusIndex.from_batches(model, batches(), nv, l_ref=l, exact_rank=True)
+        torch.cuda.synchronize()
+        fill_s = time.perf_counter() - t0
+        qf, qm = bench.synth_queries(nq, dq, be.device)
+        kw = dict(n_valid_tokens=int(qm.sum().item()))
+        same_bound = [mut.exact.e_c[m] == fixed.exact.e_c[m] for m in mut.modalities]
+        rows = []
+        for rnd in ("", ", again"):
+            rows.append(("one-shot exact index" + rnd, timed(lambda: inf.vcmr_search(model, fixed, qf, qm, **kw), args.pass_reps, 2)))
+            rows.append(("mutable exact index" + rnd, timed(lambda: inf.vcmr_search(model, mut, qf, qm, **kw), args.pass_reps, 2)))
+        a = inf.vcmr_search(model, fixed, qf[:512], qm[:512])
+        b = inf.vcmr_search(model, mut, qf[:512], qm[:512])
+        same = all(bool(torch.equal(a[k], b[k])) for k in ("top_indices", "top_scores", "flat_indices", "flat_scores"))
+        g_fixed, g_mut = graph_ms(model, fixed, qf, qm), graph_ms(model, mut, qf, qm)
+        # (c) certificate failures per pass: the running bound, stale after removals, tightened
+        fails = [("one-shot index, its host e_c", int(inf.vcmr_search(model, fixed, qf, qm, **kw)["exact"]["n_fail"]), fixed.exact.e_c),
+                 ("mutable index right after the adds (running bound)", int(inf.vcmr_search(model, mut, qf, qm, **kw)["exact"]["n_fail"]),
+                  dict(mut.exact.e_c.items()))]
+        gone = np.random.default_rng(3).permutation(nv)[:nv // 10].tolist()
+        mut.remove(gone)
+        fails.append(("after removing %d slots (10 %%), bound left alone" % len(gone),
+                      int(inf.vcmr_search(model, mut, qf, qm, **kw)["exact"]["n_fail"]), dict(mut.exact.e_c.items())))
+        t_tight = timed(mut.tighten_error_bound, args.reps)
+        fails.append(("after tighten_error_bound()", int(inf.vcmr_search(model, mut, qf, qm, **kw)["exact"]["n_fail"]),
+                      dict(mut.exact.e_c.items())))
+    fa, fb = (rows[0][1][0] + rows[2][1][0]) / 2, (rows[1][1][0] + rows[3][1][0]) / 2
+    plain_bytes = sum(t.numel() * t.element_size() for d in (mut.feat1n, mut.feat2, mut.mask) for t in d.values())
+    lines += ["", "## (b) Search at the headline shape (%d videos x %d clips, full length, hidden %d, ops.F16S model)" % (nv, l, hidden),
+              "", "One-shot build_corpus_index(exact_filter=True, length_buckets=False): %.2f GB.  Mutable exact index at capacity = "
+              "n_videos: %.2f GB, filled by add() in %.1f s (encoder included).  The running bound equals the one-shot e_c bit for "
+              "bit: %s.  First 512 queries: video lists, weights, moment lists and scores are %s."
+              % (fixed.hbm_bytes() / 1e9, mut.hbm_bytes() / 1e9, fill_s, same_bound, "bitwise identical" if same else "NOT identical"),
+              "", "| index | vcmr_search, %d queries | 50-query graph replay |" % nq, "|---|---|---|"]
+    for i, (n, tm) in enumerate(rows):
+        lines.append("| %s | %s | %s |" % (n, fmt(tm), fmt((g_fixed, g_mut)[i & 1]) if i < 2 else ""))
+    lines += ["", "Price of mutability in exact-rank mode (medians, mean of both rounds): %.1f ms -> %.1f ms per %d-query pass "
+              "(%+.1f %%); 50-query replay %.3f ms -> %.3f ms (%+.1f %%).  The same kernels run on both; the mutable index adds the "
+              "live words to the candidate K8 and to select_ge_rows, K6 reads mask bits, K7 / K9 take the valid lengths."
+              % (fa, fb, nq, (fb / fa - 1) * 100, g_fixed[0], g_mut[0], (g_mut[0] / g_fixed[0] - 1) * 100),
+              "", "## (c) Certificate failures per %d queries" % nq, "", "| state | failing queries | e_c (video, sub) |", "|---|---|---|"]
+    lines += ["| %s | %d | %s |" % (n, f, ", ".join("%.6g" % ec[m] for m in mut.modalities)) for n, f, ec in fails]
+    lines += ["", "tighten_error_bound() over %d slots x %d rows x 2 modalities (one workgroup per modality): %s."
+              % (nv, mut.lpad, fmt(t_tight)),
+              "", "## (d) hbm_bytes()", "",
+              "Mutable exact index %.3f GB: filter image, feat2 and masks %.3f GB, re-score rows and the scales of the split rows "
+              "%.3f GB, err_rows + e_c_dev %.3f GB (ExactFilter.hbm_bytes_extra: %d bytes), the rest mask words, vlen, live, slot_ids."
+              % (mut.hbm_bytes() / 1e9, plain_bytes / 1e9,
+                 sum(t.numel() * 4 + t.inv.numel() * 4 for t in mut.exact.feat1n_f32.values()) / 1e9
+                 + sum(t.inv.numel() * 4 for t in mut.feat2.values()) / 1e9,
+                 mut.exact.hbm_bytes_extra() / 1e9, mut.exact.hbm_bytes_extra())]
+    for ln in lines[-24:]:
+        print(ln, flush=True)
+    del fixed, mut
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="put,putp,e2e,c3,c3r,c3rp")
@@ -600,8 +736,10 @@ def main():
     ap.add_argument("--pass-reps", type=int, default=5)
     ap.add_argument("--chains-l", type=int, default=128)
     ap.add_argument("--suite-wall", default="")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_update_timing.md"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:      # the exact leg has a report of its own
+        args.out = os.path.join(ROOT, "profiles", "index_exact_timing.md" if args.legs == "exact" else "index_update_timing.md")
     if not torch.cuda.is_available():
         sys.exit("bench_index_update.py measures on the GPU; none is visible")
     p = torch.cuda.get_device_properties(0)
@@ -625,6 +763,8 @@ def main():
         compact_leg(args, lines)
     if "chains" in legs:
         chains_leg(args, lines)
+    if "exact" in legs:
+        exact_leg(args, lines)
     if args.suite_wall:
         lines += ["", "## GPU test wall time", "", args.suite_wall]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -261,13 +261,21 @@ SIGNATURES_PARTS = {
     "xml_chain_best_rows": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# the companion header include/xmlhip_index_exact.h (tests/test_index_exact_capi.py checks): exact-rank mode on an updatable index
+SIGNATURES_EXACT = {
+    "xml_index_put_rows_exact": (c_int, [c_int] * 2 + [c_void_p] * 8 + [c_int] * 2 + [c_void_p] * 20 + [c_int] * 6 + [c_void_p]),
+    "xml_exact_certificate_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float,
+                                          c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "xml_index_exact_bound": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
 def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
-            list(SIGNATURES_PARTS.items()):
+            list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -23,6 +23,7 @@ import heapq
 import torch
 
 from . import _lib
+from . import inference as _inference
 from . import ops as hip_ops
 from .inference import CorpusIndex, index_lpad
 
@@ -659,24 +660,39 @@ class MutableCorpusIndex(CorpusIndex):
                  of the next part (-1), the part's first clip in the video; a free slot and a one-part video: (itself, -1, 0)
       table      a ChainTable; n_videos_live counts videos, n_live slots
     A video is numbered by its HEAD slot: add(..., parts=) returns it, slot_of(id) gives it, a caller's video_allow bit for
-    the video is the head's bit, out["top_videos"] lists it.  Chains are added, replaced and removed whole."""
+    the video is the head's bit, out["top_videos"] lists it.  Chains are added, replaced and removed whole.
+
+    Exact-rank mode, create(..., exact_rank=True) with an f32 or ops.F16S model: feat1n[m] is the bf16
+    FILTER image (tiled where ops.q2c_tiled_ok takes bf16 rows of that width, else row-major), feat2[m] f32 rows or
+    ops.SplitRows, and `exact` an inference.ExactFilter whose feat1n_f32[m] are the (capacity, lpad, H) re-score rows (f32 or
+    SplitRows), err_rows[m] the (capacity, lpad) rounding-error norm of every stored row and e_c_dev the (n_mod,) running
+    bound on the device: every put raises it (ops.index_put_rows_exact, one launch for all operands of the slots), the
+    certificate of a search reads it through a pointer.  remove leaves it alone -- a bound that is too large only sends more
+    queries to the second tier --; tighten_error_bound() recomputes it over the live slots.  Searches run the exact-rank
+    chains of inference under `live AND video_allow`; a GraphedVcmrSearch (ops.F16S model) stays valid across updates."""
 
     def __init__(self, *a, **kw):
         raise TypeError("use MutableCorpusIndex.create(model, capacity) or MutableCorpusIndex.from_batches(...)")
 
     @classmethod
     def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None,
-               auto_compact=False, part_overlap=None, max_parts=32):
+               auto_compact=False, part_overlap=None, max_parts=32, exact_rank=False):
         """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l).
         tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring).
         auto_compact (the packed form): an add / put / replace that finds no run although enough blocks are free runs
         compact() once and tries again.
         part_overlap=O (None: off, nothing changes): videos longer than l_ref clips are taken as CHAINS of slots (class
-        docstring), cut by ingest.plan_parts(n_clips, l_ref, overlap=O); max_parts bounds the parts of one video."""
+        docstring), cut by ingest.plan_parts(n_clips, l_ref, overlap=O); max_parts bounds the parts of one video.
+        exact_rank=True (an f32 or ops.F16S model; tiles=None, no part_overlap): exact-rank mode (class docstring) -- the
+        index holds the bf16 filter image, the f32-grade re-score rows and the running error bound, and searches return the
+        f32 path's lists."""
         dt = getattr(model, "compute_dtype", torch.float32)
-        if dt is hip_ops.F16S or exact_filter:
+        if exact_filter or (dt is hip_ops.F16S and not exact_rank):
             raise ValueError("MutableCorpusIndex: no exact-rank mode (an ops.F16S model / exact_filter=True) -- its certificate "
-                             "rests on e_c, a bound over the WHOLE corpus that a one-video update cannot maintain")
+                             "rests on e_c, a bound over the WHOLE corpus that a one-video update cannot maintain by value; "
+                             "create(..., exact_rank=True) keeps that bound on the device instead")
+        if exact_rank:
+            cls._check_exact_rank(model, dt, l_ref, tiles, part_overlap)
         if parts is not None:
             raise ValueError("MutableCorpusIndex: no parts table -- the fold of parts into videos is planned for a fixed corpus")
         if video_offset or n_total is not None:
@@ -692,7 +708,7 @@ class MutableCorpusIndex(CorpusIndex):
                 raise ValueError("MutableCorpusIndex: part_overlap must be a number of clips in [0, l_ref = %d), got %r"
                                  % (l_ref, part_overlap))
             table = ChainTable(capacity, max_parts)
-        act = getattr(model, "act_dtype", dt)
+        act = getattr(model, "act_dtype", hip_ops.act_dtype(dt))
         h = int(model.config.hidden_size)
         lpad = index_lpad(l_ref, model, hip_ops)
         if act not in (torch.float32, torch.bfloat16) or lpad > 128 or \
@@ -712,6 +728,8 @@ class MutableCorpusIndex(CorpusIndex):
         mods = [n for n, u in (("video", model.use_video), ("sub", model.use_sub)) if u]
         cap = table.capacity
         self = object.__new__(cls)
+        if exact_rank:
+            return self._init_exact(model, table, mods, l_ref, lpad, h, dev)
         feat2 = {m: torch.zeros((cap, lpad, h), dtype=act, device=dev) for m in mods}
         mask = {m: torch.zeros((cap, lpad), dtype=torch.float32, device=dev) for m in mods}
         self.blocks, self.codes, self.auto_compact = blocks, None, bool(auto_compact) and blocks is not None
@@ -733,6 +751,72 @@ class MutableCorpusIndex(CorpusIndex):
             else:
                 feat1n[m] = torch.zeros((cap, lpad, h), dtype=act, device=dev)
         CorpusIndex.__init__(self, mods, feat1n, feat2, mask, l_ref)
+        self._init_slot_state(model, table, l_ref, dev)
+        if part_overlap is not None:         # every slot in the single state: an add of short videos never touches these
+            self.part_overlap, self.max_parts = int(part_overlap), table.max_parts
+            self.chain_head = torch.arange(cap, dtype=torch.int32, device=dev)
+            self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+            self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
+        return self
+
+    @staticmethod
+    def _check_exact_rank(model, dt, l_ref, tiles, part_overlap):
+        """What create(..., exact_rank=True) refuses, before any device allocation."""
+        if tiles is not None:
+            raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) on the packed K6 image (tiles=%r) is not "
+                             "built -- the filter image, the re-score rows and the error norms are kept per slot; use "
+                             "tiles=None" % (tiles,))
+        if part_overlap is not None:
+            raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) and part_overlap= exclude each other -- "
+                             "exact-rank mode never forms the f32 (Nq, slots) score matrix that the best part of a video is "
+                             "taken from")
+        if dt is not hip_ops.F16S and dt != torch.float32:
+            raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) needs f32 activations (XML(cfg, "
+                             "compute_dtype=torch.float32 or ops.F16S)); got a %s model" % (dt,))
+        mode = _inference.exact_mode_of(model)
+        if mode == "f16s" and _inference.EXACT_F16S_FILTER != "bf16":
+            raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) builds the bf16 filter image only; "
+                             "inference.EXACT_F16S_FILTER is %r" % (_inference.EXACT_F16S_FILTER,))
+        h = int(model.config.hidden_size)
+        lpad = index_lpad(int(model.config.max_ctx_l if l_ref is None else l_ref), model, hip_ops)
+        if lpad > 128 or not _lib.load().xml_q2c_tile_rows_l2norm_ok(h, _lib.XML_F32) or (mode == "f16s" and h % 32):
+            raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True): xml_index_put_rows_exact takes f32 rows of up "
+                             "to 128 clips and a hidden size of whole 64-byte slices (a multiple of 32 for an ops.F16S "
+                             "model); got lpad %d, hidden %d" % (lpad, h))
+
+    def _init_exact(self, model, table, mods, l_ref, lpad, h, dev):
+        """The tensors of an exact-rank index (create(..., exact_rank=True)): allocated once, zero-filled."""
+        cap = table.capacity
+        mode = _inference.exact_mode_of(model)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)         # noqa: E731
+
+        def rows():          # f32-grade rows: f32, or split-f16 data + one inv_scale per row
+            if mode == "f16s":
+                return hip_ops.SplitRows(torch.zeros((cap, lpad, h), dtype=torch.int32, device=dev), f32(cap, lpad))
+            return f32(cap, lpad, h)
+        feat2 = {m: rows() for m in mods}
+        mask = {m: f32(cap, lpad) for m in mods}
+        self.blocks, self.codes, self.auto_compact = None, None, False
+        self.mask_bits = {m: torch.zeros((cap, 4), dtype=torch.int32, device=dev) for m in mods}
+        feat1n, bf16 = {}, torch.bfloat16
+        for m in mods:       # the bf16 FILTER image, in the layout create chooses for bf16 rows of this width
+            if hip_ops.q2c_tiled_ok(lpad, h, bf16):
+                data = torch.zeros(hip_ops.q2c_tiled_numel(cap * lpad, h, bf16), dtype=bf16, device=dev)
+                feat1n[m] = hip_ops.TiledRows(data, cap * lpad, h, (cap, lpad, h), all_valid=False)
+                feat1n[m].mask_bits = self.mask_bits[m]
+            else:
+                feat1n[m] = torch.zeros((cap, lpad, h), dtype=bf16, device=dev)
+        CorpusIndex.__init__(self, mods, feat1n, feat2, mask, l_ref)
+        cells = f32(len(mods))
+        self.exact = _inference.ExactFilter({m: rows() for m in mods}, _inference._DeviceBound(cells, mods), n_candidates=256,
+                                            mode=mode)
+        self.exact.e_c_dev, self.exact.err_rows = cells, {m: f32(cap, lpad) for m in mods}
+        self._init_slot_state(model, table, l_ref, dev)
+        return self
+
+    def _init_slot_state(self, model, table, l_ref, dev):
+        """The per-slot state every form of the index has: every slot free."""
+        cap = table.capacity
         self.raw_feat1 = {}
         self.vlen = torch.full((cap,), l_ref, dtype=torch.int32, device=dev)
         self.ragged = True                   # K7 / K9 always take vlen: the launch shape does not depend on the data
@@ -740,11 +824,14 @@ class MutableCorpusIndex(CorpusIndex):
         self.slot_ids = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         self.table = table
         self.model = model
-        if part_overlap is not None:         # every slot in the single state: an add of short videos never touches these
-            self.part_overlap, self.max_parts = int(part_overlap), table.max_parts
-            self.chain_head = torch.arange(cap, dtype=torch.int32, device=dev)
-            self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
-            self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
+
+    def tighten_error_bound(self):
+        """An exact-rank index: recompute the running bound e_c_dev as the maximum of err_rows over the LIVE slots (one launch,
+        nothing read back).  After removals the bound may be larger than the live rows need -- still valid, it only sends
+        more queries to the second tier -- and this makes it tight again."""
+        if self.exact is None:
+            raise ValueError("tighten_error_bound: not an exact-rank index (MutableCorpusIndex.create(..., exact_rank=True))")
+        hip_ops.index_exact_bound([self.exact.err_rows[m] for m in self.modalities], self.live.view(-1), self.exact.e_c_dev)
         return self
 
     @classmethod
@@ -864,15 +951,16 @@ class MutableCorpusIndex(CorpusIndex):
             a1, a2, am = enc[m]
             if a1.shape[0] != len(slots) or a1.shape[1] > self.l_ref:
                 raise ValueError("put: %d slots and l_ref = %d for a batch of shape %s" % (len(slots), self.l_ref, tuple(a1.shape)))
-        if self.blocks is not None:
+        if self.blocks is not None or self.exact is not None:
             b = len(slots)
             for m in mods:      # everything the put launch could refuse, before the clear launch of the moving videos
                 a1, a2, am = enc[m]
                 want = (b, a1.shape[1], self.feat2[m].shape[2])
-                if not (a1.is_cuda and a2.is_cuda and am.is_cuda) or a1.dtype != self.feat2[m].dtype or a2.dtype != a1.dtype or \
+                want_dt = torch.float32 if self.exact is not None else self.feat2[m].dtype
+                if not (a1.is_cuda and a2.is_cuda and am.is_cuda) or a1.dtype != want_dt or a2.dtype != a1.dtype or \
                         tuple(a1.shape) != want or tuple(a2.shape) != want or tuple(am.shape) != want[:2]:
                     raise ValueError("put: %s rows (b, lb, %d) of %s on the device and a (b, lb) mask expected"
-                                     % (m, want[2], self.feat2[m].dtype))
+                                     % (m, want[2], want_dt))
 
     def _launch_put(self, slots, ids, enc, nbs, runs, clears):
         """The launches of a validated put (the packed form: with the runs _find_runs returned, committed to the BlockTable
@@ -894,6 +982,15 @@ class MutableCorpusIndex(CorpusIndex):
             self.blocks.commit_put(slots, runs)
             return
         both = self._to_device([slots, ids])
+        if self.exact is not None:     # every operand of the slots and the running bound, one launch
+            ex = self.exact
+            hip_ops.index_put_rows_exact([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
+                                         [enc[m][2].float().contiguous() for m in mods], both[0], both[1],
+                                         [self.feat1n[m] for m in mods], [ex.feat1n_f32[m] for m in mods],
+                                         [self.feat2[m] for m in mods], [ex.err_rows[m] for m in mods],
+                                         [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], ex.e_c_dev,
+                                         self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
+            return
         hip_ops.index_put_rows([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
                                [enc[m][2].float().contiguous() for m in mods], both[0], both[1],
                                [self.feat1n[m] for m in mods], [self.feat2[m] for m in mods], [self.mask[m] for m in mods],

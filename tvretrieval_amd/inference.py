@@ -31,8 +31,9 @@ The split-f16 exact mode (split_f16_rows, SplitRows, F16_UNIT_LOG2), explain_mom
 records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and searches on an index of parts (group_best_allow,
 best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
 index_clear_rows) and the searches and updates of one with chains of slots for long videos (index_set_chains,
-chain_best_allow, chain_best_rows) call further entries of tvretrieval_amd.ops; a backend without them serves every search
-that does not ask for those.
+chain_best_allow, chain_best_rows) and the updates and searches of an exact-rank one (index_put_rows_exact,
+exact_certificate_dev, index_exact_bound) call further entries of tvretrieval_amd.ops; a backend without them serves every
+search that does not ask for those.
 """
 import numpy as np
 import torch
@@ -124,6 +125,8 @@ class CorpusIndex(object):
                 tot += t.numel() * t.element_size()
                 if hasattr(t, "inv"):
                     tot += t.inv.numel() * 4
+        if self.exact is not None:
+            tot += self.exact.hbm_bytes_extra()
         return tot
 
 
@@ -143,6 +146,54 @@ class ExactFilter(object):
         #               16-bit MFMA pipe (include/xmlhip.h "Exact-rank mode on the 16-bit pipe")
         self.tier2_rows = None        # capacity of the on-device second tier (None: sized from the batch); tests shrink it
         self.tier2_cap = 1024         # candidates per second-tier query
+        # an index that takes updates (index_update.MutableCorpusIndex.create(..., exact_rank=True)):
+        #   e_c_dev      (n_mod,) f32 device, the RUNNING bound: every put raises it (atomic max), the certificate reads it
+        #                through a pointer -- no update reads anything back, a captured search sees the bound of its replay;
+        #                e_c is then a read-back of these cells, for diagnostics only
+        #   err_rows[m]  (capacity, lpad) f32: the rounding-error norm of every stored row (tighten_error_bound)
+        # None on a one-shot index, whose e_c stays the host dict.
+        self.e_c_dev = self.err_rows = None
+
+    def hbm_bytes_extra(self):
+        """Bytes of the tensors only an updatable exact-rank index holds."""
+        if self.e_c_dev is None:
+            return 0
+        return self.e_c_dev.numel() * 4 + sum(t.numel() * 4 for t in self.err_rows.values())
+
+
+class _DeviceBound(object):
+    """ExactFilter.e_c of an updatable index: a mapping modality -> the float read back from e_c_dev (one small device ->
+    host copy per access; the search never uses it)."""
+
+    def __init__(self, cells, modalities):
+        self._cells, self._mods = cells, list(modalities)
+
+    def __getitem__(self, m):
+        return float(self._cells[self._mods.index(m)].item())
+
+    def keys(self):
+        return list(self._mods)
+
+    __iter__ = lambda self: iter(self._mods)
+    __len__ = lambda self: len(self._mods)
+
+    def items(self):
+        vals = self._cells.cpu().tolist()
+        return list(zip(self._mods, vals))
+
+
+def _exact_certificate(ex, mods, ops, cand_s, top_w, eq, hidden, alpha, outside, split):
+    """The certificate of an exact-rank search.  split (the split-f16 chain): three product sums per re-scored value, one per
+    filter value -- the f32 accumulation bound of each + the second-order terms of the two error norms (e_q e_c) the
+    first-order formula of xml_exact_certificate leaves out; else the f32 chain's exact_slack.  A one-shot index hands its
+    host e_c by value (xml_exact_certificate); an updatable one its device cells, and the slack's e_c term is evaluated in
+    the kernel (xml_exact_certificate_dev)."""
+    if ex.e_c_dev is not None:
+        base = 2.0 * exact_slack(hidden) + 2.0 ** -20 if split else exact_slack(hidden)
+        return ops.exact_certificate_dev(cand_s, top_w, eq, ex.e_c_dev, base, 4.0 if split else 0.0, alpha, outside)
+    ec = [ex.e_c[m] for m in mods]
+    slack = 2.0 * exact_slack(hidden) + 4.0 * max(ec) ** 2 + 2.0 ** -20 if split else exact_slack(hidden)
+    return ops.exact_certificate(cand_s, top_w, eq, ec, slack, alpha, outside)
 
 
 # Filter operand of the split-f16 exact mode.  The K6 kernel is power-limited and every mantissa bit of its operands costs
@@ -564,10 +615,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
     cand_r = ops.q2c_rescore(q_sr, rows_c, masks, cand_i)
     top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
     outside = index.n_videos > m_c
-    # three product sums per re-scored value, one per filter value: f32 accumulation bound of each + the second-order terms
-    # of the two error norms (e_q e_c) the first-order formula of xml_exact_certificate leaves out
-    slack = 2.0 * exact_slack(hidden) + 4.0 * max(ex.e_c[m] for m in mods) ** 2 + 2.0 ** -20
-    fail, eps, thr_all, n_fail = ops.exact_certificate(cand_s, top_w, eq, [ex.e_c[m] for m in mods], slack, alpha, outside)
+    fail, eps, thr_all, n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, hidden, alpha, outside, True)
     info = dict(fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s, cand_scores=cand_r,
                 n_candidates=m_c, n_fail_dev=n_fail, n_full_rows=0, overflow_dev=None)
     if outside:
@@ -646,8 +694,8 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
     f32rows = [ex.feat1n_f32[m] for m in mods]
     cand_r = ops.q2c_rescore(qn, f32rows, masks, cand_i)
     top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
-    fail, eps, thr_all, n_fail = ops.exact_certificate(cand_s, top_w, eq, [ex.e_c[m] for m in mods],
-                                                       exact_slack(qn[0].shape[1]), alpha, index.n_videos > m_c)
+    fail, eps, thr_all, n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, qn[0].shape[1], alpha,
+                                                    index.n_videos > m_c, False)
     nf = int(n_fail.item())        # (host sync: the launch shapes below depend on it)
     n_full = 0
     if nf:
@@ -1291,7 +1339,10 @@ class GraphedVcmrSearch(object):
     two eager warm-up passes before the capture; the corpus index and the model weights must not be re-allocated
     afterwards (re-create the object after load_state_dict / an optimizer step).  An index_update.MutableCorpusIndex never
     re-allocates and takes no data-dependent launch decision, so it may be updated (add / replace / remove) between replays:
-    the live words are read by the captured pass, and a replay after an update returns the updated result."""
+    the live words are read by the captured pass, and a replay after an update returns the updated result.  On an exact-rank
+    one (create(..., exact_rank=True), ops.F16S model) the captured certificate also reads the bound cells index.exact.e_c_dev:
+    replays depend on that tensor, like the live words, never being re-allocated (updates and tighten_error_bound() write it
+    in place)."""
 
     def __init__(self, model, index, nq, lq, d_in, video_allow_rows=None, **search_kwargs):
         """video_allow_rows = None | 1 | nq: a restricted search -- a static (rows, ceil(Nv / 32)) allow-word buffer (all videos

@@ -1614,3 +1614,124 @@ def chain_best_rows(scores, chains, video):
     check(_lib.load().xml_chain_best_rows(_p(scores), scores.stride(0) if rows else cap, rows, cap, _p(head), _p(nxt),
                                           int(chains.max_parts), _p(video), _p(out), _stream()), "xml_chain_best_rows")
     return out
+
+
+# ---- exact-rank mode on an updatable index (include/xmlhip_index_exact.h; MutableCorpusIndex.create(..., exact_rank=True)) ------
+EXACT_F32, EXACT_F16S = 0, 1          # XML_EXACT_F32 / XML_EXACT_F16S
+
+
+def _exact_sides(k6, rescore, feat2, err, imask, bits):
+    """Checks the per-modality tensors of an exact-rank slot; returns (capacity, lpad, hidden, tiled, mode, k6 buffers)."""
+    n_mod = len(feat2)
+    if n_mod not in (1, 2) or not (len(k6) == len(rescore) == len(err) == len(imask) == len(bits) == n_mod):
+        raise _lib.XmlHipError("exact index update: 1 or 2 modalities, the same number of k6 / rescore / feat2 / err / mask / "
+                               "bits tensors")
+    split = isinstance(feat2[0], SplitRows)
+    cap, lpad, hidden = (int(x) for x in feat2[0].shape)
+    tiled = isinstance(k6[0], TiledRows)
+    data = []
+    for m in range(n_mod):
+        for t, name in ((rescore[m], "rescore"), (feat2[m], "feat2")):
+            if isinstance(t, SplitRows) != split:
+                raise _lib.XmlHipError("exact index update: re-score rows and feat2 are all f32 tensors or all SplitRows")
+            if split:
+                _req(t.data, name, torch.int32); _req(t.inv, name + ".inv", torch.float32)
+                if tuple(t.inv.shape) != (cap, lpad):
+                    raise _lib.XmlHipError("exact index update: %s.inv (capacity, lpad) expected" % name)
+            else:
+                _req(t, name, torch.float32)
+            if tuple(t.shape) != (cap, lpad, hidden):
+                raise _lib.XmlHipError("exact index update: %s of shape %s expected" % (name, (cap, lpad, hidden)))
+        _req(err[m], "err", torch.float32); _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
+        if tuple(err[m].shape) != (cap, lpad) or tuple(imask[m].shape) != (cap, lpad) or tuple(bits[m].shape) != (cap, 4):
+            raise _lib.XmlHipError("exact index update: err / mask (capacity, lpad) and bits (capacity, 4) expected")
+        if isinstance(k6[m], TiledRows) != tiled:
+            raise _lib.XmlHipError("exact index update: the filter images of the modalities differ in layout")
+        d = k6[m].data if tiled else k6[m]
+        _req(d, "k6", torch.bfloat16)
+        if tiled:
+            if k6[m].shape != (cap, lpad, hidden) or lpad != 128 or d.numel() != q2c_tiled_numel(cap * lpad, hidden, d.dtype):
+                raise _lib.XmlHipError("exact index update: the tile image does not hold (capacity, 128, H) rows")
+        elif tuple(d.shape) != (cap, lpad, hidden):
+            raise _lib.XmlHipError("exact index update: row-major filter image of shape %s expected" % ((cap, lpad, hidden),))
+        data.append(d)
+    return cap, lpad, hidden, tiled, EXACT_F16S if split else EXACT_F32, data
+
+
+def index_put_rows_exact(f1, f2, masks, slots, ids, k6, rescore, feat2, err, imask, bits, ec, vlen, slot_ids, live, l_ref):
+    """xml_index_put_rows_exact: one encoded f32 context batch into its slots of an exact-rank index -- bf16 filter image,
+    re-score rows, feat2, rounding-error norms, mask, mask words, vlen, ids, live bits -- and the running bound ec raised; one
+    launch, nothing read back.  f1 / f2 / masks, slots, ids: as index_put_rows (f32).  k6: per-modality TiledRows or
+    (capacity, lpad, H) tensors, bf16; rescore / feat2: per-modality (capacity, lpad, H) f32 tensors (mode "f32") or SplitRows
+    (mode "f16s"); err (capacity, lpad) f32 per modality; ec (n_mod,) f32; the rest as index_put_rows."""
+    cap, lpad, hidden, tiled, mode, data = _exact_sides(k6, rescore, feat2, err, imask, bits)
+    _index_state(vlen, live, cap, slot_ids)
+    n_mod = len(feat2)
+    _req(ec, "ec", torch.float32)
+    if ec.numel() != n_mod:
+        raise _lib.XmlHipError("index_put_rows_exact: ec (n_mod,) f32 expected")
+    if not (len(f1) == len(f2) == len(masks) == n_mod):
+        raise _lib.XmlHipError("index_put_rows_exact: the batch holds %d modalities, the index %d" % (len(f1), n_mod))
+    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
+    for m in range(n_mod):
+        _req(f1[m], "f1", torch.float32); _req(f2[m], "f2", torch.float32); _req(masks[m], "mask", torch.float32)
+        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
+            raise _lib.XmlHipError("index_put_rows_exact: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected")
+    _req(slots, "slots", torch.int32)
+    if slots.numel() != b or (ids is not None and (_req(ids, "ids", torch.int32).numel() != b)):
+        raise _lib.XmlHipError("index_put_rows_exact: one slot (and id) per video of the batch")
+    split = mode == EXACT_F16S
+    side = []
+    for m in range(n_mod):
+        side += [_p(data[m]), _p(rescore[m]), _p(rescore[m].inv) if split else None, _p(feat2[m]),
+                 _p(feat2[m].inv) if split else None, _p(err[m]), _p(imask[m]), _p(bits[m])]
+    side += [None] * (16 - len(side))
+    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    check(_lib.load().xml_index_put_rows_exact(
+        n_mod, mode, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), b, lb, *side,
+        _p(ec), _p(vlen), _p(slot_ids), _p(live), cap, lpad, int(l_ref), hidden, XML_F32, int(tiled), _stream()),
+        "xml_index_put_rows_exact")
+
+
+def exact_certificate_dev(filter_scores, top_val, eq, ec, slack_base, slack_ec2, alpha, outside):
+    """exact_certificate with the corpus bound on the device: ec (n_mod,) f32 device tensor, read when the kernel runs (a
+    captured search sees the bound of its replay); slack = slack_base + slack_ec2 * max(ec)^2 in f32 in the kernel.
+    Returns (fail, eps, thr, n_fail) as exact_certificate."""
+    _req(filter_scores, "filter_scores", torch.float32); _req(top_val, "top_val", torch.float32)
+    n_mod = len(eq)
+    for e in eq:
+        _req(e, "eq", torch.float32)
+    _req(ec, "ec", torch.float32)
+    if ec.numel() != n_mod:
+        raise _lib.XmlHipError("exact_certificate_dev: ec (n_mod,) f32 expected")
+    nq, m = filter_scores.shape
+    k = top_val.shape[1]
+    dev = top_val.device
+    fail = torch.empty((nq,), dtype=torch.int32, device=dev)
+    eps = torch.empty((nq,), dtype=torch.float32, device=dev)
+    thr = torch.empty((nq,), dtype=torch.float32, device=dev)
+    n_fail = torch.zeros((1,), dtype=torch.int32, device=dev)
+    j = 1 if n_mod > 1 else 0
+    check(_lib.load().xml_exact_certificate_dev(_p(filter_scores), m, _p(top_val), k, _p(eq[0]), _p(eq[j]), _p(ec), n_mod,
+                                                float(slack_base), float(slack_ec2), float(alpha), int(bool(outside)),
+                                                _p(fail), _p(eps), _p(thr), _p(n_fail), nq, _stream()),
+          "xml_exact_certificate_dev")
+    return fail, eps, thr, n_fail
+
+
+def index_exact_bound(err, live, ec):
+    """xml_index_exact_bound: ec[m] = max of err[m] (capacity, lpad) over the slots whose live bit is set (0 when none is);
+    one launch, nothing read back."""
+    n_mod = len(err)
+    if n_mod not in (1, 2):
+        raise _lib.XmlHipError("index_exact_bound: 1 or 2 modalities")
+    cap, lpad = (int(x) for x in err[0].shape)
+    for e in err:
+        _req(e, "err", torch.float32)
+        if tuple(e.shape) != (cap, lpad):
+            raise _lib.XmlHipError("index_exact_bound: err (capacity, lpad) per modality expected")
+    _req(live, "live", torch.int32); _req(ec, "ec", torch.float32)
+    if live.numel() != (cap + 31) // 32 or ec.numel() != n_mod:
+        raise _lib.XmlHipError("index_exact_bound: live (ceil(capacity / 32),) int32 and ec (n_mod,) f32 expected")
+    check(_lib.load().xml_index_exact_bound(n_mod, _p(err[0]), _p(err[1]) if n_mod == 2 else None, _p(live), _p(ec), cap, lpad,
+                                            _stream()), "xml_index_exact_bound")
