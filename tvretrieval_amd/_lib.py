@@ -269,13 +269,19 @@ SIGNATURES_EXACT = {
     "xml_index_exact_bound": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
 }
 
+# the companion header include/xmlhip_index_view.h (tests/test_index_view_capi.py checks): subset views of a resident index
+SIGNATURES_VIEW = {
+    "xml_index_gather_blocks": (c_int, [c_int, c_void_p, c_int] + [c_void_p] * 4 + [c_int64] + [c_void_p] * 4 + [c_int] * 2 +
+                                [c_void_p]),
+}
+
 _lib = None
 
 
 def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
-            list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()):
+            list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

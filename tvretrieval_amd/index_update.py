@@ -638,6 +638,8 @@ class MutableCorpusIndex(CorpusIndex):
       slot_ids   (capacity,) int32 device, slot -> the caller's id: the meta2vid of a search that passes none
       mask_bits  {modality: (capacity, 4) int32}: K6's mask-bit operand (on the tiled layout also feat1n[m].mask_bits)
       n_live     host counter; table: the SlotTable
+      version    host counter, raised by every committed add / put / replace / remove (not by compact(), which moves blocks
+                 but changes no video): what a subset view (inference.video_subset) compares to know its copies are current
     n_videos == capacity: the kernels run over all slots.
 
     The packed form, create(..., tiles=N) (addendum): the K6 operand is the packed image of
@@ -824,6 +826,7 @@ class MutableCorpusIndex(CorpusIndex):
         self.slot_ids = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         self.table = table
         self.model = model
+        self.version = 0
 
     def tighten_error_bound(self):
         """An exact-rank index: recompute the running bound e_c_dev as the maximum of err_rows over the LIVE slots (one launch,
@@ -940,6 +943,7 @@ class MutableCorpusIndex(CorpusIndex):
             runs, clears = self._find_runs(slots, nbs, "put")
         self._launch_put(slots, ids, enc, nbs, runs, clears)
         self.table.commit_put(slots, ids)
+        self.version += 1
         return slots
 
     def _check_enc(self, slots, enc):
@@ -1125,6 +1129,8 @@ class MutableCorpusIndex(CorpusIndex):
             self.table.commit_remove_chains(plan)
         elif slots:
             self.table.commit_remove(slots)
+        if slots:
+            self.version += 1
         return slots
 
     # ---- long videos: chains of slots ---------------------------------------------------------------
@@ -1188,4 +1194,5 @@ class MutableCorpusIndex(CorpusIndex):
         self._launch_put(slots, plan["put_ids"], enc, nbs, runs, clears)
         self._set_chains(plan["records"])
         self.table.commit_chains(plan)
+        self.version += 1
         return plan["heads"]

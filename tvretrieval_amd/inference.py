@@ -32,8 +32,9 @@ records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and search
 best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
 index_clear_rows) and the searches and updates of one with chains of slots for long videos (index_set_chains,
 chain_best_allow, chain_best_rows) and the updates and searches of an exact-rank one (index_put_rows_exact,
-exact_certificate_dev, index_exact_bound) call further entries of tvretrieval_amd.ops; a backend without them serves every
-search that does not ask for those.
+exact_certificate_dev, index_exact_bound) and the subset views of video_subset (index_gather_blocks; HIP only, a search with
+subset= refuses any other backend) call further entries of tvretrieval_amd.ops; a backend without them serves every search
+that does not ask for those.
 """
 import numpy as np
 import torch
@@ -463,24 +464,67 @@ K7_SUMMARIES = False   # vcmr_search: K7 emits per-pair candidate summaries for 
 K6_TIMER = None   # bench.py: callable returning (start, end) torch.cuda.Event pair recorded around each K6 launch
 
 
-def _k6(index, qn, ops, normalize_q=False):
-    """One fused K6 launch over the local corpus (both modalities), bracketed by the bench's HIP events."""
+def _k6(index, qn, ops, normalize_q=False, subset=None):
+    """One fused K6 launch over the local corpus (both modalities), bracketed by the bench's HIP events.
+    subset (a subset.VideoSubset of this index): the launch runs xml_q2c_scores_packed over the VIEW's image, codes and mask
+    bits; the matrix keeps its (Nq, Nv) shape and only the columns of the view's videos are written."""
     mods = index.modalities
     ev = K6_TIMER() if K6_TIMER is not None else None
     if ev:
         ev[0].record()
-    q2c = ops.q2c_scores_fused(qn, [index.feat1n[m] for m in mods], [index.mask[m] for m in mods],
-                               normalize_q=normalize_q)
+    q2c = ops.q2c_scores_fused(qn, [(index.feat1n if subset is None else subset.k6)[m] for m in mods],
+                               [index.mask[m] for m in mods], normalize_q=normalize_q)
     if ev:
         ev[1].record()
     return q2c
 
 
-def stage_q2c(index, qvec, ops=hip_ops):
-    """K6 over the local corpus: (Nq, Nv_local) f32 = mean over modalities of max-over-clips cosine (one launch)."""
+def stage_q2c(index, qvec, ops=hip_ops, subset=None):
+    """K6 over the local corpus: (Nq, Nv_local) f32 = mean over modalities of max-over-clips cosine (one launch).
+    subset (video_subset): K6 over the view; the matrix is defined on the columns of the view's videos only."""
     if index.exact is not None:
         raise ValueError("this index is an exact-rank FILTER image (bf16 operands of an f32 model): use stage_exact_topk")
-    return _k6(index, [qvec[m].contiguous() for m in index.modalities], ops, normalize_q=True)
+    return _k6(index, [qvec[m].contiguous() for m in index.modalities], ops, normalize_q=True, subset=subset)
+
+
+def video_subset(index, allowed, tiles=None, n_clips=None):
+    """A subset view of a resident index (subset.VideoSubset): the K6 blocks of the allowed videos,
+    gathered on the device into a small packed image of their own, so that a search restricted to them --
+    vcmr_search(..., subset=view), stage_video_topk, vcmr_search_host, GraphedVcmrSearch -- pays K6 for those videos only and
+    returns bitwise what vcmr_search(..., video_allow=view.allow) returns.
+    allowed: a (Nv,) bool array / tensor or an ascending list of video numbers (slots of an index that takes updates).
+    tiles=None: exactly the tiles the placement needs; tiles=N: N tiles (room for view.reset(another set)).
+    n_clips (an index that takes updates, tiles=None form): the members' valid lengths, which saves the one host read.
+    Refused with a ValueError that names its reason: a parts index, chains of slots, a corpus shard, a parent whose K6 operand
+    is not the tiled image (lpad != 128, a hidden size or dtype xml_q2c_tiled_ok refuses), float non-binary masks."""
+    from .subset import VideoSubset
+    return VideoSubset(index, allowed, tiles=tiles, n_clips=n_clips)
+
+
+def _check_subset(subset, index, ops, external_top=None, pad_tail=False):
+    """What a search through a subset view refuses, before any launch, each with its reason."""
+    from . import subset as _subset
+    if ops is not hip_ops:
+        raise ValueError("subset=: a subset view is a HIP-only operand (xml_index_gather_blocks, xml_q2c_scores_packed); a "
+                         "non-HIP ops backend cannot search it")
+    if getattr(subset, "index", None) is not index:
+        raise ValueError("subset=: this is a view of another index -- its codes name that index's videos and its blocks are "
+                         "copies of that index's rows")
+    if external_top is not None:
+        raise ValueError("subset= and external_top exclude each other: a caller's video lists replace the ranking the view "
+                         "restricts (filter the lists instead)")
+    if pad_tail:
+        raise ValueError("subset= and pad_tail=True exclude each other: the reference-shaped tail would have to invent rows in "
+                         "the empty video slots of a restricted list")
+    _subset.check_parent(index)
+    subset.check_fresh()
+
+
+def _subset_allow(subset, video_allow):
+    """The allow rows of a search through a view: the view's row, ANDed with the caller's (1 or Nq rows)."""
+    if video_allow is None:
+        return subset.allow
+    return video_allow[:, :subset.allow.shape[1]] & subset.allow
 
 
 EXACT_TIER2_CAP = 4096        # second-tier candidates per failing query beyond which the f32 K6 row is computed instead
@@ -566,14 +610,17 @@ def _allow_rows(video_allow, rows):
     return video_allow.index_select(0, rows).contiguous()
 
 
-def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None):
-    """Exact-rank replacement of K6 + K8: dispatches on index.exact.mode (round-3 f32 re-score / split-f16 pipeline)."""
+def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None, subset=None):
+    """Exact-rank replacement of K6 + K8: dispatches on index.exact.mode (round-3 f32 re-score / split-f16 pipeline).
+    subset (video_subset; video_allow must then carry the view's row): the FILTER pass runs over the view's image -- the
+    filter matrix (info["q2c_filter"]) is defined on the view's columns only, which is all a selection under the allow row
+    reads; the re-score operands and the tiers behind the filter are the parent's."""
     if index.exact.mode == "f16s":
-        return stage_exact_topk_f16s(index, qvec, k, alpha, ops, defer_check, video_allow)
-    return stage_exact_topk_f32(index, qvec, k, alpha, ops, video_allow)
+        return stage_exact_topk_f16s(index, qvec, k, alpha, ops, defer_check, video_allow, subset)
+    return stage_exact_topk_f32(index, qvec, k, alpha, ops, video_allow, subset)
 
 
-def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None):
+def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None, subset=None):
     """The exact-rank chain on the 16-bit MFMA pipe, with no host read-back on the common path (capturable):
       1. q normalised (f32) and split: hi plane (f16) -> K6 FILTER over the corpus's hi planes; rounding-error norms e_q;
       2. K8: the M best filter scores per query (M = 128: the f16 filter's error bound is 8x tighter than bf16's);
@@ -608,7 +655,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
             hi, e = ops.round_bf16_rows_err(qn)
         q_sr.append(sr), q_hi.append(hi), eq.append(e)
     nq, hidden = q_hi[0].shape
-    filt = _k6(index, q_hi, ops)
+    filt = _k6(index, q_hi, ops, subset=subset)
     m_c = min(ex.n_candidates, index.n_videos)
     cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
     rows_c = [ex.feat1n_f32[m] for m in mods]                    # SplitRows (Nv, lpad, H)
@@ -664,7 +711,7 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
     return top_w, top_i, info
 
 
-def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
+def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None, subset=None):
     """Exact-rank replacement of K6 + K8 (index.exact is set, f32 query vectors): the f32 path's top-k videos per query.
       1. q_b = rne_bf16(normalize(q)) with its rounding-error norm e_q; bf16 K6 over the filter image (the timed K6);
       2. K8 proposes the M best filter scores per query (raw values + ids);
@@ -688,7 +735,7 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None):
     for q in qn:
         b, e = ops.round_bf16_rows_err(q)
         qb.append(b), eq.append(e)
-    filt = _k6(index, qb, ops)
+    filt = _k6(index, qb, ops, subset=subset)
     m_c = min(ex.n_candidates, index.n_videos)
     cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
     f32rows = [ex.feat1n_f32[m] for m in mods]
@@ -829,12 +876,16 @@ def pad_moment_tail(flat_scores, flat_indices, k_videos, l_ref, min_pred_l=None,
 
 
 def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops=hip_ops, external_top=None,
-                     defer_exact_check=False, video_allow=None):
+                     defer_exact_check=False, video_allow=None, subset=None):
     """K6 + K8 (or the exact-rank chain, or a caller's video lists): (q2c or None, top_w (Nq, K) f32 = exp(alpha s) desc,
     top_i (Nq, K) int32, exact-rank info or None).  Per query independent of the rest of the batch.
     video_allow (pack_video_allow's words, 1 or Nq rows, on the device): every query's list is the list of the corpus that
     holds only its allowed videos (indices in this index's numbering); a query with a < K of them ends in K - a empty slots
     (top_i -1, top_w 0, or -inf when alpha == 0), which yield no moments.  K6 still scores every video.
+    subset (video_subset(index, allowed)): the same lists as video_allow=subset.allow, bitwise, but K6 runs over the view's
+    packed image -- its cost follows the allowed videos.  The allow row is the view's, ANDed with a caller's video_allow (1 or
+    Nq rows) and with index.live; the returned q2c matrix (the exact-rank filter matrix alike) is defined on the columns of the
+    view's videos only -- the others are never written.  subset=None is the path above, unchanged.
     A parts index: K6, then ops.group_best_allow (each video's best part AND the caller's mask over source videos), then K8 under
     those bits -- top_i are index rows, one per video; slots beyond the number of allowed videos are empty.
     An index that takes updates (index.live): the allow words are ANDed with the live words -- one small (rows, words) int32
@@ -842,11 +893,15 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
     One with chains (index.chain_head): K6, then ops.chain_best_allow under those words (each video's best part; a caller's
     video_allow bit for a video is the bit of its HEAD slot), then K8 under the fold's bits -- top_i are slots, one per video."""
     exact = None
+    if subset is not None:
+        _check_subset(subset, index, ops, external_top)
     if video_allow is not None:
         if external_top is not None:
             raise ValueError("video_allow and external_top exclude each other: a caller's video lists replace the ranking "
                              "the mask restricts (filter the lists instead)")
         _check_video_allow(video_allow, index, qvec[index.modalities[0]].shape[0])
+    if subset is not None:
+        video_allow = _subset_allow(subset, video_allow)
     if index.live is not None and external_top is None:
         video_allow = index.live if video_allow is None else video_allow[:, :index.live.shape[1]] & index.live
     if index.chain_head is not None:
@@ -868,9 +923,9 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
         # defer_exact_check (split-f16 exact mode): no host read-back inside the pass; out["exact"]["overflow_dev"] (device
         # bool, None when every video is a candidate) says whether the on-device second tier's capacity was exceeded
         top_w, top_i, exact = stage_exact_topk(index, qvec, min(max_vcmr_video, index.n_videos), q2c_alpha, ops,
-                                               bool(defer_exact_check), video_allow)
+                                               bool(defer_exact_check), video_allow, subset)
     elif external_top is None:
-        q2c = stage_q2c(index, qvec, ops)
+        q2c = stage_q2c(index, qvec, ops, subset)
         k = min(max_vcmr_video, index.n_videos)
         top_w, top_i = ops.topk_rows(q2c, k, alpha=q2c_alpha, allow=video_allow)
     else:   # external video-retrieval results replace K6/K8 (xml/inference.py:349-355): (meta idx int32, exp(alpha*s))
@@ -901,7 +956,7 @@ def stage_moments(model, index, qvec, top_w, top_i, min_pred_l=2, max_pred_l=16,
 def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_before_nms=200, q2c_alpha=20.0,
                 min_pred_l=2, max_pred_l=16, svmr_video=None, ops=hip_ops, external_top=None, pad_tail=False,
                 defer_exact_check=False, n_valid_tokens=None, video_allow=None, nms_thd=None, max_after_nms=100,
-                meta2vid=None, clip_length=1.5):
+                meta2vid=None, clip_length=1.5, subset=None):
     """Device part of compute_query2ctx_info for one query batch (xml/inference.py:308-386), single GPU.
 
     Returns device tensors:
@@ -916,6 +971,12 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     video_allow (pack_video_allow: (1 | Nq, ceil(Nv / 32)) int32 words on the device): the search restricted to each query's
     allowed videos -- exactly the unrestricted result on the corpus of those videos, in this index's numbering (see
     stage_video_topk for queries with fewer than K allowed videos).  Not with external_top or pad_tail=True.
+    subset (video_subset(index, allowed)): the search restricted to the view's videos -- bitwise the result of
+    video_allow=subset.allow (ANDed with video_allow when both are given), with K6 over the view's own packed image instead of
+    the corpus.  out["q2c"] (out["exact"]["q2c_filter"] on an exact-rank index) is defined on the columns of the view's videos
+    only; everything behind K6 runs on the index unchanged.  Refused with a ValueError before any launch: a view of another
+    index, a stale view (the index was updated: view.refresh()), external_top, pad_tail=True, a non-HIP ops; see video_subset
+    for the indexes that take no view.
     nms_thd (None: off): the search ends in the FINAL list on the device -- K10 (xml_moments_decode, meta2vid / clip_length as
     in vcmr_search_host) and temporal NMS (xml_nms_moments) follow on the same stream.  out additionally holds records /
     record_count (K10 of flat_scores / flat_indices: (Nq, n, 4) int32 xml_moment rows in seconds, (Nq,) int32) and nms_records
@@ -934,6 +995,8 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     is also the bit a caller's video_allow carries for the video; svmr_video names a video by any of its slots; records carry
     the video's id (slot_ids) and whole-video times (chain_offset).  Refused alike: external_top, pad_tail=True, max_pred_l >
     part_overlap."""
+    if subset is not None:
+        _check_subset(subset, index, ops, external_top, pad_tail)
     if video_allow is not None and pad_tail:
         raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
                          "rows in the empty video slots of a restricted list")
@@ -955,7 +1018,7 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     qvec = stage_query_vectors(model, query_feat, query_mask, n_valid_tokens)
     forked = fork_query_linears(model, index, qvec, ops) if not K7_SUMMARIES else None
     q2c, top_w, top_i, exact = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, external_top,
-                                                defer_exact_check, video_allow)
+                                                defer_exact_check, video_allow, subset)
     q_lin = None
     if forked is not None:
         q_lin, lin_done = forked
@@ -1155,7 +1218,7 @@ def host_chunks(nq, first=1024, growth=3, largest=16384):
 def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, meta2vid=None, chunk=1024, lq=None,
                      clip_length=1.5, buffers=None, timings=None, ops=hip_ops, max_vcmr_video=100, max_before_nms=200,
                      q2c_alpha=20.0, min_pred_l=2, max_pred_l=16, pad_tail=False, chunk_growth=3, wait=True, video_allow=None,
-                     nms_thd=None, max_after_nms=100):
+                     nms_thd=None, max_after_nms=100, subset=None):
     """VCMR from host memory to host memory: the path of the reference's query loop (xml/inference.py:302-314 moves every
     batch host -> device, :383-386 moves the lists device -> host; start_end_dataset.py:362-370) for a whole query set.
 
@@ -1180,6 +1243,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     is the caller's to take).
     video_allow: DEVICE-resident allow words (pack_video_allow), 1 row or one per query of the whole set; every chunk uses
     its own rows.  Not with pad_tail=True.
+    subset (video_subset(index, allowed)): every chunk's K6 runs over the view (see vcmr_search); the records are those of
+    video_allow=subset.allow.
     nms_thd (None: off, the records are the pre-NMS lists): temporal NMS per video (filter_vcmr_by_nms at this threshold, first
     max_before_nms candidates in, at most max_after_nms out) runs on the device behind K10 (xml_nms_moments, same stream); the
     pinned buffer and the device -> host copy then carry (Nq, max_after_nms) records -- the kept ones, best first, {-1, 0, 0, 0}
@@ -1187,6 +1252,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     from .results import MOMENT_DTYPE
     import time as _time
     t_enter = _time.perf_counter()
+    if subset is not None:
+        _check_subset(subset, index, ops, None, pad_tail)
     dev = next(model.parameters()).device
     ragged = row_start is not None
     nq = (row_start.numel() - 1) if ragged else query_feat.shape[0]
@@ -1286,7 +1353,8 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
             done.record(main)                            # the staging set is free once the query encoder has read it
             freed[c & 1] = done
             allow = video_allow if (video_allow is None or video_allow.shape[0] == 1) else video_allow[b:e]
-            _, tw, ti, _ = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, video_allow=allow)
+            _, tw, ti, _ = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, video_allow=allow,
+                                            subset=subset)
             qvecs.append(qvec), tws.append(tw), tis.append(ti)
         one = len(bounds) == 1
         qvec = {m: (qvecs[0][m] if one else torch.cat([q[m] for q in qvecs])) for m in qvecs[0]}
@@ -1342,7 +1410,10 @@ class GraphedVcmrSearch(object):
     the live words are read by the captured pass, and a replay after an update returns the updated result.  On an exact-rank
     one (create(..., exact_rank=True), ops.F16S model) the captured certificate also reads the bound cells index.exact.e_c_dev:
     replays depend on that tensor, like the live words, never being re-allocated (updates and tighten_error_bound() write it
-    in place)."""
+    in place).
+    subset=view (video_subset): the captured pass bakes in the view's n_tiles and the pointers of its image, codes, mask words
+    and allow row; view.reset(another set) / view.refresh() rewrite those buffers in place, so the next replay searches the
+    new set.  A call through a stale view raises ValueError, as the eager search does."""
 
     def __init__(self, model, index, nq, lq, d_in, video_allow_rows=None, **search_kwargs):
         """video_allow_rows = None | 1 | nq: a restricted search -- a static (rows, ceil(Nv / 32)) allow-word buffer (all videos
@@ -1396,6 +1467,8 @@ class GraphedVcmrSearch(object):
             raise ValueError("GraphedVcmrSearch was captured for queries %s / masks %s, got %s / %s"
                              % (tuple(self.query_feat.shape), tuple(self.query_mask.shape), tuple(query_feat.shape),
                                 tuple(query_mask.shape)))
+        if self._kw.get("subset") is not None:
+            self._kw["subset"].check_fresh()
         if video_allow is not None:
             if self.video_allow is None:
                 raise ValueError("GraphedVcmrSearch was captured without a video mask (video_allow_rows=None)")

@@ -1533,6 +1533,47 @@ def index_move_blocks_packed(records, k6, bits, codes):
           "xml_index_move_blocks_packed")
 
 
+# ---- subset views of a resident index (include/xmlhip_index_view.h; tvretrieval_amd/subset.py) --------------------------------
+def index_gather_blocks(src_block, k6_src, bits_src, n_blocks_src, k6_dst, bits_dst, hidden):
+    """xml_index_gather_blocks: the 16-row blocks named by src_block (16 * n_tiles_dst int32 device, one per DESTINATION block:
+    a source block >= 0, or -2 = unused; anything out of range counts as -2) are copied out of the resident K6 image(s) k6_src
+    into the packed image(s) k6_dst, with their 16 mask bits per modality.  k6_src / k6_dst: per-modality flat tile images
+    (TiledRows.data) of one dtype, the source holding at least ceil(n_blocks_src / 16) tiles, the destination exactly
+    n_tiles_dst; bits_src: per modality the source's packed mask words (int32, at least ceil(n_blocks_src / 2) of them) or None =
+    that modality is all-valid; bits_dst: per-modality (2 * n_tiles_dst, 4) int32, every word of which is written.  Source
+    and destination must not overlap.  One launch, nothing read back."""
+    n_mod = len(k6_src)
+    if n_mod not in (1, 2) or not (len(bits_src) == len(k6_dst) == len(bits_dst) == n_mod):
+        raise _lib.XmlHipError("index_gather_blocks: 1 or 2 modalities, one source image, source bits (or None), destination "
+                               "image and destination bits each")
+    _req(src_block, "src_block", torch.int32)
+    n_blocks_src, hidden = int(n_blocks_src), int(hidden)
+    if src_block.dim() != 1 or not src_block.numel() or src_block.numel() % 16 or n_blocks_src <= 0:
+        raise _lib.XmlHipError("index_gather_blocks: src_block (16 * n_tiles_dst,) int32 and n_blocks_src >= 1 expected")
+    n_tiles = int(src_block.numel()) // 16
+    dt = k6_src[0].dtype
+    if not q2c_tiled_ok(128, hidden, dt):
+        raise _lib.XmlHipError("index_gather_blocks: the tiled K6 kernel takes no %s rows of hidden size %d" % (dt, hidden))
+    per_tile = q2c_tiled_numel(256, hidden, dt)
+    for m in range(n_mod):
+        _req(k6_src[m], "k6_src", dt); _req(k6_dst[m], "k6_dst", dt); _req(bits_dst[m], "bits_dst", torch.int32)
+        if k6_src[m].numel() < (n_blocks_src + 15) // 16 * per_tile:
+            raise _lib.XmlHipError("index_gather_blocks: the source image holds fewer than n_blocks_src = %d blocks" % n_blocks_src)
+        if k6_dst[m].numel() != n_tiles * per_tile or tuple(bits_dst[m].shape) != (2 * n_tiles, 4):
+            raise _lib.XmlHipError("index_gather_blocks: a destination image of n_tiles_dst * 256 = %d rows and bits "
+                                   "(2 * n_tiles_dst, 4) expected" % (n_tiles * 256))
+        if bits_src[m] is not None:
+            _req(bits_src[m], "bits_src", torch.int32)
+            if bits_src[m].numel() < (n_blocks_src + 1) // 2:
+                raise _lib.XmlHipError("index_gather_blocks: the source mask words cover fewer than n_blocks_src = %d blocks"
+                                       % n_blocks_src)
+    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    check(_lib.load().xml_index_gather_blocks(n_mod, _p(src_block), n_tiles, _p(k6_src[0]), _p(bits_src[0]), sec(k6_src),
+                                              sec(bits_src), n_blocks_src, _p(k6_dst[0]), _p(bits_dst[0]), sec(k6_dst),
+                                              sec(bits_dst), hidden, dt_of(k6_src[0]), _stream()),
+          "xml_index_gather_blocks")
+
+
 # ---- long videos as chains of slots (include/xmlhip_index_parts.h; MutableCorpusIndex(part_overlap=O)) ------------------------
 def _chain_tables(tables, names, what):
     """The (capacity,) int32 chain tables `names` of an index (or of any object that carries them) and its max_parts."""
