@@ -22,7 +22,8 @@
 //                             reaches T_k - eps_q (the re-scored k-th value is a lower bound of the final one, so nothing
 //                             below that line can enter the top-k) -- usually a few dozen more than M; they are re-scored
 //                             like the first M and the lists re-selected, no second certificate needed.
-#include "common.h"
+#include "../../include/xmlhip_index_exact.h"
+#include "index_rows.h"
 
 namespace {
 
@@ -38,27 +39,41 @@ __global__ __launch_bounds__(256) void round_bf16_rows_err_kernel(const float* _
   for (int c = lane * 8; c < d; c += 64 * 8) {
     float f[8];
     ld8<float>(px + c, f);
-    const uint4 packed = pack16<bf16_t>(f);
-    float g[8];
-    unpack16<bf16_t>(packed, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float dlt = f[e] - g[e];          // exact in f32 (Sterbenz-like: g is f rounded to 8 significant bits)
-      s += dlt * dlt;
-    }
-    *reinterpret_cast<uint4*>(pb + c) = packed;
+    *reinterpret_cast<uint4*>(pb + c) = round_bf16_err8(f, s);
   }
   s = wave_sum(s);
   if (lane == 0) err[row] = sqrtf(s);
 }
 
+// where the certificate takes the corpus bound from: the caller's values ...
+struct BoundByValue {
+  float ec0, ec1, slack;
+  __device__ void get(int n_mod, float& e0, float& e1, float& sl) const { e0 = ec0, e1 = ec1, sl = slack; }
+};
+// ... or the device cells the exact put maintains (xml_exact_certificate_dev, include/xmlhip_index_exact.h), read when the
+// kernel runs; slack = slack_base + slack_ec2 * max(ec)^2
+struct BoundOnDevice {
+  const float* ec;
+  float slack_base, slack_ec2;
+  __device__ void get(int n_mod, float& e0, float& e1, float& sl) const {
+    e0 = ec[0], e1 = n_mod == 2 ? ec[1] : ec[0];
+    const float ecm = fmaxf(e0, e1);
+    // no product without a coefficient: 0 * inf^2 would be a NaN, and a cell at +inf (a NaN norm was put) must give
+    // eps = +inf, thr = -inf -- every certificate fails and the second tier takes every video -- in both modes
+    sl = slack_ec2 != 0.f ? slack_base + slack_ec2 * (ecm * ecm) : slack_base;
+  }
+};
+
+template <typename BOUND>
 __global__ void exact_certificate_kernel(const float* __restrict__ filt, int m, float* __restrict__ top_val, int k,
-                                         const float* __restrict__ eq0, const float* __restrict__ eq1, float ec0,
-                                         float ec1, int n_mod, float slack, float alpha, int outside,
-                                         int32_t* __restrict__ fail, float* __restrict__ eps_out,
-                                         float* __restrict__ thr_out, int32_t* __restrict__ n_fail, int nq) {
+                                         const float* __restrict__ eq0, const float* __restrict__ eq1, BOUND bound,
+                                         int n_mod, float alpha, int outside, int32_t* __restrict__ fail,
+                                         float* __restrict__ eps_out, float* __restrict__ thr_out,
+                                         int32_t* __restrict__ n_fail, int nq) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;
+  float ec0, ec1, slack;
+  bound.get(n_mod, ec0, ec1, slack);
   const float c_norm = 1.f + 1e-6f;                       // | c | of an f32-normalised row
   float eps = eq0[q] * c_norm + (c_norm + eq0[q]) * ec0;
   if (n_mod == 2) eps = (eps + eq1[q] * c_norm + (c_norm + eq1[q]) * ec1) * 0.5f;
@@ -160,9 +175,24 @@ extern "C" int xml_exact_certificate(const float* filter_scores, int m, float* t
   XML_ENTER();
   if (!filter_scores || !top_val || !eq0 || !fail || !n_fail || nq <= 0 || m <= 0 || k <= 0 || k > m) return XML_ERR_BAD_ARG;
   if (n_mod < 1 || n_mod > 2 || (n_mod == 2 && !eq1)) return XML_ERR_BAD_ARG;
-  hipLaunchKernelGGL(exact_certificate_kernel, dim3(cdiv(nq, 128)), dim3(128), 0, (hipStream_t)stream, filter_scores, m,
-                     top_val, k, eq0, eq1 ? eq1 : eq0, ec0, ec1, n_mod, slack, alpha, outside, fail, eps_out, thr_out, n_fail,
-                     nq);
+  hipLaunchKernelGGL(exact_certificate_kernel<BoundByValue>, dim3(cdiv(nq, 128)), dim3(128), 0, (hipStream_t)stream,
+                     filter_scores, m, top_val, k, eq0, eq1 ? eq1 : eq0, BoundByValue{ec0, ec1, slack}, n_mod, alpha, outside,
+                     fail, eps_out, thr_out, n_fail, nq);
+  XML_CHECK_LAUNCH();
+  return XML_OK;
+}
+
+extern "C" int xml_exact_certificate_dev(const float* filter_scores, int m, float* top_val, int k, const float* eq0,
+                                         const float* eq1, const float* ec, int n_mod, float slack_base, float slack_ec2,
+                                         float alpha, int outside, int32_t* fail, float* eps_out, float* thr_out,
+                                         int32_t* n_fail, int nq, xml_stream_t stream) {
+  XML_ENTER();
+  if (!filter_scores || !top_val || !eq0 || !ec || !fail || !n_fail || nq <= 0 || m <= 0 || k <= 0 || k > m)
+    return XML_ERR_BAD_ARG;
+  if (n_mod < 1 || n_mod > 2 || (n_mod == 2 && !eq1)) return XML_ERR_BAD_ARG;
+  hipLaunchKernelGGL(exact_certificate_kernel<BoundOnDevice>, dim3(cdiv(nq, 128)), dim3(128), 0, (hipStream_t)stream,
+                     filter_scores, m, top_val, k, eq0, eq1 ? eq1 : eq0, BoundOnDevice{ec, slack_base, slack_ec2}, n_mod, alpha,
+                     outside, fail, eps_out, thr_out, n_fail, nq);
   XML_CHECK_LAUNCH();
   return XML_OK;
 }

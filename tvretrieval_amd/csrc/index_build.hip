@@ -1,8 +1,9 @@
 // Corpus index build, last step: L2-normalise the clip rows of feat1 (F.normalize, xml/model_xml.py:447-448) and write them
-// straight into K6's slice-major tile image ([tile of 256 rows][64-byte K slice][row][64 B], see q2c_persist.hip) -- one
+// straight into K6's slice-major tile image ([tile of 256 rows][64-byte K slice][row][64 B], index_rows.h) -- one
 // pass over the index instead of l2norm_rows (read + write) followed by tile_rows (read + write).  Optionally through a
 // row map (the length-bucketed image of ragged corpora: destination row i = source row row_map[i], zeros when < 0).
 // The arithmetic is l2norm.h's: bitwise the values the two separate kernels produce.
+#include "index_rows.h"
 #include "l2norm.h"
 
 namespace {
@@ -21,12 +22,11 @@ __global__ __launch_bounds__(256) void tile_rows_l2norm_kernel(const T* __restri
   if (drow >= rows_dst) return;
   const int chunks = d / VEC;
   const int slices = chunks >> 2;                                          // 64-byte slices per row
-  char* tile = reinterpret_cast<char*>(dst) + (drow >> 8) * (int64_t)slices * (256 * 64) + (drow & 255) * 64;
 #pragma unroll
   for (int j = 0; j < L2N_MAXJ; ++j) {
     const int c = l32 + 32 * j;
-    if (c < chunks)       // chunk c = piece c & 3 of slice c >> 2; a missing row stays zero (0 / 1e-12 = 0)
-      *reinterpret_cast<uint4*>(tile + (int64_t)(c >> 2) * (256 * 64) + (c & 3) * 16) = l2n_scale_chunk<T>(v[j], nrm);
+    if (c < chunks)       // a missing row stays zero (0 / 1e-12 = 0)
+      *reinterpret_cast<uint4*>(k6img::row_chunk(reinterpret_cast<char*>(dst), drow, slices, c)) = l2n_scale_chunk<T>(v[j], nrm);
   }
 }
 

@@ -15,17 +15,16 @@
 // wave's outstanding vector loads, the LDS write (which needs the loaded value) does.  The same holds for codes and bits.
 // A record whose tile is outside [0, n_tiles) or with a src outside {-2, -1} u [0, 16 n_tiles) is dropped whole.
 #include "../../include/xmlhip_index_compact.h"
-#include "common.h"
+#include "index_rows.h"
 
 namespace {
 
 constexpr int REC = 17;                 // int32 per record
-constexpr int CHUNK = 16 * 1024;        // bytes of one (tile, slice): 256 rows of 64 bytes; a block is 1 KiB of it
 
 __global__ __launch_bounds__(256) void index_move_blocks_packed_kernel(
     const int32_t* __restrict__ records, char* k6_a, int32_t* bits_a, char* k6_b, int32_t* bits_b, int32_t* codes,
     int n_tiles, int slices) {
-  __shared__ uint4 stage[CHUNK / 16];
+  __shared__ uint4 stage[k6img::CHUNK_BYTES / 16];      // one (tile, slice) chunk
   __shared__ int s_code[16];
   __shared__ unsigned int s_bits[16];
   // the record: ONE vector load per wave, lane j < 17 holds word j (17 dependent scalar loads cost 17 latencies)
@@ -40,17 +39,11 @@ __global__ __launch_bounds__(256) void index_move_blocks_packed_kernel(
   const int slice = blockIdx.x;
 
   // ---- the image: chunk (tile, slice); wave w owns blocks w + 4 i, a lane 16 bytes of each
-  const int64_t tile_bytes = (int64_t)slices * CHUNK;
-  char* dst_chunk = k6 + (int64_t)tile * tile_bytes + (int64_t)slice * CHUNK;
+  char* dst_chunk = k6img::block_slice(k6, (int64_t)tile * 16, slices, slice);
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   int src[4];
   uint4 v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) src[i] = __builtin_amdgcn_readlane(word, 1 + wave + 4 * i);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)                                      // the four loads of a thread are in flight together
-    if (src[i] >= 0)
-      v[i] = ld_global16(k6 + (int64_t)(src[i] >> 4) * tile_bytes + (int64_t)slice * CHUNK + (src[i] & 15) * 1024 + (t & 63) * 16);
+  k6img::load_wave_blocks(k6, word, 1, wave, slices, slice, lane, src, v);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
     if (src[i] >= 0) stage[(wave + 4 * i) * 64 + (t & 63)] = v[i];
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(256) void index_move_blocks_packed_kernel(
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (src[i] >= 0) st_global16(dst_chunk + (wave + 4 * i) * 1024 + (t & 63) * 16, stage[(wave + 4 * i) * 64 + (t & 63)]);
+    if (src[i] >= 0) st_global16(dst_chunk + (wave + 4 * i) * k6img::BLOCK_BYTES + (t & 63) * 16, stage[(wave + 4 * i) * 64 + (t & 63)]);
   if (!tables) return;
   if (t < 8) reinterpret_cast<unsigned int*>(second ? bits_b : bits_a)[tile * 8 + t] = s_bits[2 * t] | s_bits[2 * t + 1] << 16;
   if (!second && mine != -1) {

@@ -7,16 +7,16 @@
 //                                                     order, wave_sum, sqrtf -- hence one wave per clip row here
 //   re-score rows  y (f32) or split-f16 at 2^14       split16.h, the functions xml_split_f16_rows runs
 //   feat2          the f2 row (f32) or split-f16 at the row's own scale
-//   mask row, mask-bit words, vlen, id, live bit     index_put_rows_kernel's block-0 code (index_update.hip)
+//   mask row, mask-bit words, vlen, id, live bit     the slot-state epilogue of every put (index_rows.h)
 // and raises the running bound ec[modality] by atomicMax on the bits of every err value.
 // One wave per clip row, four rows per block.  The normalisation wants the row in l2norm.h's lane order (half a wave, chunk
 // l, l + 32, ..: both halves of the wave load it), the rounding in lane order 8 l + 512 t: the row is fetched from memory once
 // and walked a second time out of the cache.  Everything after the norm is elementwise on that second walk, 16 bytes per lane
-// and store.  In the tiled image a row's 64-byte slices lie 256 * 64 bytes apart: four lanes fill one slice, and the four
+// and store.  In the tiled image a row's 64-byte slices lie one 16 KiB chunk apart: four lanes fill one slice, and the four
 // rows of a block are neighbours inside every slice column, so a block completes 256-byte runs.
-// xml_exact_certificate_dev is exact_certificate_kernel (exact.hip) with the corpus bound read from the device;
-// xml_index_exact_bound recomputes the bound over the live slots.
+// xml_index_exact_bound recomputes the bound over the live slots.  (xml_exact_certificate_dev: exact.hip.)
 #include "../../include/xmlhip_index_exact.h"
+#include "index_rows.h"
 #include "l2norm.h"
 #include "split16.h"
 
@@ -30,6 +30,8 @@ __device__ __forceinline__ uint32_t bound_bits(float e) {
   return e > 0.f ? __float_as_uint(e) : 0u;
 }
 
+// The operands stay plain _a / _b lists here, not index_rows.h's per-modality structs: with the structs this kernel measured
+// 2 to 3 % slower (batches of 256 videos), with the lists it is level with what it was.
 template <int MODE, bool TILED>
 __global__ __launch_bounds__(256) void index_put_rows_exact_kernel(
     const float* __restrict__ f1_a, const float* __restrict__ f2_a, const float* __restrict__ mask_a,
@@ -65,13 +67,7 @@ __global__ __launch_bounds__(256) void index_put_rows_exact_kernel(
     uint4 v[L2N_MAXJ];                                    // a missing row: zeros, nrm = 1e-12, y = 0 / 1e-12 = +0
     nrm = l2n_load_row<float>(have ? px : nullptr, d, lane & 31, v);
   }
-  char* k6_row;
-  if constexpr (TILED) {
-    const int slices = d >> 5;                            // 64-byte slices per bf16 row
-    k6_row = k6 + (drow >> 8) * (int64_t)slices * (256 * 64) + (drow & 255) * 64;
-  } else {
-    k6_row = k6 + drow * (int64_t)d * 2;
-  }
+  const int slices = d >> 5;                              // 64-byte slices per bf16 row
   char* rs_row = rs + drow * (int64_t)d * 4;
   const float unit = pow2f(XML_F16_UNIT_LOG2);
   float s = 0.f;
@@ -85,16 +81,8 @@ __global__ __launch_bounds__(256) void index_put_rows_exact_kernel(
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = f[e] / nrm;        // l2n_scale_chunk
-    const uint4 packed = pack16<bf16_t>(f);               // round_bf16_rows_err_kernel from here
-    float g[8];
-    unpack16<bf16_t>(packed, g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float dlt = f[e] - g[e];
-      s += dlt * dlt;
-    }
-    if constexpr (TILED) st_global16(k6_row + (int64_t)(c >> 5) * (256 * 64) + (c & 31) * 2, packed);
-    else st_global16(k6_row + c * 2, packed);
+    const uint4 packed = round_bf16_err8(f, s);           // round_bf16_rows_err_kernel's step (c >> 3: the 16-byte chunk)
+    st_global16(TILED ? k6img::row_chunk(k6, drow, slices, c >> 3) : k6 + drow * (int64_t)d * 2 + c * 2, packed);
     if constexpr (MODE == XML_EXACT_F16S) {               // split_rows_kernel<0> at the fixed unit scale
       uint4 hi, lo;
       (void)split8(f, unit, hi, lo);
@@ -152,68 +140,15 @@ __global__ __launch_bounds__(256) void index_put_rows_exact_kernel(
   }
   if (blockIdx.x != 0) return;
 
-  // ---- block 0 of (video, modality): the mask row, its bit words; of modality 0 also vlen, id and live bit -- the code of
-  // index_put_rows_kernel.  threads 0..127 = waves 0 and 1 stand for clips 0..127 (lpad <= 128)
-  __shared__ unsigned long long any_bits[2];
+  // ---- block 0 of (video, modality): the slot's state (index_rows.h) and the 4 mask words of the own modality
+  const unsigned long long mine = put_slot_state(lpad, lb, lpad, l_ref, i, slot, second, bmask, n_mod == 2 ? mask_b : nullptr,
+                                                 second ? imask_b : imask_a, ids, SlotState{vlen, slot_ids, live});
   const int t = threadIdx.x;
-  const int w = t >> 6;
-  if (w < 2) {
-    const float mv = t < lb ? bmask[(int64_t)i * lb + t] : 0.f;
-    float* imask = second ? imask_b : imask_a;
+  if (t < 128 && (t & 63) == 0) {
     int32_t* bits = second ? bits_b : bits_a;
-    if (t < lpad) imask[(int64_t)slot * lpad + t] = mv;
-    const unsigned long long mine = __ballot(mv != 0.f);
-    if ((t & 63) == 0) {
-      bits[(int64_t)slot * 4 + 2 * w] = (int32_t)(uint32_t)mine;
-      bits[(int64_t)slot * 4 + 2 * w + 1] = (int32_t)(uint32_t)(mine >> 32);
-    }
-    if (!second) {      // valid length over BOTH modalities' masks
-      float ov = 0.f;
-      if (n_mod == 2 && t < lb) ov = mask_b[(int64_t)i * lb + t];
-      const unsigned long long any = __ballot(mv != 0.f || ov != 0.f);
-      if ((t & 63) == 0) any_bits[w] = any;
-    }
+    bits[(int64_t)slot * 4 + 2 * (t >> 6)] = (int32_t)(uint32_t)mine;
+    bits[(int64_t)slot * 4 + 2 * (t >> 6) + 1] = (int32_t)(uint32_t)(mine >> 32);
   }
-  if (second) return;
-  __syncthreads();
-  if (t == 0) {
-    int pos = 0;                                           // last valid clip + 1
-    if (any_bits[1]) pos = 128 - __clzll((long long)any_bits[1]);
-    else if (any_bits[0]) pos = 64 - __clzll((long long)any_bits[0]);
-    if (pos == 0) pos = l_ref;                             // no valid clip: the masked softmax is uniform, nothing is skipped
-    vlen[slot] = pos < l_ref ? pos : l_ref;
-    slot_ids[slot] = ids ? ids[i] : slot;
-    atomicOr(reinterpret_cast<unsigned int*>(live) + (slot >> 5), 1u << (slot & 31));
-  }
-}
-
-// exact_certificate_kernel (exact.hip) with ec0 / ec1 and the slack's e_c term read from the device
-__global__ void exact_certificate_dev_kernel(const float* __restrict__ filt, int m, float* __restrict__ top_val, int k,
-                                             const float* __restrict__ eq0, const float* __restrict__ eq1,
-                                             const float* __restrict__ ec, int n_mod, float slack_base, float slack_ec2,
-                                             float alpha, int outside, int32_t* __restrict__ fail,
-                                             float* __restrict__ eps_out, float* __restrict__ thr_out,
-                                             int32_t* __restrict__ n_fail, int nq) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  const float ec0 = ec[0], ec1 = n_mod == 2 ? ec[1] : ec[0];
-  const float ecm = fmaxf(ec0, ec1);
-  // no product without a coefficient: 0 * inf^2 would be a NaN, and a cell at +inf (a NaN norm was put) must give
-  // eps = +inf, thr = -inf -- every certificate fails and the second tier takes every video -- in both modes
-  const float slack = slack_ec2 != 0.f ? slack_base + slack_ec2 * (ecm * ecm) : slack_base;
-  const float c_norm = 1.f + 1e-6f;                       // | c | of an f32-normalised row
-  float eps = eq0[q] * c_norm + (c_norm + eq0[q]) * ec0;
-  if (n_mod == 2) eps = (eps + eq1[q] * c_norm + (c_norm + eq1[q]) * ec1) * 0.5f;
-  eps += slack;
-  const float b_m = filt[(int64_t)q * m + (m - 1)];
-  const float t_k = top_val[(int64_t)q * k + (k - 1)];
-  const int f = (outside && !(b_m + eps < t_k)) ? 1 : 0;
-  fail[q] = f;
-  if (eps_out) eps_out[q] = eps;
-  if (thr_out) thr_out[q] = t_k - eps;                    // second tier: filter scores below this line cannot enter the top-k
-  if (f) atomicAdd(n_fail, 1);
-  if (alpha != 0.f)
-    for (int j = 0; j < k; ++j) top_val[(int64_t)q * k + j] = expf(alpha * top_val[(int64_t)q * k + j]);
 }
 
 // one workgroup of 16 waves per modality; a wave takes the slots w, w + 16, .. and skips the free ones
@@ -245,23 +180,6 @@ __global__ __launch_bounds__(1024) void index_exact_bound_kernel(const float* __
   }
 }
 
-template <int MODE>
-void launch_put_exact(bool tiled, dim3 grid, hipStream_t st, const void* f1_a, const void* f2_a, const float* mask_a,
-                      const void* f1_b, const void* f2_b, const float* mask_b, const int32_t* slots, const int32_t* ids,
-                      void* k6_a, void* rs_a, float* rs_inv_a, void* feat2_a, float* f2_inv_a, float* err_a, float* imask_a,
-                      int32_t* bits_a, void* k6_b, void* rs_b, float* rs_inv_b, void* feat2_b, float* f2_inv_b, float* err_b,
-                      float* imask_b, int32_t* bits_b, float* ec, int32_t* vlen, int32_t* slot_ids, int32_t* live, int lb,
-                      int lpad, int l_ref, int capacity, int d, int n_mod) {
-#define XML_PUT_EXACT_ARGS                                                                                                  \
-  (const float*)f1_a, (const float*)f2_a, mask_a, (const float*)f1_b, (const float*)f2_b, mask_b, slots, ids, (char*)k6_a,   \
-      (char*)rs_a, rs_inv_a, (char*)feat2_a, f2_inv_a, err_a, imask_a, bits_a, (char*)k6_b, (char*)rs_b, rs_inv_b,             \
-      (char*)feat2_b, f2_inv_b, err_b, imask_b, bits_b, reinterpret_cast<uint32_t*>(ec), vlen, slot_ids, live, lb, lpad,      \
-      l_ref, capacity, d, n_mod
-  if (tiled) hipLaunchKernelGGL((index_put_rows_exact_kernel<MODE, true>), grid, dim3(256), 0, st, XML_PUT_EXACT_ARGS);
-  else hipLaunchKernelGGL((index_put_rows_exact_kernel<MODE, false>), grid, dim3(256), 0, st, XML_PUT_EXACT_ARGS);
-#undef XML_PUT_EXACT_ARGS
-}
-
 }  // namespace
 
 extern "C" int xml_index_put_rows_exact(int n_mod, int mode, const void* f1_a, const void* f2_a, const float* mask_a,
@@ -291,32 +209,13 @@ extern "C" int xml_index_put_rows_exact(int n_mod, int mode, const void* f1_a, c
   if (tiled && !xml_q2c_tiled_ok(128, hidden, XML_BF16)) return XML_ERR_UNSUPPORTED;
   if (split && (hidden % 32)) return XML_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)(lpad / 4), (unsigned)b, (unsigned)n_mod);
-  hipStream_t st = (hipStream_t)stream;
-  if (split)
-    launch_put_exact<XML_EXACT_F16S>(tiled != 0, grid, st, f1_a, f2_a, mask_a, f1_b, f2_b, mask_b, slots, ids, k6_a, rescore_a,
-                                     rescore_inv_a, feat2_a, feat2_inv_a, err_a, imask_a, bits_a, k6_b, rescore_b,
-                                     rescore_inv_b, feat2_b, feat2_inv_b, err_b, imask_b, bits_b, ec, vlen, slot_ids, live,
-                                     lb, lpad, l_ref, capacity, hidden, n_mod);
-  else
-    launch_put_exact<XML_EXACT_F32>(tiled != 0, grid, st, f1_a, f2_a, mask_a, f1_b, f2_b, mask_b, slots, ids, k6_a, rescore_a,
-                                    rescore_inv_a, feat2_a, feat2_inv_a, err_a, imask_a, bits_a, k6_b, rescore_b, rescore_inv_b,
-                                    feat2_b, feat2_inv_b, err_b, imask_b, bits_b, ec, vlen, slot_ids, live, lb, lpad, l_ref,
-                                    capacity, hidden, n_mod);
-  XML_CHECK_LAUNCH();
-  return XML_OK;
-}
-
-extern "C" int xml_exact_certificate_dev(const float* filter_scores, int m, float* top_val, int k, const float* eq0,
-                                         const float* eq1, const float* ec, int n_mod, float slack_base, float slack_ec2,
-                                         float alpha, int outside, int32_t* fail, float* eps_out, float* thr_out,
-                                         int32_t* n_fail, int nq, xml_stream_t stream) {
-  XML_ENTER();
-  if (!filter_scores || !top_val || !eq0 || !ec || !fail || !n_fail || nq <= 0 || m <= 0 || k <= 0 || k > m)
-    return XML_ERR_BAD_ARG;
-  if (n_mod < 1 || n_mod > 2 || (n_mod == 2 && !eq1)) return XML_ERR_BAD_ARG;
-  hipLaunchKernelGGL(exact_certificate_dev_kernel, dim3(cdiv(nq, 128)), dim3(128), 0, (hipStream_t)stream, filter_scores, m,
-                     top_val, k, eq0, eq1 ? eq1 : eq0, ec, n_mod, slack_base, slack_ec2, alpha, outside, fail, eps_out,
-                     thr_out, n_fail, nq);
+  const auto kernel = split ? (tiled ? index_put_rows_exact_kernel<XML_EXACT_F16S, true> : index_put_rows_exact_kernel<XML_EXACT_F16S, false>)
+                            : (tiled ? index_put_rows_exact_kernel<XML_EXACT_F32, true> : index_put_rows_exact_kernel<XML_EXACT_F32, false>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)f1_a, (const float*)f2_a, mask_a,
+                     (const float*)f1_b, (const float*)f2_b, mask_b, slots, ids, (char*)k6_a, (char*)rescore_a, rescore_inv_a,
+                     (char*)feat2_a, feat2_inv_a, err_a, imask_a, bits_a, (char*)k6_b, (char*)rescore_b, rescore_inv_b,
+                     (char*)feat2_b, feat2_inv_b, err_b, imask_b, bits_b, reinterpret_cast<uint32_t*>(ec), vlen, slot_ids, live,
+                     lb, lpad, l_ref, capacity, hidden, n_mod);
   XML_CHECK_LAUNCH();
   return XML_OK;
 }

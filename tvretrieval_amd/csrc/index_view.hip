@@ -9,11 +9,9 @@
 // The workgroups of slice 0 also store the tile's 8 mask words of their modality, whole: thread w < 8 owns word w, i.e. the
 // 16 bits of blocks 2 w and 2 w + 1 -- plain stores, no atomics.
 #include "../../include/xmlhip_index_view.h"
-#include "common.h"
+#include "index_rows.h"
 
 namespace {
-
-constexpr int CHUNK = 16 * 1024;        // bytes of one (tile, slice): 256 rows of 64 bytes; a block is 1 KiB of it
 
 __global__ __launch_bounds__(256) void index_gather_blocks_kernel(
     const int32_t* __restrict__ src_block, const char* __restrict__ k6_src_a, const uint32_t* __restrict__ bits_src_a,
@@ -30,21 +28,14 @@ __global__ __launch_bounds__(256) void index_gather_blocks_kernel(
   if (word < 0 || (int64_t)word >= n_blocks_src) word = -2;
   const char* k6_src = second ? k6_src_b : k6_src_a;
   char* k6_dst = second ? k6_dst_b : k6_dst_a;
-  const int64_t tile_bytes = (int64_t)slices * CHUNK;
-  char* dst_chunk = k6_dst + tile * tile_bytes + (int64_t)slice * CHUNK;
+  char* dst_chunk = k6img::block_slice(k6_dst, tile * 16, slices, slice);
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   int src[4];
   uint4 v[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) src[i] = __builtin_amdgcn_readlane(word, wave + 4 * i);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)                                      // the four loads of a lane are in flight together
-    if (src[i] >= 0)
-      v[i] = ld_global16(k6_src + (int64_t)(src[i] >> 4) * tile_bytes + (int64_t)slice * CHUNK + (int64_t)(src[i] & 15) * 1024 +
-                         lane * 16);
+  k6img::load_wave_blocks(k6_src, word, 0, wave, slices, slice, lane, src, v);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if (src[i] >= 0) st_global16(dst_chunk + (wave + 4 * i) * 1024 + lane * 16, v[i]);
+    if (src[i] >= 0) st_global16(dst_chunk + (wave + 4 * i) * k6img::BLOCK_BYTES + lane * 16, v[i]);
   // ---- the tile's mask words of this modality: slice 0, thread w < 8 = word w = blocks 2 w (low half) and 2 w + 1
   // (the two entries are fetched by EVERY lane, before the branch: a shuffle reads nothing from a lane that has left)
   const int pair[2] = {__shfl(word, (2 * lane) & 15), __shfl(word, (2 * lane + 1) & 15)};

@@ -83,16 +83,18 @@ class SlotTable(object):
         if len(set(slots)) != len(slots):
             raise ValueError("%s: duplicate slots in one call: %s" % (what, sorted(s for s in set(slots) if slots.count(s) > 1)))
 
-    def _check_ids(self, slots, ids, what):
-        if len(ids) != len(slots):
-            raise ValueError("%s: %d ids for %d videos" % (what, len(ids), len(slots)))
+    def _check_ids(self, leaving, ids, what, n=None):
+        """ids for the n videos of a call; an id that is held already must be held by one of the slots in `leaving`."""
+        n = len(leaving) if n is None else n
+        if len(ids) != n:
+            raise ValueError("%s: %d ids for %d videos" % (what, len(ids), n))
         if len(set(ids)) != len(ids):
             raise ValueError("%s: duplicate video ids in one call" % what)
         for v in ids:
             if not -2 ** 31 <= v < 2 ** 31:
                 raise ValueError("%s: video id %d does not fit int32" % (what, v))
             held = self._slot.get(v)
-            if held is not None and held not in slots:
+            if held is not None and held not in leaving:
                 raise ValueError("%s: video id %d is already held by slot %d" % (what, v, held))
 
     def resolve(self, slots=None, ids=None, what="slots"):
@@ -196,17 +198,7 @@ class ChainTable(SlotTable):
 
     def resolve_videos(self, slots=None, ids=None, what="slots"):
         """The head slots of the videos a call names, by any slot of each or by id: validated, one entry per video."""
-        if (slots is None) == (ids is None):
-            raise ValueError("%s: name the videos by slots or by ids=, not both" % what)
-        if ids is not None:
-            slots = [self.slot_of(v) for v in _int_list(ids, what)]
-        else:
-            slots = _int_list(slots, what)
-        self._check_slots(slots, what)
-        for s in slots:
-            if self._id[s] is None:
-                raise ValueError("%s: slot %d is free" % (what, s))
-        heads = [self._head[s] for s in slots]
+        heads = [self._head[s] for s in self.resolve(slots, ids, what)]
         if len(set(heads)) != len(heads):
             raise ValueError("%s: a video is named twice in one call (head slots %s)"
                              % (what, sorted(h for h in set(heads) if heads.count(h) > 1)))
@@ -266,17 +258,7 @@ class ChainTable(SlotTable):
             ids = [self._id[h] if self._id[h] is not None else h for h in heads]
         else:
             ids = _int_list(ids, what)
-        if len(ids) != n:
-            raise ValueError("%s: %d ids for %d videos" % (what, len(ids), n))
-        if len(set(ids)) != len(ids):
-            raise ValueError("%s: duplicate video ids in one call" % what)
-        leaving = set(s for o in old for s in o)
-        for v in ids:
-            if not -2 ** 31 <= v < 2 ** 31:
-                raise ValueError("%s: video id %d does not fit int32" % (what, v))
-            held = self._slot.get(v)
-            if held is not None and held not in leaving:
-                raise ValueError("%s: video id %d is already held by slot %d" % (what, v, held))
+        self._check_ids(set(s for o in old for s in o), ids, what, n)
         taken = set(s for ch in chains for s in ch)
         surplus = [s for s in freed if s not in taken]
         want = {s: (s, -1, 0) for s in surplus}
@@ -737,21 +719,11 @@ class MutableCorpusIndex(CorpusIndex):
         self.blocks, self.codes, self.auto_compact = blocks, None, bool(auto_compact) and blocks is not None
         n_words = cap if blocks is None else 2 * blocks.n_tiles
         self.mask_bits = {m: torch.zeros((n_words, 4), dtype=torch.int32, device=dev) for m in mods}
-        feat1n = {}
+        plan = None
         if blocks is not None:                          # the packed image: every block unused, K6 skips all of them
             self.codes = torch.full((2 * blocks.n_tiles, 8), -2, dtype=torch.int32, device=dev)
             plan = _TablePlan(blocks, self.codes, cap)
-        for m in mods:
-            if blocks is not None:
-                data = torch.zeros(hip_ops.q2c_tiled_numel(blocks.n_tiles * 256, h, act), dtype=act, device=dev)
-                feat1n[m] = hip_ops.TiledRows(data, cap * lpad, h, (cap, lpad, h), all_valid=False)
-                feat1n[m].mask_bits, feat1n[m].plan = self.mask_bits[m], plan
-            elif hip_ops.q2c_tiled_ok(lpad, h, act):    # the plain two-slots-per-tile image; K6 in mask-bit mode, always
-                data = torch.zeros(hip_ops.q2c_tiled_numel(cap * lpad, h, act), dtype=act, device=dev)
-                feat1n[m] = hip_ops.TiledRows(data, cap * lpad, h, (cap, lpad, h), all_valid=False)
-                feat1n[m].mask_bits = self.mask_bits[m]
-            else:
-                feat1n[m] = torch.zeros((cap, lpad, h), dtype=act, device=dev)
+        feat1n = {m: self._alloc_k6_image(m, (cap, lpad, h), act, dev, plan) for m in mods}
         CorpusIndex.__init__(self, mods, feat1n, feat2, mask, l_ref)
         self._init_slot_state(model, table, l_ref, dev)
         if part_overlap is not None:         # every slot in the single state: an add of short videos never touches these
@@ -760,6 +732,21 @@ class MutableCorpusIndex(CorpusIndex):
             self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
             self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
         return self
+
+    def _alloc_k6_image(self, m, shape, dtype, dev, plan=None):
+        """The zero-filled K6 operand of modality m for (capacity, lpad, H) rows of `dtype`: the packed image of `plan` (a
+        _TablePlan), else the plain two-slots-per-tile image where the tiled kernel takes the rows (K6 in mask-bit mode,
+        always), else row-major."""
+        cap, lpad, h = shape
+        if plan is None and not hip_ops.q2c_tiled_ok(lpad, h, dtype):
+            return torch.zeros(shape, dtype=dtype, device=dev)
+        rows = cap * lpad if plan is None else plan.n_tiles * 256
+        data = torch.zeros(hip_ops.q2c_tiled_numel(rows, h, dtype), dtype=dtype, device=dev)
+        image = hip_ops.TiledRows(data, cap * lpad, h, shape, all_valid=False)
+        image.mask_bits = self.mask_bits[m]
+        if plan is not None:
+            image.plan = plan
+        return image
 
     @staticmethod
     def _check_exact_rank(model, dt, l_ref, tiles, part_overlap):
@@ -800,14 +787,8 @@ class MutableCorpusIndex(CorpusIndex):
         mask = {m: f32(cap, lpad) for m in mods}
         self.blocks, self.codes, self.auto_compact = None, None, False
         self.mask_bits = {m: torch.zeros((cap, 4), dtype=torch.int32, device=dev) for m in mods}
-        feat1n, bf16 = {}, torch.bfloat16
-        for m in mods:       # the bf16 FILTER image, in the layout create chooses for bf16 rows of this width
-            if hip_ops.q2c_tiled_ok(lpad, h, bf16):
-                data = torch.zeros(hip_ops.q2c_tiled_numel(cap * lpad, h, bf16), dtype=bf16, device=dev)
-                feat1n[m] = hip_ops.TiledRows(data, cap * lpad, h, (cap, lpad, h), all_valid=False)
-                feat1n[m].mask_bits = self.mask_bits[m]
-            else:
-                feat1n[m] = torch.zeros((cap, lpad, h), dtype=bf16, device=dev)
+        # the bf16 FILTER image, in the layout create chooses for bf16 rows of this width
+        feat1n = {m: self._alloc_k6_image(m, (cap, lpad, h), torch.bfloat16, dev) for m in mods}
         CorpusIndex.__init__(self, mods, feat1n, feat2, mask, l_ref)
         cells = f32(len(mods))
         self.exact = _inference.ExactFilter({m: rows() for m in mods}, _inference._DeviceBound(cells, mods), n_candidates=256,
@@ -969,36 +950,43 @@ class MutableCorpusIndex(CorpusIndex):
     def _launch_put(self, slots, ids, enc, nbs, runs, clears):
         """The launches of a validated put (the packed form: with the runs _find_runs returned, committed to the BlockTable
         here); the slot table is the caller's to commit."""
-        mods = self.modalities
         b = len(slots)
+        batch = [[enc[m][k].contiguous() for m in self.modalities] for k in (0, 1)] + \
+            [[enc[m][2].float().contiguous() for m in self.modalities]]
         if self.blocks is not None:
             if clears:     # videos that move: their old runs become unused blocks BEFORE the put, whose runs may reuse them
-                hip_ops.index_clear_rows_packed(self._to_device([-1] * len(clears)), self._to_device(clears), 8,
-                                                [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], self.codes,
-                                                self.vlen, self.live.view(-1), self.l_ref)
+                self._clear([-1] * len(clears), clears)
             rec = self._to_device(slots + ids + [x for r in runs for x in r])
-            hip_ops.index_put_rows_packed([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
-                                          [enc[m][2].float().contiguous() for m in mods], rec[:b], rec[b:2 * b],
-                                          rec[2 * b:].view(b, 2), max(nbs), [self.feat1n[m] for m in mods],
-                                          [self.feat2[m] for m in mods], [self.mask[m] for m in mods],
-                                          [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.slot_ids,
-                                          self.live.view(-1), self.l_ref)
+            hip_ops.index_put_rows_packed(*batch, rec[:b], rec[b:2 * b], rec[2 * b:].view(b, 2), max(nbs),
+                                          *self._sides(self.feat1n, self.feat2, self.mask, self.mask_bits), self.codes,
+                                          self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
             self.blocks.commit_put(slots, runs)
             return
         both = self._to_device([slots, ids])
         if self.exact is not None:     # every operand of the slots and the running bound, one launch
             ex = self.exact
-            hip_ops.index_put_rows_exact([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
-                                         [enc[m][2].float().contiguous() for m in mods], both[0], both[1],
-                                         [self.feat1n[m] for m in mods], [ex.feat1n_f32[m] for m in mods],
-                                         [self.feat2[m] for m in mods], [ex.err_rows[m] for m in mods],
-                                         [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], ex.e_c_dev,
-                                         self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
+            hip_ops.index_put_rows_exact(*batch, both[0], both[1],
+                                         *self._sides(self.feat1n, ex.feat1n_f32, self.feat2, ex.err_rows, self.mask,
+                                                      self.mask_bits),
+                                         ex.e_c_dev, self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
             return
-        hip_ops.index_put_rows([enc[m][0].contiguous() for m in mods], [enc[m][1].contiguous() for m in mods],
-                               [enc[m][2].float().contiguous() for m in mods], both[0], both[1],
-                               [self.feat1n[m] for m in mods], [self.feat2[m] for m in mods], [self.mask[m] for m in mods],
-                               [self.mask_bits[m] for m in mods], self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
+        hip_ops.index_put_rows(*batch, both[0], both[1], *self._sides(self.feat1n, self.feat2, self.mask, self.mask_bits),
+                               self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
+
+    def _sides(self, *tensors):
+        """Per-modality dicts -> the per-modality lists the ops entries take."""
+        return [[t[m] for m in self.modalities] for t in tensors]
+
+    def _clear(self, slots, runs=None):
+        """One clear launch over host lists: the plain entry frees `slots`; the packed one takes (slot, run) records -- a run
+        becomes unused blocks, its slot is freed unless it is -1.  `slots` may be a device tensor already (then runs is too)."""
+        if not torch.is_tensor(slots):
+            slots, runs = self._to_device(slots), None if runs is None else self._to_device(runs)
+        state = (self.vlen, self.live.view(-1), self.l_ref)
+        if self.blocks is None:
+            hip_ops.index_clear_rows(slots, *self._sides(self.mask, self.mask_bits), *state)
+        else:
+            hip_ops.index_clear_rows_packed(slots, runs, 8, *self._sides(self.mask, self.mask_bits), self.codes, *state)
 
     def _room(self, slots, masks, n_clips, b, what):
         """The packed form: refuse a batch that finds no runs BEFORE it is encoded; returns n_clips for put (the lengths read
@@ -1054,12 +1042,9 @@ class MutableCorpusIndex(CorpusIndex):
             # an entry takes 65535 records; a part of a launch that keeps the contract keeps it too (tiles are independent,
             # cross-tile sources lie in donor tiles, which no record writes)
             for i in range(0, len(recs), 65535):
-                hip_ops.index_move_blocks_packed(records[i:i + 65535], [self.feat1n[m] for m in mods],
-                                                 [self.mask_bits[m] for m in mods], self.codes)
+                hip_ops.index_move_blocks_packed(records[i:i + 65535], *self._sides(self.feat1n, self.mask_bits), self.codes)
             for i in range(0, c, 65535):     # the runs vacated in other tiles: until here their slots' codes stood twice
-                hip_ops.index_clear_rows_packed(dev[n + i:n + min(i + 65535, c)], runs[i:i + 65535], 8,
-                                                [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods], self.codes,
-                                                self.vlen, self.live.view(-1), self.l_ref)
+                self._clear(dev[n + i:n + min(i + 65535, c)], runs[i:i + 65535])
         self.blocks.commit_compact(plan)
         after = self.blocks.stats()
         moved = sum(nb for rnd in plan for (_, nb), _ in rnd["moves"].values())
@@ -1114,16 +1099,8 @@ class MutableCorpusIndex(CorpusIndex):
             slots = plan["slots"]
         else:
             slots = self.table.resolve(slots, ids, "remove")
-        mods = self.modalities
-        if slots and self.blocks is not None:
-            runs = self.blocks.check_remove(slots)
-            hip_ops.index_clear_rows_packed(self._to_device(slots), self._to_device(runs), 8, [self.mask[m] for m in mods],
-                                            [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.live.view(-1),
-                                            self.l_ref)
-            self.blocks.commit_remove(slots)
-        elif slots:
-            hip_ops.index_clear_rows(self._to_device(slots), [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods],
-                                     self.vlen, self.live.view(-1), self.l_ref)
+        if slots:
+            self._free_slots(slots)
         if plan is not None:
             self._set_chains(plan["records"])
             self.table.commit_remove_chains(plan)
@@ -1132,6 +1109,13 @@ class MutableCorpusIndex(CorpusIndex):
         if slots:
             self.version += 1
         return slots
+
+    def _free_slots(self, slots):
+        """The clear launch that frees live slots; the packed form frees their runs too (BlockTable committed here)."""
+        if self.blocks is None:
+            return self._clear(slots)
+        self._clear(slots, self.blocks.check_remove(slots))
+        self.blocks.commit_remove(slots)
 
     # ---- long videos: chains of slots (DESIGN.md section 20c) ---------------------------------------------------------------
     def _set_chains(self, records):
@@ -1182,15 +1166,8 @@ class MutableCorpusIndex(CorpusIndex):
             runs, clears = self._find_runs(slots, nbs, what, freed=surplus)
         enc = self.encode(video_feat, video_mask, sub_feat, sub_mask)
         self._check_enc(slots, enc)
-        if surplus and self.blocks is not None:
-            gone = self.blocks.check_remove(surplus)
-            hip_ops.index_clear_rows_packed(self._to_device(surplus), self._to_device(gone), 8, [self.mask[m] for m in mods],
-                                            [self.mask_bits[m] for m in mods], self.codes, self.vlen, self.live.view(-1),
-                                            self.l_ref)
-            self.blocks.commit_remove(surplus)
-        elif surplus:
-            hip_ops.index_clear_rows(self._to_device(surplus), [self.mask[m] for m in mods], [self.mask_bits[m] for m in mods],
-                                     self.vlen, self.live.view(-1), self.l_ref)
+        if surplus:
+            self._free_slots(surplus)
         self._launch_put(slots, plan["put_ids"], enc, nbs, runs, clears)
         self._set_chains(plan["records"])
         self.table.commit_chains(plan)

@@ -1342,6 +1342,51 @@ def unsplit_f16_rows(sr):
 
 
 # ---- in-place index updates (include/xmlhip.h "In-place updates of a resident index"; inference.MutableCorpusIndex) ---------
+def _second(n_mod):
+    """The _b operand of an entry out of a per-modality list: the address of its second tensor, NULL with one modality."""
+    return (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+
+
+def _batch_sides(what, f1, f2, masks, n_mod, hidden, dtype):
+    """Checks the per-modality (b, lb, H) / (b, lb, H) / (b, lb) batch operands of a put entry; returns (b, lb)."""
+    if not (len(f1) == len(f2) == len(masks) == n_mod):
+        raise _lib.XmlHipError("%s: the batch holds %d modalities, the index %d" % (what, len(f1), n_mod))
+    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
+    for m in range(n_mod):
+        _req(f1[m], "f1", dtype); _req(f2[m], "f2", dtype); _req(masks[m], "mask", torch.float32)
+        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
+            raise _lib.XmlHipError("%s: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected" % what)
+    return b, lb
+
+
+def _slot_records(what, slots, ids, b):
+    _req(slots, "slots", torch.int32)
+    if slots.numel() != b or (ids is not None and (_req(ids, "ids", torch.int32).numel() != b)):
+        raise _lib.XmlHipError("%s: one slot (and id) per video of the batch" % what)
+
+
+def _codes_tiles(what, codes):
+    """Checks the (2 * n_tiles, 8) int32 code table of a packed image; returns n_tiles."""
+    _req(codes, "codes", torch.int32)
+    if codes.dim() != 2 or codes.shape[1] != 8 or codes.shape[0] % 2 or not codes.shape[0]:
+        raise _lib.XmlHipError("%s: codes (2 * n_tiles, 8) int32 expected" % what)
+    return int(codes.shape[0]) // 2
+
+
+def _k6_side(what, k6, tiled, cap, lpad, hidden, dtype, image):
+    """Checks one modality's K6 operand of a per-slot index (`image`: what the messages call it); returns its buffer."""
+    if isinstance(k6, TiledRows) != tiled:
+        raise _lib.XmlHipError("%s: the %ss of the modalities differ in layout" % (what, image))
+    d = k6.data if tiled else k6
+    _req(d, "k6", dtype)
+    if tiled:
+        if k6.shape != (cap, lpad, hidden) or lpad != 128 or d.numel() != q2c_tiled_numel(cap * lpad, hidden, d.dtype):
+            raise _lib.XmlHipError("%s: the tile image does not hold (capacity, 128, H) rows" % what)
+    elif tuple(d.shape) != (cap, lpad, hidden):
+        raise _lib.XmlHipError("%s: row-major %s of shape %s expected" % (what, image, (cap, lpad, hidden)))
+    return d
+
+
 def _index_sides(k6, feat2, imask, bits):
     """Checks the per-modality index tensors of the two update entries; returns (capacity, lpad, hidden, tiled, k6 buffers)."""
     n_mod = len(feat2)
@@ -1354,16 +1399,7 @@ def _index_sides(k6, feat2, imask, bits):
         _req(feat2[m], "feat2", feat2[0].dtype); _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
         if tuple(feat2[m].shape) != (cap, lpad, hidden) or tuple(imask[m].shape) != (cap, lpad) or tuple(bits[m].shape) != (cap, 4):
             raise _lib.XmlHipError("index update: feat2 (capacity, lpad, H), mask (capacity, lpad), bits (capacity, 4) expected")
-        if isinstance(k6[m], TiledRows) != tiled:
-            raise _lib.XmlHipError("index update: the K6 operands of the modalities differ in layout")
-        d = k6[m].data if tiled else k6[m]
-        _req(d, "k6", feat2[0].dtype)
-        if tiled:
-            if k6[m].shape != (cap, lpad, hidden) or lpad != 128 or d.numel() != q2c_tiled_numel(cap * lpad, hidden, d.dtype):
-                raise _lib.XmlHipError("index update: the tile image does not hold (capacity, 128, H) rows")
-        elif tuple(d.shape) != (cap, lpad, hidden):
-            raise _lib.XmlHipError("index update: row-major K6 operand of shape %s expected" % ((cap, lpad, hidden),))
-        data.append(d)
+        data.append(_k6_side("index update", k6[m], tiled, cap, lpad, hidden, feat2[0].dtype, "K6 operand"))
     return int(cap), int(lpad), int(hidden), tiled, data
 
 
@@ -1386,18 +1422,9 @@ def index_put_rows(f1, f2, masks, slots, ids, k6, feat2, imask, bits, vlen, slot
     cap, lpad, hidden, tiled, data = _index_sides(k6, feat2, imask, bits)
     _index_state(vlen, live, cap, slot_ids)
     n_mod = len(feat2)
-    if not (len(f1) == len(f2) == len(masks) == n_mod):
-        raise _lib.XmlHipError("index_put_rows: the batch holds %d modalities, the index %d" % (len(f1), n_mod))
-    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
-    for m in range(n_mod):
-        _req(f1[m], "f1", feat2[0].dtype); _req(f2[m], "f2", feat2[0].dtype); _req(masks[m], "mask", torch.float32)
-        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
-            raise _lib.XmlHipError("index_put_rows: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected")
-    _req(slots, "slots", torch.int32)
-    if slots.numel() != b or (ids is not None and (_req(ids, "ids", torch.int32).numel() != b)):
-        raise _lib.XmlHipError("index_put_rows: one slot (and id) per video of the batch")
-    j = n_mod - 1
-    sec = (lambda t: _p(t[j])) if n_mod == 2 else (lambda t: None)
+    b, lb = _batch_sides("index_put_rows", f1, f2, masks, n_mod, hidden, feat2[0].dtype)
+    _slot_records("index_put_rows", slots, ids, b)
+    sec = _second(n_mod)
     check(_lib.load().xml_index_put_rows(
         n_mod, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), b, lb,
         _p(data[0]), _p(feat2[0]), _p(imask[0]), _p(bits[0]), sec(data), sec(feat2), sec(imask), sec(bits),
@@ -1418,7 +1445,7 @@ def index_clear_rows(slots, imask, bits, vlen, live, l_ref):
             raise _lib.XmlHipError("index_clear_rows: mask (capacity, lpad) and bits (capacity, 4) expected")
     _index_state(vlen, live, cap)
     _req(slots, "slots", torch.int32)
-    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    sec = _second(n_mod)
     check(_lib.load().xml_index_clear_rows(n_mod, _p(slots), int(slots.numel()), _p(imask[0]), _p(bits[0]), sec(imask), sec(bits),
                                            _p(vlen), _p(live), int(cap), int(lpad), int(l_ref), _stream()),
           "xml_index_clear_rows")
@@ -1430,10 +1457,7 @@ def _packed_sides(k6, feat2, imask, bits, codes):
     n_mod = len(imask)
     if n_mod not in (1, 2) or len(bits) != n_mod or (k6 is not None and not (len(k6) == len(feat2) == n_mod)):
         raise _lib.XmlHipError("packed index update: 1 or 2 modalities, the same number of k6 / feat2 / mask / bits tensors")
-    _req(codes, "codes", torch.int32)
-    if codes.dim() != 2 or codes.shape[1] != 8 or codes.shape[0] % 2 or not codes.shape[0]:
-        raise _lib.XmlHipError("packed index update: codes (2 * n_tiles, 8) int32 expected")
-    n_tiles, cap = int(codes.shape[0]) // 2, int(imask[0].shape[0])
+    n_tiles, cap = _codes_tiles("packed index update", codes), int(imask[0].shape[0])
     hidden, data = None, None
     for m in range(n_mod):
         _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
@@ -1469,17 +1493,10 @@ def index_put_rows_packed(f1, f2, masks, slots, ids, runs, nb_max, k6, feat2, im
     cap, hidden, n_tiles, data = _packed_sides(k6, feat2, imask, bits, codes)
     _index_state(vlen, live, cap, slot_ids)
     n_mod = len(feat2)
-    if not (len(f1) == len(f2) == len(masks) == n_mod):
-        raise _lib.XmlHipError("index_put_rows_packed: the batch holds %d modalities, the index %d" % (len(f1), n_mod))
-    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
-    for m in range(n_mod):
-        _req(f1[m], "f1", feat2[0].dtype); _req(f2[m], "f2", feat2[0].dtype); _req(masks[m], "mask", torch.float32)
-        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
-            raise _lib.XmlHipError("index_put_rows_packed: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected")
+    b, lb = _batch_sides("index_put_rows_packed", f1, f2, masks, n_mod, hidden, feat2[0].dtype)
     if _packed_records(slots, runs, "index_put_rows_packed") != b or (ids is not None and _req(ids, "ids", torch.int32).numel() != b):
         raise _lib.XmlHipError("index_put_rows_packed: one slot, run (and id) per video of the batch")
-    j = n_mod - 1
-    sec = (lambda t: _p(t[j])) if n_mod == 2 else (lambda t: None)
+    sec = _second(n_mod)
     check(_lib.load().xml_index_put_rows_packed(
         n_mod, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), _p(runs), b, lb, int(nb_max),
         _p(data[0]), _p(feat2[0]), _p(imask[0]), _p(bits[0]), sec(data), sec(feat2), sec(imask), sec(bits), _p(codes),
@@ -1493,7 +1510,7 @@ def index_clear_rows_packed(slots, runs, nb_max, imask, bits, codes, vlen, live,
     cap, _, n_tiles, _ = _packed_sides(None, None, imask, bits, codes)
     _index_state(vlen, live, cap)
     n = _packed_records(slots, runs, "index_clear_rows_packed")
-    sec = (lambda t: _p(t[1])) if len(imask) == 2 else (lambda t: None)
+    sec = _second(len(imask))
     check(_lib.load().xml_index_clear_rows_packed(len(imask), _p(slots), _p(runs), n, int(nb_max), _p(imask[0]), _p(bits[0]),
                                                   sec(imask), sec(bits), _p(codes), _p(vlen), _p(live), cap, n_tiles, 128,
                                                   int(l_ref), _stream()),
@@ -1509,10 +1526,7 @@ def index_move_blocks_packed(records, k6, bits, codes):
     n_mod = len(k6)
     if n_mod not in (1, 2) or len(bits) != n_mod:
         raise _lib.XmlHipError("index_move_blocks_packed: 1 or 2 modalities, one k6 image and one bits tensor each")
-    _req(codes, "codes", torch.int32)
-    if codes.dim() != 2 or codes.shape[1] != 8 or codes.shape[0] % 2 or not codes.shape[0]:
-        raise _lib.XmlHipError("index_move_blocks_packed: codes (2 * n_tiles, 8) int32 expected")
-    n_tiles = int(codes.shape[0]) // 2
+    n_tiles = _codes_tiles("index_move_blocks_packed", codes)
     _req(records, "records", torch.int32)
     if records.dim() != 2 or records.shape[1] != 17 or not records.shape[0]:
         raise _lib.XmlHipError("index_move_blocks_packed: records (n, 17) int32 = {tile, src[16]} expected")
@@ -1527,7 +1541,7 @@ def index_move_blocks_packed(records, k6, bits, codes):
             raise _lib.XmlHipError("index_move_blocks_packed: tile images of n_tiles * 256 = %d rows of one hidden size and bits "
                                    "(2 * n_tiles, 4) expected -- the same n_tiles as codes" % (n_tiles * 256))
         data.append(d)
-    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    sec = _second(n_mod)
     check(_lib.load().xml_index_move_blocks_packed(n_mod, _p(records), int(records.shape[0]), _p(data[0]), _p(bits[0]), sec(data),
                                                    sec(bits), _p(codes), n_tiles, int(k6[0].hidden), dt_of(data[0]), _stream()),
           "xml_index_move_blocks_packed")
@@ -1567,7 +1581,7 @@ def index_gather_blocks(src_block, k6_src, bits_src, n_blocks_src, k6_dst, bits_
             if bits_src[m].numel() < (n_blocks_src + 1) // 2:
                 raise _lib.XmlHipError("index_gather_blocks: the source mask words cover fewer than n_blocks_src = %d blocks"
                                        % n_blocks_src)
-    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    sec = _second(n_mod)
     check(_lib.load().xml_index_gather_blocks(n_mod, _p(src_block), n_tiles, _p(k6_src[0]), _p(bits_src[0]), sec(k6_src),
                                               sec(bits_src), n_blocks_src, _p(k6_dst[0]), _p(bits_dst[0]), sec(k6_dst),
                                               sec(bits_dst), hidden, dt_of(k6_src[0]), _stream()),
@@ -1686,16 +1700,7 @@ def _exact_sides(k6, rescore, feat2, err, imask, bits):
         _req(err[m], "err", torch.float32); _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
         if tuple(err[m].shape) != (cap, lpad) or tuple(imask[m].shape) != (cap, lpad) or tuple(bits[m].shape) != (cap, 4):
             raise _lib.XmlHipError("exact index update: err / mask (capacity, lpad) and bits (capacity, 4) expected")
-        if isinstance(k6[m], TiledRows) != tiled:
-            raise _lib.XmlHipError("exact index update: the filter images of the modalities differ in layout")
-        d = k6[m].data if tiled else k6[m]
-        _req(d, "k6", torch.bfloat16)
-        if tiled:
-            if k6[m].shape != (cap, lpad, hidden) or lpad != 128 or d.numel() != q2c_tiled_numel(cap * lpad, hidden, d.dtype):
-                raise _lib.XmlHipError("exact index update: the tile image does not hold (capacity, 128, H) rows")
-        elif tuple(d.shape) != (cap, lpad, hidden):
-            raise _lib.XmlHipError("exact index update: row-major filter image of shape %s expected" % ((cap, lpad, hidden),))
-        data.append(d)
+        data.append(_k6_side("exact index update", k6[m], tiled, cap, lpad, hidden, torch.bfloat16, "filter image"))
     return cap, lpad, hidden, tiled, EXACT_F16S if split else EXACT_F32, data
 
 
@@ -1711,23 +1716,15 @@ def index_put_rows_exact(f1, f2, masks, slots, ids, k6, rescore, feat2, err, ima
     _req(ec, "ec", torch.float32)
     if ec.numel() != n_mod:
         raise _lib.XmlHipError("index_put_rows_exact: ec (n_mod,) f32 expected")
-    if not (len(f1) == len(f2) == len(masks) == n_mod):
-        raise _lib.XmlHipError("index_put_rows_exact: the batch holds %d modalities, the index %d" % (len(f1), n_mod))
-    b, lb = int(f1[0].shape[0]), int(f1[0].shape[1])
-    for m in range(n_mod):
-        _req(f1[m], "f1", torch.float32); _req(f2[m], "f2", torch.float32); _req(masks[m], "mask", torch.float32)
-        if tuple(f1[m].shape) != (b, lb, hidden) or tuple(f2[m].shape) != (b, lb, hidden) or tuple(masks[m].shape) != (b, lb):
-            raise _lib.XmlHipError("index_put_rows_exact: f1 / f2 (b, lb, H) and mask (b, lb) of one batch expected")
-    _req(slots, "slots", torch.int32)
-    if slots.numel() != b or (ids is not None and (_req(ids, "ids", torch.int32).numel() != b)):
-        raise _lib.XmlHipError("index_put_rows_exact: one slot (and id) per video of the batch")
+    b, lb = _batch_sides("index_put_rows_exact", f1, f2, masks, n_mod, hidden, torch.float32)
+    _slot_records("index_put_rows_exact", slots, ids, b)
     split = mode == EXACT_F16S
     side = []
     for m in range(n_mod):
         side += [_p(data[m]), _p(rescore[m]), _p(rescore[m].inv) if split else None, _p(feat2[m]),
                  _p(feat2[m].inv) if split else None, _p(err[m]), _p(imask[m]), _p(bits[m])]
     side += [None] * (16 - len(side))
-    sec = (lambda t: _p(t[1])) if n_mod == 2 else (lambda t: None)
+    sec = _second(n_mod)
     check(_lib.load().xml_index_put_rows_exact(
         n_mod, mode, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), b, lb, *side,
         _p(ec), _p(vlen), _p(slot_ids), _p(live), cap, lpad, int(l_ref), hidden, XML_F32, int(tiled), _stream()),
