@@ -1,7 +1,8 @@
 """Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
 
-usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains,exact] [--batch 200] [--reps 21]
+usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains,exact,exactp] [--batch 200] [--reps 21]
                                           [--pass-reps 5] [--queries 10000] [--videos 21793] [--suite-wall "..."]
+                                          [--parent-lib path/to/another/libxmlhip.so]
                                           [--out profiles/index_update_timing.md; --legs exact: profiles/index_exact_timing.md]
 
   put   xml_index_put_rows alone on a --batch-video batch at the headline shape (H = 768, lpad = 128, bf16, two modalities),
@@ -28,6 +29,14 @@ usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compa
         f32 index and to the one-shot chain over the same rows; the 10 000-query pass and the 50-query replay next to the
         one-shot exact index of the same videos; certificate failures per pass under the running bound, after removing 10 % of
         the slots, and after tighten_error_bound(); hbm_bytes()
+  exactp  (not in the default set) exact-rank mode with the packed filter image (filter_tiles=N):
+        xml_index_put_rows_packed_exact on batches of 256 and 2 048 videos with the TVR clip counts next to
+        xml_index_put_rows_exact on the same rows; on the ragged corpus at the headline shape (ops.F16S model) the 10 000-query
+        pass and the 50-query replay on filter_tiles = what the corpus order needs and that plus 10 %, on the exact-rank index
+        with the plain per-slot filter image and on the one-shot exact index with length buckets: bitwise equality of the first
+        512 queries' lists, certificate failures per pass, hbm_bytes(); with --parent-lib PATH (a libxmlhip.so built from the
+        commit to compare with) an A/B of xml_index_put_rows_exact between the two libraries in this process.  Its report
+        (--out, default profiles/index_exact_packed_run.md) is the source of the last sections of profiles/index_exact_timing.md
 
 Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
 same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
@@ -726,6 +735,187 @@ def exact_leg(args, lines):
     torch.cuda.empty_cache()
 
 
+def exactp_put_leg(args, lines, b):
+    """xml_index_put_rows_packed_exact on a b-video f32 batch with the TVR clip counts next to xml_index_put_rows_exact on the
+    same rows and masks (the plain per-slot filter image), alternating."""
+    import bench
+    dev, h, lpad, bf16 = "cuda", 768, 128, torch.bfloat16
+    cap = 2 * b
+    lens = [int(x) for x in bench.real_clip_counts(b, lpad).tolist()]
+    g = torch.Generator(device=dev).manual_seed(0)
+    mask = (torch.arange(lpad, device=dev)[None] < torch.tensor(lens, device=dev)[:, None]).float()
+    enc = [(torch.randn((b, lpad, h), device=dev, generator=g), torch.randn((b, lpad, h), device=dev, generator=g), mask)
+           for _ in range(2)]
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)        # noqa: E731
+    split = lambda: ops.SplitRows(z(cap, lpad, h, dt=torch.int32), z(cap, lpad))   # noqa: E731
+    tiles = cap // 2                                          # as many tiles as the plain image: room for any lengths
+    image = lambda rows: [ops.TiledRows(z(ops.q2c_tiled_numel(rows, h, bf16), dt=bf16), cap * lpad, h, (cap, lpad, h))   # noqa: E731
+                          for _ in range(2)]
+    k6, pk6 = image(cap * lpad), image(tiles * 256)
+    resc, f2, err = [split() for _ in range(2)], [split() for _ in range(2)], [z(cap, lpad) for _ in range(2)]
+    mk = [z(cap, lpad) for _ in range(2)]
+    bits, pbits = [z(cap, 4, dt=torch.int32) for _ in range(2)], [z(2 * tiles, 4, dt=torch.int32) for _ in range(2)]
+    codes = torch.full((2 * tiles, 8), -2, dtype=torch.int32, device=dev)
+    ec, vlen, sid, live = z(2), z(cap, dt=torch.int32), z(cap, dt=torch.int32), z((cap + 31) // 32, dt=torch.int32)
+    scattered = torch.from_numpy(np.random.default_rng(0).permutation(cap)[:b].astype(np.int32)).to(dev)
+    table = BlockTable(tiles)
+    nbs = [blocks_of(n) for n in lens]
+    runs = torch.tensor(table.check_put(list(range(b)), nbs)[0], dtype=torch.int32, device=dev)
+    cols = lambda i: [e[i] for e in enc]                                           # noqa: E731
+
+    def put_exact():
+        ops.index_put_rows_exact(cols(0), cols(1), cols(2), scattered, None, k6, resc, f2, err, mk, bits, ec, vlen, sid, live, lpad)
+
+    def put_packed():
+        ops.index_put_rows_packed_exact(cols(0), cols(1), cols(2), scattered, None, runs, max(nbs), pk6, resc, f2, err, mk, pbits,
+                                        codes, ec, vlen, sid, live, lpad)
+
+    per = b * lpad * h
+    rest = 2 * (per * (4 + 4 + 4 + 4) + b * lpad * 4 * 5 + b * 16)                # f1, f2 read; re-score, feat2 written; norms, masks
+    by_exact, by_packed = rest + 2 * per * 2, rest + 2 * sum(nbs) * 16 * h * 2
+    res = []
+    for rnd in ("", ", again"):
+        res += [("xml_index_put_rows_packed_exact (mode f16s), TVR clip counts: %d blocks of %d" % (sum(nbs), 8 * b) + rnd,
+                 timed(put_packed, args.reps), by_packed),
+                ("xml_index_put_rows_exact (mode f16s), the same rows and masks" + rnd, timed(put_exact, args.reps), by_exact)]
+    lines += ["", "### Batches of %d videos" % b, "",
+              "%d videos x %d clips x H = %d, f32 rows, two modalities, prefix masks of the TVR clip counts, scattered slots of %d; "
+              "runs handed out by a BlockTable of %d tiles.  Bytes counted from the shapes: %.1f MB per packed put (the filter rows "
+              "of the runs only), %.1f MB per plain exact-rank put." % (b, lpad, h, cap, tiles, by_packed / 1e6, by_exact / 1e6),
+              "", "| what | time per call | videos / s | bytes / s |", "|---|---|---|---|"]
+    for name, t, moved in res:
+        lines.append("| %s | %s | %.3g | %.2f TB/s |" % (name, fmt(t, "us"), b / (t[0] * 1e-3), moved / (t[0] * 1e-3) / 1e12))
+    med = lambda i: (res[i][1][0] + res[i + 2][1][0]) / 2                         # noqa: E731
+    lines += ["", "Medians, mean of both rounds: packed exact-rank put %.1f us, exact-rank put %.1f us (x %.3f)."
+              % (med(0) * 1e3, med(1) * 1e3, med(0) / med(1))]
+    for ln in lines[-10:]:
+        print(ln, flush=True)
+    torch.cuda.empty_cache()
+
+
+def exact_put_ab_leg(args, lines):
+    """xml_index_put_rows_exact of this library against the same entry of another build of it (--parent-lib: a libxmlhip.so
+    built from the commit to compare with), both loaded into this process and called through the C ABI on the same tensors
+    (exact_put_leg's shapes), alternating, four rounds: the regression guard of a change to that kernel's source."""
+    import ctypes
+    from tvretrieval_amd import _lib
+    new, old = _lib.load(), ctypes.CDLL(os.path.abspath(args.parent_lib))
+    old.xml_index_put_rows_exact.restype, old.xml_index_put_rows_exact.argtypes = _lib.SIGNATURES_EXACT["xml_index_put_rows_exact"]
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())                                  # noqa: E731
+    lines += ["", "## (g) A/B of xml_index_put_rows_exact against another build of the library", "",
+              "`xml_index_put_rows_exact` of this library and of `--parent-lib` (built from the parent commit), loaded into one "
+              "process and called through the C ABI on the same tensors (section (a)'s shapes: ones masks, scattered slots, mode "
+              "f16s, tiled filter image), alternating, four rounds of %d repetitions each." % args.reps]
+    for b in (256, 2048):
+        dev, h, lpad, bf16 = "cuda", 768, 128, torch.bfloat16
+        cap = 2 * b
+        g = torch.Generator(device=dev).manual_seed(0)
+        enc = [(torch.randn((b, lpad, h), device=dev, generator=g), torch.randn((b, lpad, h), device=dev, generator=g),
+                torch.ones((b, lpad), device=dev)) for _ in range(2)]
+        z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt, device=dev)    # noqa: E731
+        side, outs = [], []
+        for _ in range(2):      # k6, rescore, rescore_inv, feat2, feat2_inv, err, imask, bits
+            t = [z(ops.q2c_tiled_numel(cap * lpad, h, bf16), dt=bf16), z(cap, lpad, h, dt=torch.int32), z(cap, lpad),
+                 z(cap, lpad, h, dt=torch.int32), z(cap, lpad), z(cap, lpad), z(cap, lpad), z(cap, 4, dt=torch.int32)]
+            side += [ptr(x) for x in t]
+            outs += t
+        ec, vlen, sid, live = z(2), z(cap, dt=torch.int32), z(cap, dt=torch.int32), z((cap + 31) // 32, dt=torch.int32)
+        outs += [ec, vlen, sid, live]
+        slots = torch.from_numpy(np.random.default_rng(0).permutation(cap)[:b].astype(np.int32)).to(dev)
+
+        def call(lib):
+            st = lib.xml_index_put_rows_exact(2, ops.EXACT_F16S, ptr(enc[0][0]), ptr(enc[0][1]), ptr(enc[0][2]), ptr(enc[1][0]),
+                                              ptr(enc[1][1]), ptr(enc[1][2]), ptr(slots), None, b, lpad, *side, ptr(ec), ptr(vlen),
+                                              ptr(sid), ptr(live), cap, lpad, lpad, h, 0, 1,
+                                              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            if st != 0:
+                raise RuntimeError("xml_index_put_rows_exact returned %d" % st)
+        call(new)
+        mine = [t.clone() for t in outs]
+        for t in outs:
+            t.zero_()
+        call(old)
+        same = all(torch.equal(x.view(torch.uint8), y.view(torch.uint8)) for x, y in zip(mine, outs))
+        rounds = [(timed(lambda: call(old), args.reps), timed(lambda: call(new), args.reps)) for _ in range(4)]
+        mo, mn = (float(np.median([r[i][0] for r in rounds])) for i in (0, 1))
+        lo, hi = min(r[0][0] for r in rounds), max(r[0][0] for r in rounds)
+        lines += ["", "### Batches of %d videos; every output tensor bitwise equal: %s" % (b, same), "",
+                  "| round | --parent-lib | this library |", "|---|---|---|"]
+        lines += ["| %d | %s | %s |" % (i, fmt(r[0], "us"), fmt(r[1], "us")) for i, r in enumerate(rounds)]
+        lines += ["", "Median of the four medians: --parent-lib %.1f us, this library %.1f us (%+.2f %%); the medians of --parent-lib "
+                  "span %.1f .. %.1f us (%.2f %% of their median)."
+                  % (mo * 1e3, mn * 1e3, (mn / mo - 1) * 100, lo * 1e3, hi * 1e3, (hi - lo) / mo * 100)]
+        for ln in lines[-9:]:
+            print(ln, flush=True)
+        del enc, outs, mine, side
+        torch.cuda.empty_cache()
+
+
+def exactp_leg(args, lines):
+    """Exact-rank mode with the packed filter image (create(..., exact_rank=True, filter_tiles=N)) on the ragged corpus at the
+    headline shape: the put next to xml_index_put_rows_exact, the 10 000-query pass and the 50-query replay on four forms."""
+    import bench
+    lines += ["## Exact-rank mode with the packed filter image (create(..., exact_rank=True, filter_tiles=N), mode f16s)", "",
+              "## (e) The packed exact-rank put next to xml_index_put_rows_exact"]
+    for b in (256, 2048):
+        exactp_put_leg(args, lines, b)
+    _, _, l, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3r"]
+    nv, nq = args.videos, args.queries
+    be = bench.HipBackend(0)
+    torch.manual_seed(0)
+    model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), ops.F16S)
+    lens = bench.real_clip_counts(nv, l)
+    n_clips = [int(x) for x in lens.tolist()]
+    batches = lambda: bench.context_batches(0, nv, l, dv, ds, True, True, be.device, lens=lens)      # noqa: E731
+    need, straddles = tiles_in_corpus_order(n_clips, bench.CHUNK)
+    keys = ("top_indices", "top_scores", "flat_indices", "flat_scores")
+    with torch.no_grad():
+        forms = [("filter_tiles=%d (corpus order)" % t,
+                  MutableCorpusIndex.from_batches(model, batches(), nv, l_ref=l, n_clips=n_clips, exact_rank=True, filter_tiles=t), t)
+                 for t in (need, -(-need * 11 // 10))]
+        forms.append(("exact_rank=True, plain per-slot filter image",
+                      MutableCorpusIndex.from_batches(model, batches(), nv, l_ref=l, exact_rank=True), (nv + 1) // 2))
+        fixed = inf.build_corpus_index(model, batches(), l_ref=l, n_videos=nv, exact_filter=True)
+        plan = fixed.feat1n[fixed.modalities[0]].plan
+        forms.append(("one-shot build_corpus_index(exact_filter=True), length buckets", fixed, plan.n_tiles))
+        qf, qm = bench.synth_queries(nq, dq, be.device)
+        kw = dict(n_valid_tokens=int(qm.sum().item()))
+        passes = [[], []]
+        for rnd in (0, 1):
+            for _, index, _ in forms:
+                passes[rnd].append(timed(lambda: inf.vcmr_search(model, index, qf, qm, **kw), args.pass_reps, 2))
+        firsts = [inf.vcmr_search(model, index, qf[:512], qm[:512]) for _, index, _ in forms]
+        same = [all(bool(torch.equal(firsts[2][k], o[k])) for k in keys) for o in firsts]
+        fails = [int(inf.vcmr_search(model, index, qf, qm, **kw)["exact"]["n_fail"]) for _, index, _ in forms]
+        bounds = [[float(index.exact.e_c[m]) for m in index.modalities] for _, index, _ in forms]
+        graphs = [graph_ms(model, index, qf, qm) for _, index, _ in forms]
+    lines += ["", "## (f) Search on the ragged corpus (%d videos x %d clips, real TVR clip counts, hidden %d, ops.F16S model, %d queries)"
+              % (nv, l, hidden, nq), "",
+              "A BlockTable filled in corpus order, %d videos per call, needs %d tiles (%d straddling videos); the one-shot plan "
+              "packs the corpus into %d tiles; the plain per-slot filter image has %d.  First 512 queries, video lists, weights, "
+              "moment lists and scores against the plain exact-rank index: %s."
+              % (bench.CHUNK, need, straddles, plan.n_tiles, (nv + 1) // 2,
+                 "; ".join("%s: %s" % (n, "bitwise identical" if s else "NOT identical") for (n, _, _), s in zip(forms, same))),
+              "", "| index | filter tiles | vcmr_search, %d queries | again | 50-query graph replay | failing certificates per pass | "
+              "e_c (video, sub) | hbm_bytes() |" % nq, "|---|---|---|---|---|---|---|---|"]
+    for i, (name, index, t) in enumerate(forms):
+        lines.append("| %s | %d | %s | %s | %s | %d | %s | %.3f GB |"
+                     % (name, t, fmt(passes[0][i]), fmt(passes[1][i]), fmt(graphs[i]), fails[i],
+                        ", ".join("%.6g" % x for x in bounds[i]), index.hbm_bytes() / 1e9))
+    med = [(passes[0][i][0] + passes[1][i][0]) / 2 for i in range(len(forms))]
+    for i in (0, 1):
+        lines += ["", "%s: %.1f ms per pass against %.1f ms on the plain filter image (%+.1f %%) and %.1f ms one-shot (x %.3f); replay "
+                  "%.3f ms against %.3f ms and %.3f ms."
+                  % (forms[i][0], med[i], med[2], (med[i] / med[2] - 1) * 100, med[3], med[i] / med[3], graphs[i][0], graphs[2][0],
+                     graphs[3][0])]
+    for ln in lines[-14:]:
+        print(ln, flush=True)
+    del forms, fixed, firsts
+    torch.cuda.empty_cache()
+    if args.parent_lib:
+        exact_put_ab_leg(args, lines)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="put,putp,e2e,c3,c3r,c3rp")
@@ -735,11 +925,13 @@ def main():
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--pass-reps", type=int, default=5)
     ap.add_argument("--chains-l", type=int, default=128)
+    ap.add_argument("--parent-lib", default="")
     ap.add_argument("--suite-wall", default="")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:      # the exact leg has a report of its own
-        args.out = os.path.join(ROOT, "profiles", "index_exact_timing.md" if args.legs == "exact" else "index_update_timing.md")
+        args.out = os.path.join(ROOT, "profiles", {"exact": "index_exact_timing.md", "exactp": "index_exact_packed_run.md"}.get(
+            args.legs, "index_update_timing.md"))
     if not torch.cuda.is_available():
         sys.exit("bench_index_update.py measures on the GPU; none is visible")
     p = torch.cuda.get_device_properties(0)
@@ -765,6 +957,8 @@ def main():
         chains_leg(args, lines)
     if "exact" in legs:
         exact_leg(args, lines)
+    if "exactp" in legs:
+        exactp_leg(args, lines)
     if args.suite_wall:
         lines += ["", "## GPU test wall time", "", args.suite_wall]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -275,13 +275,21 @@ SIGNATURES_VIEW = {
                                 [c_void_p]),
 }
 
+# the companion header include/xmlhip_index_exact_packed.h (tests/test_index_exact_packed_capi.py checks): exact-rank mode with
+# the packed filter image
+SIGNATURES_EXACT_PACKED = {
+    "xml_index_put_rows_packed_exact": (c_int, [c_int] * 2 + [c_void_p] * 9 + [c_int] * 3 + [c_void_p] * 21 + [c_int] * 6 +
+                                        [c_void_p]),
+}
+
 _lib = None
 
 
 def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
-            list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()):
+            list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()) + \
+            list(SIGNATURES_EXACT_PACKED.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

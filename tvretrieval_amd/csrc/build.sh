@@ -26,7 +26,8 @@ build() {   # $1 = object dir, $2 = extra flags, $3 = output, $4.. = sources
        || [ debug.h -nt "$o" ] || [ l2norm.h -nt "$o" ] || [ dispatch.h -nt "$o" ] || [ ring256.h -nt "$o" ] || [ split16.h -nt "$o" ] \
        || [ index_rows.h -nt "$o" ] || [ ../../include/xmlhip.h -nt "$o" ] || [ ../../include/xmlhip_index.h -nt "$o" ] \
        || [ ../../include/xmlhip_index_compact.h -nt "$o" ] || [ ../../include/xmlhip_index_parts.h -nt "$o" ] \
-       || [ ../../include/xmlhip_index_exact.h -nt "$o" ] || [ ../../include/xmlhip_index_view.h -nt "$o" ]; then
+       || [ ../../include/xmlhip_index_exact.h -nt "$o" ] || [ ../../include/xmlhip_index_view.h -nt "$o" ] \
+       || [ ../../include/xmlhip_index_exact_packed.h -nt "$o" ]; then
       $HIPCC $FLAGS $extra -I. -c "$s" -o "$o" &
       pids+=($!)
     fi

@@ -1,7 +1,7 @@
 // What the kernels of a resident index share (index_build.hip, index_update.hip, index_update_exact.hip, index_compact.hip,
 // index_view.hip, exact.hip): the geometry of K6's tile image, the per-modality operand structs of the
-// update launches, the slot-state epilogue of a put and the slot-freeing tail of a clear, and the round-to-bf16 step of the
-// exact-rank filter image.
+// update launches, the slot-state epilogue of a put, the run records and the bits-and-codes tail of a put into the packed
+// image, the slot-freeing tail of a clear, and the round-to-bf16 step of the exact-rank filter image.
 #pragma once
 #include "common.h"
 
@@ -106,6 +106,37 @@ __device__ __forceinline__ unsigned long long put_slot_state(int keep, int lb, i
   return mine;
 }
 
+// ---- the PACKED form (index_update.hip's header comment; xml_q2c_scores_packed): where the K6 rows of a put go, the run
+// records of the packed entries, and the tail of a put that keeps the run's mask fields and codes in step with its rows
+enum { ROW_MAJOR, TILED, PACKED };
+
+struct PackedRuns {        // the packed form's operands; unused by the others
+  const int32_t* runs;     // (first block, blocks) per record
+  int32_t* codes;
+  int n_tiles, nb_max;
+};
+
+// a run record (first block, block count) the kernels act on: 1..nb_max blocks, inside the image, inside one tile
+__device__ __forceinline__ bool run_ok(int first, int nb, int nb_max, int n_tiles) {
+  return nb >= 1 && nb <= nb_max && first >= 0 && first <= n_tiles * 16 - nb && (first >> 4) == ((first + nb - 1) >> 4);
+}
+
+// called by waves 0 and 1 (threadIdx.x < 128) behind put_slot_state, `mine` its ballot: the 16-bit mask fields of the run's
+// nb blocks (two videos may share a word: atomics) and, by modality 0, the run's codes
+__device__ __forceinline__ void put_run_bits_codes(unsigned long long mine, int first, int nb, int slot, bool second,
+                                                   int32_t* __restrict__ bits, int32_t* __restrict__ codes) {
+  const int t = threadIdx.x;
+  const int k = (t >> 6) * 4 + (t & 63);                   // lanes 0..3 of a wave: blocks 4 w .. 4 w + 3 of the run
+  if ((t & 63) < 4 && k < nb) {
+    unsigned int* word = reinterpret_cast<unsigned int*>(bits) + ((first + k) >> 1);
+    const int sh = ((first + k) & 1) * 16;
+    const unsigned int b16 = (unsigned int)(mine >> (16 * (t & 63))) & 0xffffu;
+    atomicAnd(word, ~(0xffffu << sh));                     // (same thread, same address: the OR comes after the AND)
+    atomicOr(word, b16 << sh);
+  }
+  if (!second && t < nb) codes[first + t] = t == nb - 1 ? slot : (((first + t) & 15) == 7 ? -3 : -1);
+}
+
 // ---- the slot-freeing tail of a clear (one workgroup of >= lpad threads per slot, thread t): mask rows zeroed, vlen = l_ref,
 // live bit cleared; the feature rows stay.  imask_b: NULL when there is one modality.
 __device__ __forceinline__ void free_slot_state(int slot, int t, int lpad, int l_ref, float* __restrict__ imask_a,
@@ -121,8 +152,11 @@ __device__ __forceinline__ void free_slot_state(int slot, int t, int lpad, int l
 }
 
 // ---- one trip of the exact-rank filter rows (round_bf16_rows_err_kernel, exact.hip; the exact put): the 8 values rounded to
-// bf16 (returned packed) and s += sum of (f - rne_bf16(f))^2, elements in order
+// bf16 (returned packed) and s += sum of (f - rne_bf16(f))^2, elements in order.  The square and the sum are two roundings
+// (contract off): with -ffp-contract=fast the compiler fuses them or not by the shape of the code around the call, and the
+// callers' values are bitwise one another's.
 __device__ __forceinline__ uint4 round_bf16_err8(const float (&f)[8], float& s) {
+#pragma clang fp contract(off)
   const uint4 packed = pack16<bf16_t>(f);
   float g[8];
   unpack16<bf16_t>(packed, g);

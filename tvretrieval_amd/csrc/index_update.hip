@@ -36,19 +36,7 @@
 
 namespace {
 
-enum { ROW_MAJOR, TILED, PACKED };      // where the K6 rows of a put go
-
-struct PackedRuns {        // the packed form's operands; unused by the others
-  const int32_t* runs;     // (first block, blocks) per record
-  int32_t* codes;
-  int n_tiles, nb_max;
-};
-
-// a run record (first block, block count) the kernels act on: 1..nb_max blocks, inside the image, inside one tile
-__device__ __forceinline__ bool run_ok(int first, int nb, int nb_max, int n_tiles) {
-  return nb >= 1 && nb <= nb_max && first >= 0 && first <= n_tiles * 16 - nb && (first >> 4) == ((first + nb - 1) >> 4);
-}
-
+// (ROW_MAJOR | TILED | PACKED, PackedRuns, run_ok and the bits-and-codes tail of a packed put: index_rows.h)
 template <typename T, int FORM>
 __global__ __launch_bounds__(256) void index_put_rows_kernel(Sides<BatchSide> batch, Sides<IndexSide> index,
                                                              const int32_t* __restrict__ slots,
@@ -104,15 +92,7 @@ __global__ __launch_bounds__(256) void index_put_rows_kernel(Sides<BatchSide> ba
   const int w = t >> 6;
   if (w >= 2) return;
   if constexpr (FORM == PACKED) {
-    const int k = w * 4 + (t & 63);                        // lanes 0..3 of a wave: blocks 4 w .. 4 w + 3 of the run
-    if ((t & 63) < 4 && k < nb) {
-      unsigned int* word = reinterpret_cast<unsigned int*>(ix.bits) + ((first + k) >> 1);
-      const int sh = ((first + k) & 1) * 16;
-      const unsigned int b16 = (unsigned int)(mine >> (16 * (t & 63))) & 0xffffu;
-      atomicAnd(word, ~(0xffffu << sh));                   // (same thread, same address: the OR comes after the AND)
-      atomicOr(word, b16 << sh);
-    }
-    if (!second && t < nb) pk.codes[first + t] = t == nb - 1 ? slot : (((first + t) & 15) == 7 ? -3 : -1);
+    put_run_bits_codes(mine, first, nb, slot, second, ix.bits, pk.codes);
   } else if ((t & 63) == 0) {                              // 4 words per slot
     ix.bits[(int64_t)slot * 4 + 2 * w] = (int32_t)(uint32_t)mine;
     ix.bits[(int64_t)slot * 4 + 2 * w + 1] = (int32_t)(uint32_t)(mine >> 32);

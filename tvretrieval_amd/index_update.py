@@ -653,14 +653,19 @@ class MutableCorpusIndex(CorpusIndex):
     bound on the device: every put raises it (ops.index_put_rows_exact, one launch for all operands of the slots), the
     certificate of a search reads it through a pointer.  remove leaves it alone -- a bound that is too large only sends more
     queries to the second tier --; tighten_error_bound() recomputes it over the live slots.  Searches run the exact-rank
-    chains of inference under `live AND video_allow`; a GraphedVcmrSearch (ops.F16S model) stays valid across updates."""
+    chains of inference under `live AND video_allow`; a GraphedVcmrSearch (ops.F16S model) stays valid across updates.
+    create(..., exact_rank=True, filter_tiles=N): the bf16 filter image ALONE is the packed image over
+    N tiles, with blocks / codes / mask_bits as in the packed form (ops.index_put_rows_packed_exact: the filter rows, codes
+    and mask words of a video go to its run, everything else to its slot, one launch); re-score rows, feat2, err_rows and the
+    bound are those of the plain exact-rank index bit for bit, mask and vlen follow the effective mask of the packed form.
+    n_clips=, compact() and auto_compact work as there; the filter then costs N tiles, not capacity / 2."""
 
     def __init__(self, *a, **kw):
         raise TypeError("use MutableCorpusIndex.create(model, capacity) or MutableCorpusIndex.from_batches(...)")
 
     @classmethod
     def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None,
-               auto_compact=False, part_overlap=None, max_parts=32, exact_rank=False):
+               auto_compact=False, part_overlap=None, max_parts=32, exact_rank=False, filter_tiles=None):
         """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l).
         tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring).
         auto_compact (the packed form): an add / put / replace that finds no run although enough blocks are free runs
@@ -669,14 +674,19 @@ class MutableCorpusIndex(CorpusIndex):
         docstring), cut by ingest.plan_parts(n_clips, l_ref, overlap=O); max_parts bounds the parts of one video.
         exact_rank=True (an f32 or ops.F16S model; tiles=None, no part_overlap): exact-rank mode (class docstring) -- the
         index holds the bf16 filter image, the f32-grade re-score rows and the running error bound, and searches return the
-        f32 path's lists."""
+        f32 path's lists.
+        filter_tiles=N (with exact_rank=True only): the bf16 FILTER image alone is the packed image over N tiles -- re-score
+        rows, feat2 and error norms stay per slot --; updates then take n_clips=, compact() and auto_compact work as in the
+        packed form (class docstring)."""
         dt = getattr(model, "compute_dtype", torch.float32)
+        if filter_tiles is not None:
+            cls._check_filter_tiles(filter_tiles, exact_rank, tiles, part_overlap)
         if exact_filter or (dt is hip_ops.F16S and not exact_rank):
             raise ValueError("MutableCorpusIndex: no exact-rank mode (an ops.F16S model / exact_filter=True) -- its certificate "
                              "rests on e_c, a bound over the WHOLE corpus that a one-video update cannot maintain by value; "
                              "create(..., exact_rank=True) keeps that bound on the device instead")
         if exact_rank:
-            cls._check_exact_rank(model, dt, l_ref, tiles, part_overlap)
+            cls._check_exact_rank(model, dt, l_ref, tiles, part_overlap, filter_tiles)
         if parts is not None:
             raise ValueError("MutableCorpusIndex: no parts table -- the fold of parts into videos is planned for a fixed corpus")
         if video_offset or n_total is not None:
@@ -713,7 +723,7 @@ class MutableCorpusIndex(CorpusIndex):
         cap = table.capacity
         self = object.__new__(cls)
         if exact_rank:
-            return self._init_exact(model, table, mods, l_ref, lpad, h, dev)
+            return self._init_exact(model, table, mods, l_ref, lpad, h, dev, filter_tiles, auto_compact)
         feat2 = {m: torch.zeros((cap, lpad, h), dtype=act, device=dev) for m in mods}
         mask = {m: torch.zeros((cap, lpad), dtype=torch.float32, device=dev) for m in mods}
         self.blocks, self.codes, self.auto_compact = blocks, None, bool(auto_compact) and blocks is not None
@@ -749,12 +759,26 @@ class MutableCorpusIndex(CorpusIndex):
         return image
 
     @staticmethod
-    def _check_exact_rank(model, dt, l_ref, tiles, part_overlap):
+    def _check_filter_tiles(filter_tiles, exact_rank, tiles, part_overlap):
+        """What create(..., filter_tiles=N) refuses about the keyword itself, before any device allocation."""
+        if not exact_rank:
+            raise ValueError("MutableCorpusIndex: filter_tiles=%r without exact_rank=True -- it packs the bf16 FILTER image of "
+                             "exact-rank mode; an index without that mode packs its K6 image with tiles=N" % (filter_tiles,))
+        if tiles is not None or part_overlap is not None:
+            raise ValueError("MutableCorpusIndex: filter_tiles=%r together with %s -- exact-rank mode (exact_rank=True) keeps "
+                             "re-score rows and error norms per slot and packs the filter image alone (tiles=None), and it "
+                             "holds no chains of slots" % (filter_tiles, "tiles=" if tiles is not None else "part_overlap="))
+        if isinstance(filter_tiles, bool) or int(filter_tiles) != filter_tiles or int(filter_tiles) <= 0:
+            raise ValueError("MutableCorpusIndex: filter_tiles must be a positive integer number of 256-row tiles, got %r"
+                             % (filter_tiles,))
+
+    @staticmethod
+    def _check_exact_rank(model, dt, l_ref, tiles, part_overlap, filter_tiles=None):
         """What create(..., exact_rank=True) refuses, before any device allocation."""
         if tiles is not None:
             raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) on the packed K6 image (tiles=%r) is not "
                              "built -- the filter image, the re-score rows and the error norms are kept per slot; use "
-                             "tiles=None" % (tiles,))
+                             "tiles=None (filter_tiles=N packs the filter image alone)" % (tiles,))
         if part_overlap is not None:
             raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) and part_overlap= exclude each other -- "
                              "exact-rank mode never forms the f32 (Nq, slots) score matrix that the best part of a video is "
@@ -772,10 +796,17 @@ class MutableCorpusIndex(CorpusIndex):
             raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True): xml_index_put_rows_exact takes f32 rows of up "
                              "to 128 clips and a hidden size of whole 64-byte slices (a multiple of 32 for an ops.F16S "
                              "model); got lpad %d, hidden %d" % (lpad, h))
+        if filter_tiles is not None and (lpad != 128 or not hip_ops.q2c_tiled_ok(128, h, torch.bfloat16)):
+            raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) with the packed filter image "
+                             "(filter_tiles=%d) needs the tiled bf16 K6 operand -- 128-clip slots and bf16 rows the tiled "
+                             "kernel takes; got lpad %d, hidden %d.  Use filter_tiles=None" % (filter_tiles, lpad, h))
 
-    def _init_exact(self, model, table, mods, l_ref, lpad, h, dev):
-        """The tensors of an exact-rank index (create(..., exact_rank=True)): allocated once, zero-filled."""
+    def _init_exact(self, model, table, mods, l_ref, lpad, h, dev, filter_tiles=None, auto_compact=False):
+        """The tensors of an exact-rank index (create(..., exact_rank=True)): allocated once, zero-filled.  filter_tiles=N:
+        the filter image is the packed one, with the BlockTable, the code table and the packed mask words of the packed
+        form; everything else stays per slot."""
         cap = table.capacity
+        blocks = None if filter_tiles is None else BlockTable(filter_tiles)
         mode = _inference.exact_mode_of(model)
         f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)         # noqa: E731
 
@@ -785,10 +816,15 @@ class MutableCorpusIndex(CorpusIndex):
             return f32(cap, lpad, h)
         feat2 = {m: rows() for m in mods}
         mask = {m: f32(cap, lpad) for m in mods}
-        self.blocks, self.codes, self.auto_compact = None, None, False
-        self.mask_bits = {m: torch.zeros((cap, 4), dtype=torch.int32, device=dev) for m in mods}
-        # the bf16 FILTER image, in the layout create chooses for bf16 rows of this width
-        feat1n = {m: self._alloc_k6_image(m, (cap, lpad, h), torch.bfloat16, dev) for m in mods}
+        self.blocks, self.codes, self.auto_compact = blocks, None, bool(auto_compact) and blocks is not None
+        n_words = cap if blocks is None else 2 * blocks.n_tiles
+        self.mask_bits = {m: torch.zeros((n_words, 4), dtype=torch.int32, device=dev) for m in mods}
+        plan = None
+        if blocks is not None:                          # the packed filter image: every block unused
+            self.codes = torch.full((2 * blocks.n_tiles, 8), -2, dtype=torch.int32, device=dev)
+            plan = _TablePlan(blocks, self.codes, cap)
+        # the bf16 FILTER image: packed, else in the layout create chooses for bf16 rows of this width
+        feat1n = {m: self._alloc_k6_image(m, (cap, lpad, h), torch.bfloat16, dev, plan) for m in mods}
         CorpusIndex.__init__(self, mods, feat1n, feat2, mask, l_ref)
         cells = f32(len(mods))
         self.exact = _inference.ExactFilter({m: rows() for m in mods}, _inference._DeviceBound(cells, mods), n_candidates=256,
@@ -957,9 +993,18 @@ class MutableCorpusIndex(CorpusIndex):
             if clears:     # videos that move: their old runs become unused blocks BEFORE the put, whose runs may reuse them
                 self._clear([-1] * len(clears), clears)
             rec = self._to_device(slots + ids + [x for r in runs for x in r])
-            hip_ops.index_put_rows_packed(*batch, rec[:b], rec[b:2 * b], rec[2 * b:].view(b, 2), max(nbs),
-                                          *self._sides(self.feat1n, self.feat2, self.mask, self.mask_bits), self.codes,
-                                          self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
+            records = (rec[:b], rec[b:2 * b], rec[2 * b:].view(b, 2), max(nbs))
+            if self.exact is not None:     # the packed FILTER image: its runs and every per-slot operand, one launch
+                ex = self.exact
+                hip_ops.index_put_rows_packed_exact(*batch, *records,
+                                                    *self._sides(self.feat1n, ex.feat1n_f32, self.feat2, ex.err_rows, self.mask,
+                                                                 self.mask_bits),
+                                                    self.codes, ex.e_c_dev, self.vlen, self.slot_ids, self.live.view(-1),
+                                                    self.l_ref)
+            else:
+                hip_ops.index_put_rows_packed(*batch, *records,
+                                              *self._sides(self.feat1n, self.feat2, self.mask, self.mask_bits), self.codes,
+                                              self.vlen, self.slot_ids, self.live.view(-1), self.l_ref)
             self.blocks.commit_put(slots, runs)
             return
         both = self._to_device([slots, ids])
@@ -1048,7 +1093,7 @@ class MutableCorpusIndex(CorpusIndex):
         self.blocks.commit_compact(plan)
         after = self.blocks.stats()
         moved = sum(nb for rnd in plan for (_, nb), _ in rnd["moves"].values())
-        row_bytes = sum(self.feat2[m].shape[2] * self.feat2[m].element_size() for m in mods)
+        row_bytes = sum(self.feat1n[m].hidden * self.feat1n[m].element_size() for m in mods)      # the image's rows move
         return dict(rounds=len(plan), blocks_moved=moved, tiles_touched=len({r[0] for rnd in plan for r in rnd["records"]}),
                     tiles_emptied=after["tiles_empty"] - before["tiles_empty"],
                     largest_free_run_before=before["largest_free_run"], largest_free_run_after=after["largest_free_run"],

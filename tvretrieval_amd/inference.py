@@ -32,9 +32,9 @@ records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and search
 best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
 index_clear_rows) and the searches and updates of one with chains of slots for long videos (index_set_chains,
 chain_best_allow, chain_best_rows) and the updates and searches of an exact-rank one (index_put_rows_exact,
-exact_certificate_dev, index_exact_bound) and the subset views of video_subset (index_gather_blocks; HIP only, a search with
-subset= refuses any other backend) call further entries of tvretrieval_amd.ops; a backend without them serves every search
-that does not ask for those.
+exact_certificate_dev, index_exact_bound; with the packed filter image index_put_rows_packed_exact) and the subset views of
+video_subset (index_gather_blocks; HIP only, a search with subset= refuses any other backend) call further entries of
+tvretrieval_amd.ops; a backend without them serves every search that does not ask for those.
 """
 import numpy as np
 import torch

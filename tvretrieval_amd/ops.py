@@ -1675,8 +1675,9 @@ def chain_best_rows(scores, chains, video):
 EXACT_F32, EXACT_F16S = 0, 1          # XML_EXACT_F32 / XML_EXACT_F16S
 
 
-def _exact_sides(k6, rescore, feat2, err, imask, bits):
-    """Checks the per-modality tensors of an exact-rank slot; returns (capacity, lpad, hidden, tiled, mode, k6 buffers)."""
+def _exact_sides(k6, rescore, feat2, err, imask, bits, n_tiles=None):
+    """Checks the per-modality tensors of an exact-rank slot; returns (capacity, lpad, hidden, tiled, mode, k6 buffers).
+    n_tiles (index_put_rows_packed_exact): the filter image is the packed one over n_tiles * 256 rows, bits its mask words."""
     n_mod = len(feat2)
     if n_mod not in (1, 2) or not (len(k6) == len(rescore) == len(err) == len(imask) == len(bits) == n_mod):
         raise _lib.XmlHipError("exact index update: 1 or 2 modalities, the same number of k6 / rescore / feat2 / err / mask / "
@@ -1698,9 +1699,22 @@ def _exact_sides(k6, rescore, feat2, err, imask, bits):
             if tuple(t.shape) != (cap, lpad, hidden):
                 raise _lib.XmlHipError("exact index update: %s of shape %s expected" % (name, (cap, lpad, hidden)))
         _req(err[m], "err", torch.float32); _req(imask[m], "mask", torch.float32); _req(bits[m], "bits", torch.int32)
-        if tuple(err[m].shape) != (cap, lpad) or tuple(imask[m].shape) != (cap, lpad) or tuple(bits[m].shape) != (cap, 4):
-            raise _lib.XmlHipError("exact index update: err / mask (capacity, lpad) and bits (capacity, 4) expected")
-        data.append(_k6_side("exact index update", k6[m], tiled, cap, lpad, hidden, torch.bfloat16, "filter image"))
+        if tuple(err[m].shape) != (cap, lpad) or tuple(imask[m].shape) != (cap, lpad):
+            raise _lib.XmlHipError("exact index update: err / mask (capacity, lpad) expected")
+        if n_tiles is None:
+            if tuple(bits[m].shape) != (cap, 4):
+                raise _lib.XmlHipError("exact index update: bits (capacity, 4) expected")
+            data.append(_k6_side("exact index update", k6[m], tiled, cap, lpad, hidden, torch.bfloat16, "filter image"))
+            continue
+        if lpad != 128 or tuple(bits[m].shape) != (2 * n_tiles, 4) or not tiled or not isinstance(k6[m], TiledRows):
+            raise _lib.XmlHipError("packed exact index update: slots of 128 clips, bits (2 * n_tiles, 4) and a TiledRows filter "
+                                   "image expected")
+        d = k6[m].data
+        _req(d, "k6", torch.bfloat16)
+        if not q2c_tiled_ok(128, hidden, d.dtype) or d.numel() != q2c_tiled_numel(n_tiles * 256, hidden, d.dtype):
+            raise _lib.XmlHipError("packed exact index update: the filter image does not hold n_tiles * 256 rows of H = %d"
+                                   % hidden)
+        data.append(d)
     return cap, lpad, hidden, tiled, EXACT_F16S if split else EXACT_F32, data
 
 
@@ -1729,6 +1743,38 @@ def index_put_rows_exact(f1, f2, masks, slots, ids, k6, rescore, feat2, err, ima
         n_mod, mode, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), b, lb, *side,
         _p(ec), _p(vlen), _p(slot_ids), _p(live), cap, lpad, int(l_ref), hidden, XML_F32, int(tiled), _stream()),
         "xml_index_put_rows_exact")
+
+
+def index_put_rows_packed_exact(f1, f2, masks, slots, ids, runs, nb_max, k6, rescore, feat2, err, imask, bits, codes, ec, vlen,
+                                slot_ids, live, l_ref):
+    """xml_index_put_rows_packed_exact (include/xmlhip_index_exact_packed.h): index_put_rows_exact on an exact-rank index whose
+    bf16 FILTER image is the packed one -- the filter rows, codes and mask words go to the videos' runs as
+    index_put_rows_packed puts them, every per-slot operand (rescore, feat2, err, mask) and the running bound are written as
+    index_put_rows_exact writes them; one launch, nothing read back.  runs (b, 2) int32 device, nb_max: index_put_rows_packed;
+    k6: per-modality bf16 TiledRows over n_tiles * 256 rows; bits: per-modality (2 * n_tiles, 4); codes (2 * n_tiles, 8)
+    int32; the rest as index_put_rows_exact."""
+    n_tiles = _codes_tiles("index_put_rows_packed_exact", codes)
+    cap, _, hidden, _, mode, data = _exact_sides(k6, rescore, feat2, err, imask, bits, n_tiles)
+    _index_state(vlen, live, cap, slot_ids)
+    n_mod = len(feat2)
+    _req(ec, "ec", torch.float32)
+    if ec.numel() != n_mod:
+        raise _lib.XmlHipError("index_put_rows_packed_exact: ec (n_mod,) f32 expected")
+    b, lb = _batch_sides("index_put_rows_packed_exact", f1, f2, masks, n_mod, hidden, torch.float32)
+    if _packed_records(slots, runs, "index_put_rows_packed_exact") != b or \
+            (ids is not None and _req(ids, "ids", torch.int32).numel() != b):
+        raise _lib.XmlHipError("index_put_rows_packed_exact: one slot, run (and id) per video of the batch")
+    split = mode == EXACT_F16S
+    side = []
+    for m in range(n_mod):
+        side += [_p(data[m]), _p(rescore[m]), _p(rescore[m].inv) if split else None, _p(feat2[m]),
+                 _p(feat2[m].inv) if split else None, _p(err[m]), _p(imask[m]), _p(bits[m])]
+    side += [None] * (16 - len(side))
+    sec = _second(n_mod)
+    check(_lib.load().xml_index_put_rows_packed_exact(
+        n_mod, mode, _p(f1[0]), _p(f2[0]), _p(masks[0]), sec(f1), sec(f2), sec(masks), _p(slots), _p(ids), _p(runs), b, lb,
+        int(nb_max), *side, _p(codes), _p(ec), _p(vlen), _p(slot_ids), _p(live), cap, n_tiles, 128, int(l_ref), hidden, XML_F32,
+        _stream()), "xml_index_put_rows_packed_exact")
 
 
 def exact_certificate_dev(filter_scores, top_val, eq, ec, slack_base, slack_ec2, alpha, outside):
