@@ -1,6 +1,6 @@
 """Timing of an index that takes updates (index_update.MutableCorpusIndex).  GPU box only.
 
-usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains,exact,exactp] [--batch 200] [--reps 21]
+usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compact,chains,exact,exactp,exactc] [--batch 200] [--reps 21]
                                           [--pass-reps 5] [--queries 10000] [--videos 21793] [--suite-wall "..."]
                                           [--parent-lib path/to/another/libxmlhip.so]
                                           [--out profiles/index_update_timing.md; --legs exact: profiles/index_exact_timing.md]
@@ -37,6 +37,12 @@ usage: python tools/bench_index_update.py [--legs put,putp,e2e,c3,c3r,c3rp,compa
         512 queries' lists, certificate failures per pass, hbm_bytes(); with --parent-lib PATH (a libxmlhip.so built from the
         commit to compare with) an A/B of xml_index_put_rows_exact between the two libraries in this process.  Its report
         (--out, default profiles/index_exact_packed_run.md) is the source of the last sections of profiles/index_exact_timing.md
+  exactc  (not in the default set) long videos on the exact-rank index (exact_part_overlap=16, ops.F16S
+        model, filter_tiles=N) on the corpus of the chains leg at l_ref = 128 and l_ref = 100: the 10 000-query pass and the
+        50-query eager pass on the index with chains, on the same corpus truncated at l_ref on an index created without the
+        keyword, and on the truncated corpus on an index created WITH it (no long video: the price of the fold alone);
+        failing certificates and third-tier queries per pass, xml_cand_best_part alone on the pass's candidate lists,
+        hbm_bytes().  Its report: --out, default profiles/index_exact_parts_run.md
 
 Every figure is the median of repeated runs between HIP events after warm-up runs (min .. max); two versions are timed in the
 same process, alternating.  Bytes are counted from the shapes: per modality the batch's feat1 and feat2 rows read once, the
@@ -916,6 +922,98 @@ def exactp_leg(args, lines):
         exact_put_ab_leg(args, lines)
 
 
+def exactc_leg(args, lines):
+    """Long videos on the exact-rank index (create(..., exact_rank=True, filter_tiles=N, exact_part_overlap=16)), module
+    docstring."""
+    import bench
+    from tvretrieval_amd.ingest import plan_parts
+    _, _, _, hidden, dv, ds, dq, ctx_mode, _ = bench.WORKLOADS["c3r"]
+    nv, nq, ov = args.videos, args.queries, 16
+    be = bench.HipBackend(0)
+    dev = be.device
+    lines += ["## Long videos on the exact-rank index (create(..., exact_rank=True, filter_tiles=N, exact_part_overlap=%d), mode f16s)" % ov]
+    for l in (128, 100):
+        torch.manual_seed(0)
+        model = be.make_model(bench.model_config(hidden, dv, ds, dq, ctx_mode, l), ops.F16S)
+        full = full_clip_counts(nv)
+        cut = torch.clamp(full, max=l)
+        n_cut = [int(x) for x in cut.tolist()]
+        table = plan_parts(full.numpy(), l, ov)
+        n_parts = table.n_parts
+        counts = np.diff(table.group_start)
+        part_len = torch.from_numpy(table.part_len.astype(np.int64))
+        tiles = max(tiles_in_corpus_order([int(x) for x in table.part_len], bench.CHUNK)[0],
+                    tiles_in_corpus_order(n_cut, bench.CHUNK)[0])
+
+        def part_batches():
+            v0 = 0
+            while v0 < nv:
+                v1 = min(v0 + bench.CHUNK - 64, nv)
+                t = plan_parts(full[v0:v1].numpy(), l, ov)
+                r0 = int(table.group_start[v0])
+                pieces = list(bench.context_batches(r0, r0 + t.n_parts, l, dv, ds, True, True, dev, lens=part_len))
+                yield tuple(torch.cat([p[i] for p in pieces]) for i in range(4)), t
+                v0 = v1
+
+        cut_batches = lambda: bench.context_batches(0, nv, l, dv, ds, True, True, dev, lens=cut)      # noqa: E731
+        ekw = dict(l_ref=l, exact_rank=True, filter_tiles=tiles)
+        with torch.no_grad():
+            chained = MutableCorpusIndex.create(model, n_parts, exact_part_overlap=ov, **ekw)
+            for batch, t in part_batches():
+                chained.add(*batch, parts=t)
+            assert chained.n_live == n_parts and chained.n_videos_live == nv
+            forms = [("exact_part_overlap=%d, videos of up to %d clips in %d slots" % (ov, int(full.max()), n_parts), chained),
+                     ("no keyword, videos cut at %d clips" % l,
+                      MutableCorpusIndex.from_batches(model, cut_batches(), n_parts, n_clips=n_cut, **ekw)),
+                     ("exact_part_overlap=%d, videos cut at %d clips (no long video)" % (ov, l),
+                      MutableCorpusIndex.from_batches(model, cut_batches(), n_parts, n_clips=n_cut, exact_part_overlap=ov, **ekw))]
+            qf, qm = bench.synth_queries(nq, dq, dev)
+            kw = dict(n_valid_tokens=int(qm.sum().item()))
+            kw50 = dict(n_valid_tokens=int(qm[:50].sum().item()))
+            passes, small = [[], []], [[], []]
+            for rnd in (0, 1):
+                for _, index in forms:
+                    passes[rnd].append(timed(lambda: inf.vcmr_search(model, index, qf, qm, **kw), args.pass_reps, 2))
+                for _, index in forms:
+                    small[rnd].append(timed(lambda: inf.vcmr_search(model, index, qf[:50], qm[:50], **kw50), args.reps))
+            infos = [inf.vcmr_search(model, index, qf, qm, **kw)["exact"] for _, index in forms]
+            folds, lost = [], []
+            for (_, index), info in zip(forms, infos):
+                if index.chain_head is None:
+                    folds.append(None), lost.append(0)
+                    continue
+                cs, ci = info["cand_scores"], info["cand_indices"]
+                folds.append(timed(lambda: ops.cand_best_part(cs, ci, index.chain_head, index.chain_offset), args.reps))
+                lost.append(int(((info["cand_folded_indices"] < 0) & (ci >= 0)).sum()))
+            cut_lists = [inf.vcmr_search(model, index, qf[:512], qm[:512]) for _, index in forms[1:]]
+            same = all(bool(torch.equal(cut_lists[0][k], cut_lists[1][k]))
+                       for k in ("top_indices", "top_scores", "flat_indices", "flat_scores"))
+        m_c = int(infos[0]["n_candidates"])
+        lines += ["", "## l_ref = %d: %d videos with the TVR clip counts (last bin spread up to %d clips), %d of more than %d clips, %d "
+                  "parts, hidden %d, ops.F16S model, %d queries, filter_tiles = %d, capacity %d on all three"
+                  % (l, nv, int(full.max()), int((counts > 1).sum()), l, n_parts, hidden, nq, tiles, n_parts), "",
+                  "First 512 queries on the two indexes that hold the cut corpus (with and without the keyword): %s."
+                  % ("bitwise identical lists" if same else "lists NOT identical"), "",
+                  "| index | vcmr_search, %d queries | again | 50 queries, eager | again | failing certificates | third-tier queries | "
+                  "xml_cand_best_part alone, %d x %d | candidates folded away | hbm_bytes() |" % (nq, nq, m_c),
+                  "|---|---|---|---|---|---|---|---|---|---|"]
+        for i, (name, index) in enumerate(forms):
+            lines.append("| %s | %s | %s | %s | %s | %d | %d | %s | %d | %.3f GB |"
+                         % (name, fmt(passes[0][i]), fmt(passes[1][i]), fmt(small[0][i]), fmt(small[1][i]), int(infos[i]["n_fail"]),
+                            int(infos[i]["n_full_rows"]), "-" if folds[i] is None else fmt(folds[i], "us"), lost[i],
+                            index.hbm_bytes() / 1e9))
+        med = [(passes[0][i][0] + passes[1][i][0]) / 2 for i in range(3)]
+        lines += ["", "l_ref = %d, medians (mean of both rounds): %.2f ms with chains, %.2f ms cut without the keyword, %.2f ms cut "
+                  "with it (%+.2f %% for the long videos, %+.2f %% for the keyword alone); the fold moves %.1f MB in and out, %.1f us "
+                  "at the %.1f TB/s stream rate."
+                  % (l, med[0], med[1], med[2], (med[0] / med[1] - 1) * 100, (med[2] / med[1] - 1) * 100, 2 * nq * m_c * 8 / 1e6,
+                     2 * nq * m_c * 8 / HBM_STREAM * 1e6, HBM_STREAM / 1e12)]
+        for ln in lines[-12:]:
+            print(ln, flush=True)
+        del forms, chained, infos, cut_lists
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", default="put,putp,e2e,c3,c3r,c3rp")
@@ -930,7 +1028,8 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:      # the exact leg has a report of its own
-        args.out = os.path.join(ROOT, "profiles", {"exact": "index_exact_timing.md", "exactp": "index_exact_packed_run.md"}.get(
+        args.out = os.path.join(ROOT, "profiles", {"exact": "index_exact_timing.md", "exactp": "index_exact_packed_run.md",
+                                                   "exactc": "index_exact_parts_run.md"}.get(
             args.legs, "index_update_timing.md"))
     if not torch.cuda.is_available():
         sys.exit("bench_index_update.py measures on the GPU; none is visible")
@@ -959,6 +1058,8 @@ def main():
         exact_leg(args, lines)
     if "exactp" in legs:
         exactp_leg(args, lines)
+    if "exactc" in legs:
+        exactc_leg(args, lines)
     if args.suite_wall:
         lines += ["", "## GPU test wall time", "", args.suite_wall]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -282,6 +282,16 @@ SIGNATURES_EXACT_PACKED = {
                                         [c_void_p]),
 }
 
+# the companion header include/xmlhip_index_parts_exact.h (tests/test_index_parts_exact_capi.py checks): long videos as chains
+# of slots on an exact-rank index -- the fold on candidate lists
+SIGNATURES_PARTS_EXACT = {
+    "xml_cand_best_part_max_m": (c_int, []),
+    "xml_cand_best_part": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_int64, c_void_p]),
+    "xml_chain_spread_allow": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "xml_chain_members": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+}
+
 _lib = None
 
 
@@ -289,7 +299,7 @@ def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
             list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()) + \
-            list(SIGNATURES_EXACT_PACKED.items()):
+            list(SIGNATURES_EXACT_PACKED.items()) + list(SIGNATURES_PARTS_EXACT.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

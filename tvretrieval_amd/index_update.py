@@ -658,27 +658,38 @@ class MutableCorpusIndex(CorpusIndex):
     N tiles, with blocks / codes / mask_bits as in the packed form (ops.index_put_rows_packed_exact: the filter rows, codes
     and mask words of a video go to its run, everything else to its slot, one launch); re-score rows, feat2, err_rows and the
     bound are those of the plain exact-rank index bit for bit, mask and vlen follow the effective mask of the packed form.
-    n_clips=, compact() and auto_compact work as there; the filter then costs N tiles, not capacity / 2."""
+    n_clips=, compact() and auto_compact work as there; the filter then costs N tiles, not capacity / 2.
+    create(..., exact_rank=True, exact_part_overlap=O) (with or without filter_tiles=N): long videos on
+    an exact-rank index -- chains of slots with everything part_overlap=O gives (parts=, the ChainTable, chain_head /
+    chain_next / chain_offset, videos numbered by their head slot, added, replaced and removed whole).  Every part is an
+    ordinary exact-rank slot to the put kernels; a search folds the parts of a video on its re-scored candidate lists
+    (ops.cand_best_part) and returns the f32 path's lists of VIDEOS, each ranked by its best part."""
 
     def __init__(self, *a, **kw):
         raise TypeError("use MutableCorpusIndex.create(model, capacity) or MutableCorpusIndex.from_batches(...)")
 
     @classmethod
     def create(cls, model, capacity, l_ref=None, exact_filter=False, parts=None, video_offset=0, n_total=None, tiles=None,
-               auto_compact=False, part_overlap=None, max_parts=32, exact_rank=False, filter_tiles=None):
+               auto_compact=False, part_overlap=None, max_parts=32, exact_rank=False, filter_tiles=None,
+               exact_part_overlap=None):
         """An empty index (all slots free) for `capacity` videos of up to l_ref clips (default model.config.max_ctx_l).
         tiles=None: the plain K6 image, two slots per tile; tiles=N: the packed image over N tiles (class docstring).
         auto_compact (the packed form): an add / put / replace that finds no run although enough blocks are free runs
         compact() once and tries again.
         part_overlap=O (None: off, nothing changes): videos longer than l_ref clips are taken as CHAINS of slots (class
         docstring), cut by ingest.plan_parts(n_clips, l_ref, overlap=O); max_parts bounds the parts of one video.
-        exact_rank=True (an f32 or ops.F16S model; tiles=None, no part_overlap): exact-rank mode (class docstring) -- the
-        index holds the bf16 filter image, the f32-grade re-score rows and the running error bound, and searches return the
+        exact_rank=True (an f32 or ops.F16S model; tiles=None, no part_overlap -- exact_part_overlap instead): exact-rank mode
+        (class docstring) -- the index holds the bf16 filter image, the f32-grade re-score rows and the running error bound, and searches return the
         f32 path's lists.
         filter_tiles=N (with exact_rank=True only): the bf16 FILTER image alone is the packed image over N tiles -- re-score
         rows, feat2 and error norms stay per slot --; updates then take n_clips=, compact() and auto_compact work as in the
-        packed form (class docstring)."""
+        packed form (class docstring).
+        exact_part_overlap=O (with exact_rank=True only, with or without filter_tiles=N): what part_overlap=O is on an index
+        without exact-rank mode -- long videos as chains of slots, max_parts parts at the most; searches fold the parts of
+        a video on their re-scored candidate lists (class docstring)."""
         dt = getattr(model, "compute_dtype", torch.float32)
+        if exact_part_overlap is not None:
+            cls._check_exact_part_overlap(model, exact_part_overlap, exact_rank, tiles, part_overlap, l_ref)
         if filter_tiles is not None:
             cls._check_filter_tiles(filter_tiles, exact_rank, tiles, part_overlap)
         if exact_filter or (dt is hip_ops.F16S and not exact_rank):
@@ -695,7 +706,9 @@ class MutableCorpusIndex(CorpusIndex):
         l_ref = int(model.config.max_ctx_l if l_ref is None else l_ref)
         if l_ref <= 0:
             raise ValueError("MutableCorpusIndex: l_ref must be positive, got %d" % l_ref)
-        if part_overlap is None:
+        if exact_part_overlap is not None:       # (validated above, with exact_rank=True)
+            table = ChainTable(capacity, max_parts)
+        elif part_overlap is None:
             table = SlotTable(capacity)
         else:
             if isinstance(part_overlap, bool) or int(part_overlap) != part_overlap or not 0 <= int(part_overlap) < l_ref:
@@ -723,7 +736,10 @@ class MutableCorpusIndex(CorpusIndex):
         cap = table.capacity
         self = object.__new__(cls)
         if exact_rank:
-            return self._init_exact(model, table, mods, l_ref, lpad, h, dev, filter_tiles, auto_compact)
+            self._init_exact(model, table, mods, l_ref, lpad, h, dev, filter_tiles, auto_compact)
+            if exact_part_overlap is not None:
+                self._init_chains(int(exact_part_overlap), table, dev)
+            return self
         feat2 = {m: torch.zeros((cap, lpad, h), dtype=act, device=dev) for m in mods}
         mask = {m: torch.zeros((cap, lpad), dtype=torch.float32, device=dev) for m in mods}
         self.blocks, self.codes, self.auto_compact = blocks, None, bool(auto_compact) and blocks is not None
@@ -736,12 +752,18 @@ class MutableCorpusIndex(CorpusIndex):
         feat1n = {m: self._alloc_k6_image(m, (cap, lpad, h), act, dev, plan) for m in mods}
         CorpusIndex.__init__(self, mods, feat1n, feat2, mask, l_ref)
         self._init_slot_state(model, table, l_ref, dev)
-        if part_overlap is not None:         # every slot in the single state: an add of short videos never touches these
-            self.part_overlap, self.max_parts = int(part_overlap), table.max_parts
-            self.chain_head = torch.arange(cap, dtype=torch.int32, device=dev)
-            self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
-            self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
+        if part_overlap is not None:
+            self._init_chains(int(part_overlap), table, dev)
         return self
+
+    def _init_chains(self, overlap, table, dev):
+        """The chain tables of an index that holds long videos: every slot in the single state -- an add of short videos
+        never touches these."""
+        cap = table.capacity
+        self.part_overlap, self.max_parts = overlap, table.max_parts
+        self.chain_head = torch.arange(cap, dtype=torch.int32, device=dev)
+        self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
+        self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
 
     def _alloc_k6_image(self, m, shape, dtype, dev, plan=None):
         """The zero-filled K6 operand of modality m for (capacity, lpad, H) rows of `dtype`: the packed image of `plan` (a
@@ -759,6 +781,21 @@ class MutableCorpusIndex(CorpusIndex):
         return image
 
     @staticmethod
+    def _check_exact_part_overlap(model, overlap, exact_rank, tiles, part_overlap, l_ref):
+        """What create(..., exact_part_overlap=O) refuses about the keyword itself, before any device allocation."""
+        if not exact_rank:
+            raise ValueError("MutableCorpusIndex: exact_part_overlap=%r without exact_rank=True -- it is the chains of slots of "
+                             "exact-rank mode; an index without that mode takes long videos with part_overlap=O" % (overlap,))
+        if tiles is not None or part_overlap is not None:
+            raise ValueError("MutableCorpusIndex: exact_part_overlap=%r together with %s -- exact-rank mode (exact_rank=True) "
+                             "packs its filter image alone (filter_tiles=N, tiles=None), and its chains are asked for with "
+                             "exact_part_overlap= alone" % (overlap, "tiles=" if tiles is not None else "part_overlap="))
+        l_ref = int(model.config.max_ctx_l if l_ref is None else l_ref)
+        if isinstance(overlap, bool) or int(overlap) != overlap or not 0 <= int(overlap) < l_ref:
+            raise ValueError("MutableCorpusIndex: exact_part_overlap must be a number of clips in [0, l_ref = %d), got %r"
+                             % (l_ref, overlap))
+
+    @staticmethod
     def _check_filter_tiles(filter_tiles, exact_rank, tiles, part_overlap):
         """What create(..., filter_tiles=N) refuses about the keyword itself, before any device allocation."""
         if not exact_rank:
@@ -766,8 +803,9 @@ class MutableCorpusIndex(CorpusIndex):
                              "exact-rank mode; an index without that mode packs its K6 image with tiles=N" % (filter_tiles,))
         if tiles is not None or part_overlap is not None:
             raise ValueError("MutableCorpusIndex: filter_tiles=%r together with %s -- exact-rank mode (exact_rank=True) keeps "
-                             "re-score rows and error norms per slot and packs the filter image alone (tiles=None), and it "
-                             "holds no chains of slots" % (filter_tiles, "tiles=" if tiles is not None else "part_overlap="))
+                             "re-score rows and error norms per slot and packs the filter image alone (tiles=None), and its "
+                             "chains of slots are asked for with exact_part_overlap=O"
+                             % (filter_tiles, "tiles=" if tiles is not None else "part_overlap="))
         if isinstance(filter_tiles, bool) or int(filter_tiles) != filter_tiles or int(filter_tiles) <= 0:
             raise ValueError("MutableCorpusIndex: filter_tiles must be a positive integer number of 256-row tiles, got %r"
                              % (filter_tiles,))
@@ -782,7 +820,8 @@ class MutableCorpusIndex(CorpusIndex):
         if part_overlap is not None:
             raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) and part_overlap= exclude each other -- "
                              "exact-rank mode never forms the f32 (Nq, slots) score matrix that the best part of a video is "
-                             "taken from")
+                             "taken from; exact_part_overlap=O holds long videos as chains of slots there, folded on the "
+                             "re-scored candidate lists")
         if dt is not hip_ops.F16S and dt != torch.float32:
             raise ValueError("MutableCorpusIndex: exact-rank mode (exact_rank=True) needs f32 activations (XML(cfg, "
                              "compute_dtype=torch.float32 or ops.F16S)); got a %s model" % (dt,))
@@ -1174,7 +1213,8 @@ class MutableCorpusIndex(CorpusIndex):
             return [1] * b, [[0]] * b, None
         if self.chain_head is None:
             raise ValueError("%s: parts= on an index created without part_overlap= -- it holds videos of up to l_ref = %d clips "
-                             "only (MutableCorpusIndex.create(..., part_overlap=O))" % (what, self.l_ref))
+                             "only (MutableCorpusIndex.create(..., part_overlap=O); in exact-rank mode exact_part_overlap=O)"
+                             % (what, self.l_ref))
         for name in ("max_ctx_len", "overlap", "n_parts", "n_videos", "group_start", "part_offset", "part_len"):
             if not hasattr(table, name):
                 raise ValueError("%s: parts must be the ingest.PartTable of the batch (ingest.plan_parts), got %s"

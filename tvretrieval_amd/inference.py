@@ -32,7 +32,8 @@ records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and search
 best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
 index_clear_rows) and the searches and updates of one with chains of slots for long videos (index_set_chains,
 chain_best_allow, chain_best_rows) and the updates and searches of an exact-rank one (index_put_rows_exact,
-exact_certificate_dev, index_exact_bound; with the packed filter image index_put_rows_packed_exact) and the subset views of
+exact_certificate_dev, index_exact_bound; with the packed filter image index_put_rows_packed_exact; with chains of slots
+cand_best_part, chain_spread_allow, chain_members) and the subset views of
 video_subset (index_gather_blocks; HIP only, a search with subset= refuses any other backend) call further entries of
 tvretrieval_amd.ops; a backend without them serves every search that does not ask for those.
 """
@@ -592,7 +593,7 @@ def _check_parts_search(index, max_pred_l, external_top=None, pad_tail=False):
     if external_top is not None:
         raise ValueError("external_top on a parts index: a caller's lists name index rows and would bypass the fold that lets "
                          "only the best part of a video compete (rank the source videos with the index instead)")
-    if index.exact is not None:
+    if index.exact is not None and index.chain_head is None:     # (with chains the fold runs on the re-scored candidate lists)
         raise ValueError("a parts index cannot be an exact-rank index (exact_filter=True): no f32 score matrix exists to "
                          "take the best part of a video from")
     if int(max_pred_l) > overlap:
@@ -608,6 +609,21 @@ def _allow_rows(video_allow, rows):
     if video_allow is None or video_allow.shape[0] == 1:
         return video_allow
     return video_allow.index_select(0, rows).contiguous()
+
+
+def _exact_chain_allow(index, video_allow, ops):
+    """The allow words of an exact-rank search on an index with chains: (per-slot words for the selections that propose
+    candidate SLOTS, head-bit words for the fold of a full row).  video_allow is what stage_video_topk hands on: the live
+    words themselves -- they carry every bit of a chain, nothing is launched -- or a caller's mask ANDed with them, whose bits
+    number videos by their head slot: ops.chain_spread_allow gives every slot its head's bit."""
+    if video_allow is None or video_allow is index.live:
+        return index.live, index.live
+    return ops.chain_spread_allow(video_allow, index) & index.live, video_allow
+
+
+def _exact_chain_fold(index, ops, scores, ids):
+    """Candidate lists of SLOTS -> the same lists with every video reduced to its best candidate part (the others (-inf, -1))."""
+    return ops.cand_best_part(scores, ids, index.chain_head, index.chain_offset)
 
 
 def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None, subset=None):
@@ -635,12 +651,21 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
     video_allow (pack_video_allow's words, 1 or Nq rows): every selection over corpus columns -- the candidate K8, the second
     tier's select_ge_rows, the third tier's full row -- takes the mask; candidate slots a short row leaves empty are id -1,
     which the re-score turns into -inf.  The certificate is unchanged (conservative: a -inf at the candidates' end passes).
+    An index with chains of slots (index.chain_head): the lists are of VIDEOS, each ranked by its best
+    part, top_i the slots of those parts.  Candidates are proposed as slots under per-slot allow words (_exact_chain_allow);
+    every re-scored list is folded (ops.cand_best_part) before its top-k, so T_k is the k-th value over k DISTINCT videos and
+    the certificate holds unchanged; the third tier's full row is folded by ops.chain_best_allow under the head-bit words.
+    info then also holds cand_folded_indices / cand_folded_scores and q_rescore (the query operands of ops.q2c_rescore).
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
     ex = index.exact
     mods = index.modalities
     if k > min(ex.n_candidates, index.n_videos):
         raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
                          "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
+    chains = index.chain_head is not None
+    head_allow = video_allow
+    if chains:
+        video_allow, head_allow = _exact_chain_allow(index, video_allow, ops)
     masks = [index.mask[m] for m in mods]
     q_sr, q_hi, eq = [], [], []
     for m in mods:
@@ -660,11 +685,14 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
     cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
     rows_c = [ex.feat1n_f32[m] for m in mods]                    # SplitRows (Nv, lpad, H)
     cand_r = ops.q2c_rescore(q_sr, rows_c, masks, cand_i)
-    top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
+    fold_r, fold_i = _exact_chain_fold(index, ops, cand_r, cand_i) if chains else (cand_r, cand_i)
+    top_w, top_i = ops.topk_rows(fold_r, k, alpha=0.0, idx_in=fold_i)
     outside = index.n_videos > m_c
     fail, eps, thr_all, n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, hidden, alpha, outside, True)
     info = dict(fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s, cand_scores=cand_r,
                 n_candidates=m_c, n_fail_dev=n_fail, n_full_rows=0, overflow_dev=None)
+    if chains:
+        info.update(cand_folded_indices=fold_i, cand_folded_scores=fold_r, q_rescore=q_sr)
     if outside:
         r_cap = min(nq, ex.tier2_rows if ex.tier2_rows is not None else max(32, nq // 64))
         c_cap = min(int(ex.tier2_cap), index.n_videos)
@@ -679,6 +707,8 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
         q_sub = [sr[order] for sr in q_sr]
         q_sub = [ops.SplitRows(sr.data.contiguous(), sr.inv.contiguous()) for sr in q_sub]
         full = ops.q2c_rescore(q_sub, rows_c, masks, cand2)
+        if chains:
+            full, cand2 = _exact_chain_fold(index, ops, full, cand2)
         # slots of PASSING queries selected nothing: their rows are c_cap times -inf, and the top-k of an all-tied row with
         # payloads takes K8's one-block-minimum-per-element path (0.46 ms for 156 such rows -- more than the second tier's
         # re-score).  Their results are discarded below; a ramp of distinct values keeps them on the fast path.
@@ -702,7 +732,10 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
                     qs = [ops.SplitRows(sr.data.index_select(0, rows).contiguous(), sr.inv.index_select(0, rows).contiguous())
                           for sr in q_sr]
                     allv = ops.q2c_rescore(qs, rows_c, masks, every.repeat(rows.numel(), 1).contiguous())
-                    fw, fi = ops.topk_rows(allv, k, alpha=alpha, allow=_allow_rows(video_allow, rows))
+                    row_allow = _allow_rows(video_allow, rows)
+                    if chains:       # the fold of index_parts.hip on a full f32-grade row, under the head-bit words
+                        row_allow = ops.chain_best_allow(allv, index, _allow_rows(head_allow, rows))
+                    fw, fi = ops.topk_rows(allv, k, alpha=alpha, allow=row_allow)
                     top_w.index_copy_(0, rows, fw)
                     top_i.index_copy_(0, rows, fi)
                 info["n_full_rows"] = int(bad.numel())
@@ -721,12 +754,18 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None, s
          score reaches T_k - eps_q (nothing below that line can enter the top-k) is re-scored too -- or, when the scores are
          too close together for that (> EXACT_TIER2_CAP such videos), a full f32 K6 row (the f32 path itself).
     video_allow: as in stage_exact_topk_f16s -- the candidate K8, both select_ge_rows calls and the fallback's full row.
+    An index with chains of slots: as in stage_exact_topk_f16s -- every re-scored list is folded before its top-k, the
+    fallback's full f32 row by ops.chain_best_allow.
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
     ex = index.exact
     mods = index.modalities
     if k > min(ex.n_candidates, index.n_videos):
         raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
                          "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
+    chains = index.chain_head is not None
+    head_allow = video_allow
+    if chains:
+        video_allow, head_allow = _exact_chain_allow(index, video_allow, ops)
     masks = [index.mask[m] for m in mods]
     qn = [ops.l2norm_rows(qvec[m].contiguous()) for m in mods]
     if qn[0].dtype != torch.float32:
@@ -740,7 +779,8 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None, s
     cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
     f32rows = [ex.feat1n_f32[m] for m in mods]
     cand_r = ops.q2c_rescore(qn, f32rows, masks, cand_i)
-    top_w, top_i = ops.topk_rows(cand_r, k, alpha=0.0, idx_in=cand_i)
+    fold_r, fold_i = _exact_chain_fold(index, ops, cand_r, cand_i) if chains else (cand_r, cand_i)
+    top_w, top_i = ops.topk_rows(fold_r, k, alpha=0.0, idx_in=fold_i)
     fail, eps, thr_all, n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, qn[0].shape[1], alpha,
                                                     index.n_videos > m_c, False)
     nf = int(n_fail.item())        # (host sync: the launch shapes below depend on it)
@@ -758,15 +798,22 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None, s
         if cap <= EXACT_TIER2_CAP:
             cand2, _ = ops.select_ge_rows(frows, thr, cap, allow=_allow_rows(video_allow, rows))
             full = ops.q2c_rescore(qsub, f32rows, masks, cand2)                       # (-inf where a row has fewer candidates)
+            if chains:
+                full, cand2 = _exact_chain_fold(index, ops, full, cand2)
             fw, fi = ops.topk_rows(full, k, alpha=alpha, idx_in=cand2)
         else:   # scores so close together that the filter cannot separate them: the f32 K6 row itself
             n_full = nf
             full = ops.q2c_scores_fused(qsub, f32rows, masks)
-            fw, fi = ops.topk_rows(full, k, alpha=alpha, allow=_allow_rows(video_allow, rows))
+            row_allow = _allow_rows(video_allow, rows)
+            if chains:           # the fold of index_parts.hip on the full f32 row, under the head-bit words
+                row_allow = ops.chain_best_allow(full, index, _allow_rows(head_allow, rows))
+            fw, fi = ops.topk_rows(full, k, alpha=alpha, allow=row_allow)
         top_w.index_copy_(0, rows, fw)
         top_i.index_copy_(0, rows, fi)
     info = dict(n_fail=nf, n_full_rows=n_full, fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s,
                 cand_scores=cand_r, n_candidates=m_c)
+    if chains:
+        info.update(cand_folded_indices=fold_i, cand_folded_scores=fold_r, q_rescore=qn)
     return top_w, top_i, info
 
 
@@ -891,7 +938,9 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
     An index that takes updates (index.live): the allow words are ANDed with the live words -- one small (rows, words) int32
     pass, part of a captured search -- so the lists are those of the corpus of the live videos, in slot numbering.
     One with chains (index.chain_head): K6, then ops.chain_best_allow under those words (each video's best part; a caller's
-    video_allow bit for a video is the bit of its HEAD slot), then K8 under the fold's bits -- top_i are slots, one per video."""
+    video_allow bit for a video is the bit of its HEAD slot), then K8 under the fold's bits -- top_i are slots, one per video.
+    One with chains in exact-rank mode (create(..., exact_rank=True, exact_part_overlap=O)): the exact-rank chain with the fold
+    on its candidate lists (stage_exact_topk_f16s) -- the same lists of videos, f32-grade; q2c is None."""
     exact = None
     if subset is not None:
         _check_subset(subset, index, ops, external_top)
@@ -904,6 +953,12 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
         video_allow = _subset_allow(subset, video_allow)
     if index.live is not None and external_top is None:
         video_allow = index.live if video_allow is None else video_allow[:, :index.live.shape[1]] & index.live
+    if index.chain_head is not None and index.exact is not None:
+        # chains on an exact-rank index: no f32 matrix to fold -- the exact-rank chain folds its candidate lists itself
+        _check_parts_search(index, 0, external_top)
+        k = min(max_vcmr_video, index.n_videos)
+        top_w, top_i, exact = stage_exact_topk(index, qvec, k, q2c_alpha, ops, bool(defer_exact_check), video_allow)
+        return None, top_w, top_i, exact
     if index.chain_head is not None:
         _check_parts_search(index, 0, external_top)
         q2c = stage_q2c(index, qvec, ops)
@@ -994,7 +1049,9 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     index rows -- the fold walks the chain tables (ops.chain_best_allow), top_videos names each listed slot's HEAD slot, which
     is also the bit a caller's video_allow carries for the video; svmr_video names a video by any of its slots; records carry
     the video's id (slot_ids) and whole-video times (chain_offset).  Refused alike: external_top, pad_tail=True, max_pred_l >
-    part_overlap."""
+    part_overlap.  In exact-rank mode (create(..., exact_rank=True, exact_part_overlap=O)) all of this holds with the f32
+    path's lists: the fold runs on the re-scored candidate lists (stage_exact_topk_f16s), out["q2c"] is None, and svmr_video
+    re-scores the slots of the named video (ops.chain_members) to find its best part."""
     if subset is not None:
         _check_subset(subset, index, ops, external_top, pad_tail)
     if video_allow is not None and pad_tail:
@@ -1041,7 +1098,16 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         if parts is not None:       # a SOURCE video per query: its best part for that query stands for it (-1: unknown id)
             pv = ops.best_part_rows(q2c, parts, pv)
             out["svmr_rows"] = pv
-        if chains:                  # any slot of a video: the slot of its best part for that query (-1: outside the index)
+        if chains and index.exact is not None:
+            # no q2c matrix: the slots of each video, re-scored with the query operands the exact-rank chain made, folded to
+            # the best part.  The fold leaves one slot per row (the head for a chain of nothing but -inf, where a top-1 by
+            # value would find an empty list): the largest id is that slot, -1 for a slot outside the index.
+            members = ops.chain_members(index, pv)
+            sc = ops.q2c_rescore(exact["q_rescore"], [index.exact.feat1n_f32[m] for m in index.modalities],
+                                 [index.mask[m] for m in index.modalities], members)
+            pv = _exact_chain_fold(index, ops, sc, members)[1].amax(1).to(torch.int32)
+            out["svmr_rows"] = pv
+        elif chains:                # any slot of a video: the slot of its best part for that query (-1: outside the index)
             pv = ops.chain_best_rows(q2c, index, pv)
             out["svmr_rows"] = pv
         pv = pv.reshape(-1, 1)

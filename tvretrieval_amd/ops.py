@@ -1671,6 +1671,76 @@ def chain_best_rows(scores, chains, video):
     return out
 
 
+# ---- chains on an exact-rank index (include/xmlhip_index_parts_exact.h; create(..., exact_rank=True, exact_part_overlap=O)) ----
+def cand_best_part_max_m():
+    """The widest candidate list cand_best_part folds (xml_cand_best_part_max_m)."""
+    return int(_lib.load().xml_cand_best_part_max_m())
+
+
+def cand_best_part(scores, ids, group, order, out=None):
+    """The fold of a chain index on a candidate list (xml_cand_best_part).  scores (rows, m) f32 and ids (rows, m) int32
+    (slots; an id outside [0, n) is an empty candidate), contiguous; group / order (n,) int32
+    per-slot tables (chain_head / chain_offset).  Candidates of one group (in-range ids with equal group values; a group
+    value outside [0, n) is a group of its own) are reduced to the best one -- the greatest isnan(s) ? -inf : s, ties to the
+    smallest order, then to the lower position --, which keeps its score bits and id; the others become (-inf, -1).
+    out=None -> new (scores, ids); out=(scores, ids) writes there, the inputs themselves fold in place."""
+    _req(scores, "scores", torch.float32); _req(ids, "ids", torch.int32)
+    (g, o), n = _chain_tables(types.SimpleNamespace(group=group, order=order), ("group", "order"), "cand_best_part")
+    if scores.dim() != 2 or ids.shape != scores.shape or scores.shape[1] < 1:
+        raise ValueError("cand_best_part: scores and ids must be (rows, m >= 1) matrices of one shape, got %s and %s"
+                         % (tuple(scores.shape), tuple(ids.shape)))
+    rows, m = scores.shape
+    if m > cand_best_part_max_m():
+        raise ValueError("cand_best_part: a list of %d candidates; xml_cand_best_part folds at most %d" % (m, cand_best_part_max_m()))
+    if scores.device != g.device or ids.device != g.device:
+        raise ValueError("cand_best_part: the lists are on %s / %s, the tables on %s" % (scores.device, ids.device, g.device))
+    if out is None:
+        out = (torch.empty((rows, m), dtype=torch.float32, device=scores.device),
+               torch.empty((rows, m), dtype=torch.int32, device=scores.device))
+    out_s, out_i = out
+    _req(out_s, "out scores", torch.float32); _req(out_i, "out ids", torch.int32)
+    if out_s.shape != scores.shape or out_i.shape != scores.shape:
+        raise ValueError("cand_best_part: out must be a (scores, ids) pair of shape %s" % (tuple(scores.shape),))
+    if rows:          # (contiguous lists: both row strides are m)
+        check(_lib.load().xml_cand_best_part(_p(scores), _p(ids), m, rows, m, _p(g), _p(o), n, _p(out_s), _p(out_i), m,
+                                             _stream()), "xml_cand_best_part")
+    return out_s, out_i
+
+
+def chain_spread_allow(video_allow, chains):
+    """A caller's head-bit mask made per-slot (xml_chain_spread_allow).  video_allow (R, >= ceil(capacity / 32)) int32 words
+    in which a video is numbered by its HEAD slot; chains: the index (chain_head) -> (R, ceil(capacity / 32)) int32 words, bit
+    s = the allow bit of chain_head[s] (0 for a head outside the index; padding bits 0)."""
+    (head,), cap = _chain_tables(chains, ("chain_head",), "chain_spread_allow")
+    if not torch.is_tensor(video_allow) or video_allow.dim() != 2:
+        raise ValueError("chain_spread_allow: video_allow must be a 2-D int32 tensor of bit words (inference.pack_video_allow)")
+    rows = video_allow.shape[0]
+    video_allow, _ = _allow_args(video_allow, 0, rows, cap, head.device, "chain_spread_allow")
+    out = torch.empty((rows, (cap + 31) // 32), dtype=torch.int32, device=head.device)
+    if rows:
+        check(_lib.load().xml_chain_spread_allow(_p(video_allow), video_allow.stride(0), rows, rows, cap, _p(head), _p(out),
+                                                 out.stride(0), _stream()), "xml_chain_spread_allow")
+    return out
+
+
+def chain_members(chains, video):
+    """video (rows,) int32: ANY slot of one video per row -> (rows, max_parts) int32, the slots of that video's chain in rising
+    offset order, -1 behind its end (all -1 for a slot outside the index)  (xml_chain_members)."""
+    (head, nxt), cap = _chain_tables(chains, ("chain_head", "chain_next"), "chain_members")
+    if not torch.is_tensor(video) or video.dtype != torch.int32 or video.dim() != 1:
+        raise ValueError("chain_members: video must be a (rows,) int32 tensor of slots, got %s %s"
+                         % (getattr(video, "dtype", type(video).__name__), tuple(getattr(video, "shape", ()))))
+    if video.device != head.device:
+        raise ValueError("chain_members: video is on %s, the chain tables on %s" % (video.device, head.device))
+    video = video.contiguous()
+    rows, mp = video.numel(), int(chains.max_parts)
+    out = torch.empty((rows, mp), dtype=torch.int32, device=head.device)
+    if rows:
+        check(_lib.load().xml_chain_members(_p(video), rows, cap, _p(head), _p(nxt), mp, _p(out), out.stride(0), _stream()),
+              "xml_chain_members")
+    return out
+
+
 # ---- exact-rank mode on an updatable index (include/xmlhip_index_exact.h; MutableCorpusIndex.create(..., exact_rank=True)) ------
 EXACT_F32, EXACT_F16S = 0, 1          # XML_EXACT_F32 / XML_EXACT_F16S
 
