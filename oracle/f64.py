@@ -18,6 +18,7 @@ stage to the forward value AND / OR to the gradient crossing the same point, as 
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -212,11 +213,52 @@ def train_qkv(x, ws, bs, stage=ident, residual=None):
     return y if residual is None else (y, xs)
 
 
-def train_attention(q, k, v, q_mask, k_mask, n_heads, stage=ident):
-    """AttentionCoreFn / AttentionKvFn / AttentionQkvFn, p_drop = 0, fused (attention_train.hip) and unfused chain alike.
+def drop_keep(count, p, seed):
+    """Host model of xml_dropout's mask: keep[i] for the elements i = 0 .. count - 1 of a tensor (numpy bool).  Restates
+    common.h: xml_seed_words (s0 = low seed word, s1 = high word * 0x27D4EB2F + 0x165667B1) and drop_hash, in uint64 arithmetic
+    cut to 32 bits after every step; element i is kept when hash(i) >= uint32(double(float32 p) * 2^32).  No base seed
+    (train_ops.SEED_BASE is None outside a captured step)."""
+    m32 = np.uint64(0xFFFFFFFF)
+    seed = int(seed) % (1 << 64)
+    s0 = np.uint64(seed & 0xFFFFFFFF)
+    s1 = np.uint64(((seed >> 32) * 0x27D4EB2F + 0x165667B1) & 0xFFFFFFFF)
+    thresh = np.uint64(int(float(np.float32(p)) * 4294967296.0) & 0xFFFFFFFF)
+    i = np.arange(count, dtype=np.uint64)
+    h = ((i & m32) * np.uint64(0x9E3779B1) + s0) & m32
+    h ^= ((i >> np.uint64(32)) * np.uint64(0x85EBCA77)) & m32
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & m32
+    h ^= h >> np.uint64(13)
+    h = (h + s1) & m32
+    h = (h * np.uint64(0xC2B2AE35)) & m32
+    h ^= h >> np.uint64(16)
+    return h >= thresh
+
+
+def drop_scale(p):
+    """the factor of a kept element, 1 / (1 - p) in float32 arithmetic as xml_dropout and attention_train.hip compute it."""
+    return float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
+def attention_drop(n, heads, lq, lk, p, seed):
+    """The factor keep / (1 - p) of every probability, (N, heads, Lq, Lk) float64: the mask of the (N * heads, lq8, lk8) tensor
+    of the unfused chain (lengths padded to multiples of 8), which the fused kernels index the same way."""
+    lq8, lk8 = (lq + 7) // 8 * 8, (lk + 7) // 8 * 8
+    keep = torch.from_numpy(drop_keep(n * heads * lq8 * lk8, p, seed)).view(n, heads, lq8, lk8)[:, :, :lq, :lk]
+    return keep.double() * drop_scale(p)
+
+
+def train_attention(q, k, v, q_mask, k_mask, n_heads, stage=ident, drop=None):
+    """AttentionCoreFn / AttentionKvFn / AttentionQkvFn, fused (attention_train.hip) and -- for p_drop = 0 -- unfused chain alike.
     bf16 stores: P where it feeds P V and P^T dO (LDS patch / attn_softmax's P, P^T; the softmax backward itself uses the f32
     P), the context O, dS = P (dP - delta) / sqrt(dh) (LDS / attn_softmax's dS, dS^T: the gradient of the RAW Q K^T), and
-    dQ, dK, dV.  S and dP stay f32 (accumulators / out_f32 GEMMs)."""
+    dQ, dK, dV.  S and dP stay f32 (accumulators / out_f32 GEMMs).
+    drop: None, or the (N, heads, Lq, Lk) factors keep / (1 - p) (`attention_drop`) of the FUSED kernels' dropout: the f32
+    probabilities are multiplied in registers and Pd = rne(P o M / (1 - p)) is what is stored -- forward: at_tile_times_rows' patch
+    store in front of Pd V; backward: the Pd^T store into R2 in step 4, in front of dV = Pd^T dO.  dPd = dO V^T comes out of the
+    accumulators and dP = dPd o M / (1 - p), delta and the softmax backward (on the f32 P, not on Pd) stay f32 (step 2); dS is
+    rounded where it is without dropout (patch in step 3, dS^T in step 4).  The unfused chain rounds P to bf16 BEFORE its
+    dropout launch and the product again: another staging, not modelled here."""
     n, lq, hsz = q.shape
     lk = k.shape[1]
     dh = hsz // n_heads
@@ -225,6 +267,8 @@ def train_attention(q, k, v, q_mask, k_mask, n_heads, stage=ident):
     sp = lambda t, l: staged(t, stage, fwd=False).view(n, l, n_heads, dh).permute(0, 2, 1, 3)      # noqa: E731
     raw = staged(torch.matmul(sp(q, lq), sp(k, lk).transpose(-1, -2)), stage, fwd=False)
     probs = torch.softmax(raw / math.sqrt(dh) + (1 - att.unsqueeze(1)) * O.ATT_NEG, dim=-1)
+    if drop is not None:
+        probs = probs * drop.to(probs.dtype)
     ctx = torch.matmul(staged(probs, stage, bwd=False), sp(v, lk))
     return staged(ctx.permute(0, 2, 1, 3).contiguous().view(n, lq, hsz), stage, bwd=False)
 

@@ -11,7 +11,11 @@ gradient: what comes back is what the node returns, before autograd drops or cas
 * bf16 tensors one store away from exact operands: a correct round-to-nearest of a value within the f32 allowance of W
   (numerics_regimes.check_bf16_rounding, >= 25 % of the elements decided);
 * bf16 (and VideoLevelScoresFn's f32 scores) behind more than one bf16 boundary: max|G - W| <= C_TRAIN_CHAIN max|S - W| and
-  rms(G - W) <= C_TRAIN_CHAIN / 2 rms(S - W).
+  rms(G - W) <= C_TRAIN_CHAIN / 2 rms(S - W);
+* the attention nodes in addition block by block -- one (sequence, head, 16-row tile) of O, dQ, dK, dV, what one wave of
+  attention_train.hip computes as one tile: the same two bounds against the block's OWN staged error, and exactly W where the
+  staged reference is exactly W (train_bf16_cases.check_blocks; tests/test_numerics_reference.py runs the same check on an
+  f32-arithmetic model of a correct kernel).
 Every case prints `NUMERICS node.tensor case storage: kernel_err ref_err ratio` lines (pytest -s); the table, the derivation of
 C_TRAIN_CHAIN and the run time are in profiles/numerics_margins.md ("Training ops, bf16")."""
 import numpy as np
@@ -30,7 +34,9 @@ F32_SUM = 2e-5          # f32 sums of exact products: the figure of gemm_tn / th
 C_ALLOW = 2             # f32 allowance under a bf16 store: C_GEMM / C_ROWWISE of tests/test_gpu_numerics.py
 # worst measured ratio over the chain cases of this module: 1.001 in max (VideoLevelScoresFn scores 7x19x128 m2: 7.09e-4 against
 # the staged reference's 7.08e-4), 1.00 in rms -> doubled once = 2.003 -> rounded up to a power of two = 4, the inference
-# chains' figure (table: profiles/numerics_margins.md, "Training ops, bf16")
+# chains' figure (table: profiles/numerics_margins.md, "Training ops, bf16").  The block-wise check of the attention cases uses
+# the same constant, derived from the reference side alone: the f32-arithmetic model of a correct kernel has a worst BLOCK
+# ratio of 1.07 in max and 1.007 in rms (tests/test_numerics_reference.py) -> doubled once, rounded up to a power of two = 4
 C_TRAIN_CHAIN = 4
 
 
@@ -201,23 +207,32 @@ ATTENTION = TC.attention_cases()
 
 @pytest.mark.parametrize("case", ATTENTION, ids=TC.ids(ATTENTION))
 def test_attention_fns_bf16(case):
-    """p_drop = 0 (the dropout cases: tests/test_gpu_train.py).  Fused and unfused chain share ONE staged reference: both keep
-    S and dP in f32 and round P, O, dS, dQ, dK, dV to bf16."""
+    """Fused and unfused chain share ONE staged reference at p_drop = 0: both keep S and dP in f32 and round P, O, dS, dQ, dK,
+    dV to bf16.  Dropout on the probabilities (fused only: the chain rounds P before its dropout launch -- another staging,
+    compared in tests/test_gpu_train.py) has its references from the host model of the mask (oracle/f64.py drop_keep, pinned to
+    the kernel by test_dropout_mask_equals_the_host_model).  A shape without a fused instantiation (`supported` false in the case
+    table) runs the chain because the library says so, not because the test switched the fused kernels off."""
     from tvretrieval_amd import train_ops as TO
     from tvretrieval_amd.autograd import AttentionCoreFn, AttentionKvFn, AttentionQkvFn
     cfg = case.cfg
     qm = None if cfg["q_mask"] is None else cfg["q_mask"].to(DEV)
     km, heads = cfg["k_mask"].to(DEV), cfg["heads"]
-    lq, lk = case.gouts[0].shape[1], km.shape[1]
-    assert TO.attention_train_supported(lq, lk, case.gouts[0].shape[2], heads, BF16)
+    lq, lk, hidden = case.gouts[0].shape[1], km.shape[1], case.gouts[0].shape[2]
+    assert TO.attention_train_supported(lq, lk, hidden, heads, BF16) == cfg["supported"]
+    assert cfg["supported"] or not cfg["fused"]
+    drop = (cfg["p_drop"], cfg["seed"])
+    if cfg["drop"] is not None:          # the mask drops something in every (sequence, head), among the valid pairs too
+        assert cfg["fused"] and TO.SEED_BASE is None
+        valid = cfg["k_mask"][:, None, None, :] * (1 if cfg["q_mask"] is None else cfg["q_mask"][:, None, :, None])
+        assert bool(((cfg["drop"] == 0) & (valid > 0)).flatten(2).any(-1).all())
     try:
-        TO.DISABLE_FUSED_ATTENTION = not cfg["fused"]
+        TO.DISABLE_FUSED_ATTENTION = cfg["supported"] and not cfg["fused"]
         if cfg["form"] == "core":
-            outs, grads = run_node(case, lambda q, k, v: ((AttentionCoreFn.apply(q, k, v, qm, km, heads),), (0, 1, 2)))
+            outs, grads = run_node(case, lambda q, k, v: ((AttentionCoreFn.apply(q, k, v, qm, km, heads, *drop),), (0, 1, 2)))
         elif cfg["form"] == "kv":
-            outs, grads = run_node(case, lambda q, kv: ((AttentionKvFn.apply(q, kv, qm, km, heads),), (0, 1)))
+            outs, grads = run_node(case, lambda q, kv: ((AttentionKvFn.apply(q, kv, qm, km, heads, *drop),), (0, 1)))
         else:
-            outs, grads = run_node(case, lambda t: ((AttentionQkvFn.apply(t, km, heads),), (0,)))
+            outs, grads = run_node(case, lambda t: ((AttentionQkvFn.apply(t, km, heads, *drop),), (0,)))
     finally:
         TO.DISABLE_FUSED_ATTENTION = False
     keep = None if cfg["q_mask"] is None else (cfg["q_mask"] > 0)[:, :, None]
@@ -225,6 +240,30 @@ def test_attention_fns_bf16(case):
     # keys that are masked out get exactly no gradient (covered by "G == 0 wherever W == 0"; make sure W has such rows)
     wk = case.refs()["W"][1][-1]
     assert bool((wk.view(wk.shape[0], wk.shape[1], -1)[cfg["k_mask"] == 0][..., -8:] == 0).all()) and bool((cfg["k_mask"] == 0).any())
+    # block by block: one (sequence, head, 16-row tile) against its own staged error
+    (Wo, Wg), (So, Sg) = case.refs()["W"], case.refs()["S"]
+    for (name, g, rows), w, s in zip(TC.attention_tensors(case, outs, grads), Wo + Wg, So + Sg):
+        TC.check_blocks("%s.%s" % (case.op, name), case.name, g, w, s, hidden // heads, C_TRAIN_CHAIN, rows)
+
+
+@pytest.mark.parametrize("p", [0.1, 0.2])
+@pytest.mark.parametrize("seed", [4242, (0x9E3779B9 << 32) + 7])
+def test_dropout_mask_equals_the_host_model(p, seed):
+    """oracle/f64.py drop_keep / drop_scale == xml_dropout bit for bit: on the (N * heads, L8, L8) tensor of the unfused
+    attention chain with L8 != L (the layout the fused kernels index, attention_train.hip) and on a flat tensor of 2^16 + 3
+    elements.  The second seed has a high word: both seed words of xml_seed_words matter."""
+    from oracle import f64
+    from tvretrieval_amd import train_ops as TO
+    assert TO.SEED_BASE is None
+    for shape in ((2 * 4, 24, 40), (2 ** 16 + 3,)):           # L = 21 / 33 -> L8 = 24 / 40
+        got = TO.dropout(torch.ones(shape, device=DEV), p, seed).cpu()
+        keep = torch.from_numpy(f64.drop_keep(got.numel(), p, seed)).view(shape)
+        assert torch.equal(got != 0, keep), "%d of %d elements differ" % (int(((got != 0) != keep).sum()), got.numel())
+        assert torch.equal(got.double(), keep.double() * f64.drop_scale(p))
+        assert 0 < int((~keep).sum()) < keep.numel()
+    n, heads, lq, lk = 2, 4, 21, 33
+    want = TO.dropout(torch.ones(n * heads, 24, 40, device=DEV), p, seed).cpu().view(n, heads, 24, 40)[:, :, :lq, :lk]
+    assert torch.equal(f64.attention_drop(n, heads, lq, lk, p, seed), want.double())
 
 
 # ---- ModularPoolFn ----------------------------------------------------------------------------------------------------------

@@ -4,6 +4,8 @@ without a GPU.
 * each generator achieves the figure it promises;
 * the float32 reference is finite in every regime and passes the new checks itself (as f32, and rounded to bf16 by torch),
   the 1 % cap on rounding-boundary elements included;
+* the host model of the dropout mask (oracle/f64.py drop_keep) against a scalar restatement; the attention case table
+  against the library's list of fused head sizes; the block-wise chain check on an f32-arithmetic model of a correct kernel;
 * the staged float64 AUTOGRAD references of the training nodes (oracle/f64.py, tests/train_bf16_cases.py): identity stage ==
   plain float64 autograd bit for bit, staged != exact, one bf16 store stays within half a bf16 ulp of W (<= 2^-8 |W|) plus one f32 rounding;
 * sensitivity: deliberately wrong stand-ins are rejected by the check meant for them while the existing `close(...)`
@@ -249,7 +251,8 @@ def _plain(case, ls):
         km, qm = cfg["k_mask"].double(), cfg["q_mask"]
         att = km.unsqueeze(1) if qm is None else torch.einsum("bm,bn->bmn", qm.double(), km)
         s = torch.matmul(sp(q, h), sp(k, h).transpose(-1, -2)) / math.sqrt(h // cfg["heads"]) + (1 - att.unsqueeze(1)) * O.ATT_NEG
-        o = torch.matmul(torch.softmax(s, dim=-1), sp(v, h))
+        p = torch.softmax(s, dim=-1)
+        o = torch.matmul(p if cfg["drop"] is None else p * cfg["drop"], sp(v, h))
         return o.permute(0, 2, 1, 3).contiguous().view(q.shape)
     if case.op == "ModularPoolFn":
         enc, wm = ls
@@ -265,7 +268,10 @@ def _plain(case, ls):
     return torch.einsum("bd,bld->bl", *ls)
 
 
-@pytest.mark.parametrize("case", TC.all_cases(), ids=repr)
+ALL_CASES = TC.all_cases()           # references are computed once per case object: the attention tests below share them
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=repr)
 def test_training_node_references(case):
     refs = case.refs()
     (Wo, Wg), (So, Sg), (Ro, Rg) = refs["W"], refs["S"], refs["R"]
@@ -325,3 +331,125 @@ def test_staged_is_straight_through():
     w = torch.randn(8, 8, requires_grad=True)
     f64.operand(w).sum().backward()
     assert torch.equal(f64.operand(w).detach(), w.detach().to(BF16).float()) and torch.equal(w.grad, torch.ones(8, 8))
+
+
+# ---- attention cases: dropout mask model, coverage of the case table, block-wise check ------------------------------------------
+def _drop_hash_scalar(i, seed):
+    """common.h xml_seed_words + drop_hash on Python integers."""
+    m = 0xFFFFFFFF
+    s0, s1 = seed & m, ((seed >> 32) * 0x27D4EB2F + 0x165667B1) & m
+    h = ((i & m) * 0x9E3779B1 + s0) & m
+    h ^= ((i >> 32) * 0x85EBCA77) & m
+    h ^= h >> 16
+    h = h * 0x85EBCA6B & m
+    h ^= h >> 13
+    h = (h + s1) & m
+    h = h * 0xC2B2AE35 & m
+    return h ^ (h >> 16)
+
+
+def test_dropout_mask_host_model_is_self_consistent():
+    """drop_keep (vectorised, uint64 cut to 32 bits) == the scalar form on Python integers; a prefix of a longer mask is the
+    shorter mask (counter based); both seed words matter; the kept share is 1 - p; the threshold and scale are float32 p's.
+    (Equality with xml_dropout itself: tests/test_gpu_train_bf16.py::test_dropout_mask_equals_the_host_model.)"""
+    import numpy as np
+    for p in (0.1, 0.2):
+        thresh = int(float(np.float32(p)) * 4294967296.0)
+        assert thresh != int(p * 4294967296.0)                       # float32(p) is not p: the kernels get a float
+        for seed in (4242, (0x9E3779B9 << 32) + 7, (1 << 32) + 4242):
+            keep = f64.drop_keep(5000, p, seed)
+            assert keep.dtype == np.bool_ and keep.shape == (5000,)
+            assert [bool(k) for k in keep[:600]] == [_drop_hash_scalar(i, seed) >= thresh for i in range(600)]
+            assert np.array_equal(f64.drop_keep(777, p, seed), keep[:777])
+            assert abs(float(keep.mean()) - (1 - p)) < 4 * math.sqrt(p * (1 - p) / 5000)
+        assert not np.array_equal(f64.drop_keep(5000, p, 4242), f64.drop_keep(5000, p, (1 << 32) + 4242))
+        assert not np.array_equal(f64.drop_keep(5000, p, 4242), f64.drop_keep(5000, p, 4243))
+        assert f64.drop_scale(p) == float(np.float32(1) / (np.float32(1) - np.float32(p)))
+    assert f64.drop_scale(0.2) == 1.25 and f64.drop_scale(0.1) != 1 / (1 - 0.1)      # float32 arithmetic, as the kernels'
+    # the attention layout: rows and columns padded to multiples of 8, the valid corner cut out
+    d = f64.attention_drop(2, 4, 13, 21, 0.2, 99)
+    full = torch.from_numpy(f64.drop_keep(8 * 16 * 24, 0.2, 99)).view(2, 4, 16, 24)
+    assert d.shape == (2, 4, 13, 21) and torch.equal(d != 0, full[:, :, :13, :21])
+    assert set(d.unique().tolist()) == {0.0, f64.drop_scale(0.2)}
+
+
+ATTENTION = [c for c in ALL_CASES if c.op.startswith("Attention")]
+
+
+def test_attention_case_table_reaches_every_fused_instantiation():
+    """The set of head sizes H / heads over the fused attention cases IS the library's list XML_ATTN_HEAD_SIZES (a head size
+    added to the dispatch list without a training case fails here), each in every entry form its shape admits and with dropout
+    somewhere; head counts 1, 2, 4, 8, 24; every listed length on some side; every case has a masked key, none a sequence
+    without a valid key; `supported` is the library's answer."""
+    import kernel_forms as DM
+    assert len({c.name for c in ATTENTION}) == len(ATTENTION)
+    dh_of = lambda c: c.gouts[0].shape[2] // c.cfg["heads"]      # noqa: E731
+    fused = [c for c in ATTENTION if c.cfg["fused"]]
+    assert {dh_of(c) for c in fused} == set(DM.ATTN_DH)
+    for dh in DM.ATTN_DH:
+        forms = {(c.cfg["form"], c.cfg["q_mask"] is not None) for c in fused if dh_of(c) == dh}
+        assert ("core", False) in forms or ("core", True) in forms, dh
+        assert any(f == "qkv" for f, _ in forms) or any(f == "kv" for f, _ in forms), dh
+        # a wave's second row tile (rows >= 64) in use on the query and on the key side
+        assert any(c.gouts[0].shape[1] > 64 and c.cfg["k_mask"].shape[1] > 64 for c in fused if dh_of(c) == dh), dh
+    assert {c.cfg["form"] for c in fused} == {"core", "kv", "qkv"}
+    assert {c.cfg["heads"] for c in fused} == {1, 2, 4, 8, 24}
+    lengths = {l for c in fused for l in (c.gouts[0].shape[1], c.cfg["k_mask"].shape[1])}
+    assert {1, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 96, 97, 127, 128} <= lengths
+    for c in ATTENTION:
+        lq, lk, h = c.gouts[0].shape[1], c.cfg["k_mask"].shape[1], c.gouts[0].shape[2]
+        assert DM.attn_train_ok(lq, lk, h, c.cfg["heads"]) == c.cfg["supported"], c
+        assert c.cfg["supported"] or not c.cfg["fused"]
+        km = c.cfg["k_mask"]
+        assert bool((km == 0).any()) and bool((km.sum(1) > 0).all()) and bool((km[0] == 1).all())
+        if c.cfg["drop"] is not None:
+            qm = 1 if c.cfg["q_mask"] is None else c.cfg["q_mask"][:, None, :, None]
+            assert bool(((c.cfg["drop"] == 0) & (km[:, None, None, :] * qm > 0)).flatten(2).any(-1).all()), c
+    chain = [c for c in ATTENTION if not c.cfg["fused"]]
+    assert any(not c.cfg["supported"] for c in chain) and {dh_of(c) for c in chain} - set(DM.ATTN_DH) == {48}
+    drops = [c for c in ATTENTION if c.cfg["drop"] is not None]
+    assert len(drops) == 7 and all(c.cfg["p_drop"] == 0.2 for c in drops) and len({c.cfg["seed"] for c in drops}) == 7
+    # L8 != L on both sides in some dropout case (an index formed from lq / lk instead of lq8 / lk8 shows up)
+    assert any(c.gouts[0].shape[1] % 8 and c.cfg["k_mask"].shape[1] % 8 for c in drops)
+
+
+@pytest.mark.parametrize("case", ATTENTION, ids=TC.ids(ATTENTION))
+def test_f32_arithmetic_model_passes_the_block_wise_check(case):
+    """The model of a CORRECT kernel -- the staged reference evaluated in float32 arithmetic: f32 accumulation, bf16 stores --
+    under the block-wise check of tests/test_gpu_train_bf16.py.  Its worst block ratios against S over the attention cases are
+    1.07 in max (O of `core 2x65x97x384 h4`) and 1.007 in rms; doubled once and rounded up to a power of two the max figure
+    gives C_TRAIN_CHAIN = 4.  Asserted here: the max bound with margin 2 (ratio <= C_TRAIN_CHAIN / 2), and the rms bound as the
+    GPU test has it (ratio <= C_TRAIN_CHAIN / 2 = 2).  Margin 2 on the rms would be a limit of 1.0, which no model that rounds
+    where S rounds can meet: its rms error scatters around S's on both sides (1.007 at worst)."""
+    from test_gpu_train_bf16 import C_TRAIN_CHAIN
+    (Wo, Wg), (So, Sg) = case.refs()["W"], case.refs()["S"]
+    outs, grads = case.run(F32, f64.bf16_round)
+    dh = case.gouts[0].shape[2] // case.cfg["heads"]
+    for (name, g, rows), w, s in zip(TC.attention_tensors(case, outs, grads), Wo + Wg, So + Sg):
+        assert torch.equal(g.double(), f64.bf16_round(g))                 # the model's results are bf16 stores
+        TC.check_blocks("f32 model %s" % name, case.name, g, w, s, dh, C_TRAIN_CHAIN / 2, rows, c_rms=C_TRAIN_CHAIN / 2)
+
+
+def test_block_wise_check_sees_a_fault_that_the_tensor_wide_bound_hides():
+    """One wrong tile of small values: the last key tile of the short sequence's dV in one head, off by 3 times its own staged
+    error -- far below the tensor's largest staged error, so max|G - W| <= c max|S - W| over the tensor holds."""
+    from test_gpu_train_bf16 import C_TRAIN_CHAIN
+    case = [c for c in ATTENTION if c.name == "core 2x17x33x128 h4 fused"][0]
+    (Wo, Wg), (So, Sg) = case.refs()["W"], case.refs()["S"]
+    w, s = Wg[2], Sg[2]
+    dh = 32
+    rows, cols = slice(16, 22), slice(2 * dh, 3 * dh)          # sequence 1 has 22 valid keys: key tile 1, head 2
+    bad = s.clone()
+    bad[1, rows, cols] = w[1, rows, cols] + 6 * (s - w)[1, rows, cols]
+    kerr, serr = float((bad - w).abs().max()), float((s - w).abs().max())
+    krms, srms = float((bad - w).pow(2).mean().sqrt()), float((s - w).pow(2).mean().sqrt())
+    assert kerr <= C_TRAIN_CHAIN * serr and krms <= C_TRAIN_CHAIN / 2 * srms          # check_chain's two bounds hold
+    TC.check_blocks("dV", case.name, s, w, s, dh, C_TRAIN_CHAIN)
+    with pytest.raises(AssertionError, match=r"block \(n, tile, column block\) \[1, 1, 2\]"):
+        TC.check_blocks("dV wrong tile", case.name, bad, w, s, dh, C_TRAIN_CHAIN)
+    # an exact zero of W that the kernel misses where S has it: rejected whatever the size
+    off = s.clone()
+    assert float(w[1, 22:].abs().max()) == 0
+    off[1, 32, 5] = 2.0 ** -30
+    with pytest.raises(AssertionError, match="staged reference is exact"):
+        TC.check_blocks("dV masked key", case.name, off, w, s, dh, C_TRAIN_CHAIN)

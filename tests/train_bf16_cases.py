@@ -4,7 +4,11 @@ W  float64 autograd on the bf16-rounded operands (oracle/f64.py, identity stage)
 S  the staged float64 reference (bf16 where the kernels store an activation or a gradient in bf16),
 R  float32 autograd on the CPU (the "f32 allowance" of numerics_regimes.check_bf16_rounding).
 No GPU is needed: tests/test_numerics_reference.py checks the references themselves.  The shapes are the smallest that reach
-each dispatch branch of autograd.py (see the tables in the test module); references are computed once per case (`refs`)."""
+each dispatch branch of autograd.py (see the tables in the test module); the attention shapes go further and reach every
+instantiation of attention_train.hip (head sizes 32, 64, 96, 128, 192; tests/test_numerics_reference.py ties the table to the
+library's list), the waves' second row tiles (rows >= 64), head counts 1, 2, 4, 8 and 24, every tile / padding edge of the sequence
+lengths, the entry forms with ld = 2H / 3H, and dropout on the probabilities through a host model of the mask.  References are
+computed once per case (`refs`)."""
 import functools
 
 import torch
@@ -130,37 +134,149 @@ def qkv_cases():
 
 
 # ---- attention --------------------------------------------------------------------------------------------------------------
-ATTENTION_SHAPES = [(2, 13, 21, 128, 4), (2, 24, 24, 128, 4)]     # (N, Lq, Lk, H, heads); the first with a query mask
+# (N, Lq, Lk, H, heads).  One workgroup of attention_train.hip handles a (sequence, head): wave w owns the 16-row tiles w and
+# w + 4, reductions are padded to multiples of 32 (lkp / lqp), the dropout index runs in the (N * heads, lq8, lk8) layout of the
+# unfused chain (multiples of 8), every operand goes through LDS rows of DH * 2 + 16 bytes.
+ATTENTION_SHAPES = [(2, 13, 21, 128, 4), (2, 24, 24, 128, 4)]     # the first with a query mask; masks from lens_mask seeds
+# every instantiation (DH 32, 64, 96, 128, 192) with the waves' second row tiles (rows >= 64) in use: all four at L = 128
+ATTENTION_FULL = [(2, 128, 128, 128, 4), (2, 100, 100, 256, 4), (2, 65, 97, 384, 4), (2, 128, 128, 512, 4), (2, 100, 100, 768, 4)]
+# head counts other than 4 (gridDim.x in `unit = n * heads + head` and the head * DH column offset): DH 128, 96, 32, 96, 32
+ATTENTION_HEADS = [(2, 24, 24, 128, 1), (2, 40, 40, 192, 2), (2, 33, 64, 256, 8), (2, 30, 30, 768, 8), (2, 20, 20, 768, 24)]
+# (Lq, Lk) at H = 128, 4 heads: 64 | 65 is where a wave's second row tile starts, multiples of 32 the reduction padding,
+# multiples of 8 the dropout layout, 16 the tile
+ATTENTION_EDGES = [(1, 17), (16, 16), (17, 33), (32, 31), (9, 8), (8, 9), (15, 63), (63, 15), (64, 32), (65, 64), (96, 65),
+                   (97, 96), (127, 128), (128, 127)]
+# the unfused bf16 chain; the last has DH = 48, no fused instantiation: the chain is what training runs there
+ATTENTION_CHAIN = [(2, 65, 97, 384, 4), (2, 100, 100, 768, 4), (2, 40, 40, 192, 2), (2, 21, 21, 192, 4)]
+ATTENTION_CHAIN_ONLY = (2, 21, 21, 192, 4)
+# dropout on the probabilities, p = 0.2, fused only; the last two have L8 != L on both sides
+ATTENTION_DROP = [((2, 65, 97, 384, 4), "core"), ((2, 65, 97, 384, 4), "kv"), ((2, 128, 128, 512, 4), "qkv"),
+                  ((2, 100, 100, 768, 4), "core"), ((2, 30, 30, 768, 8), "qkv"), ((2, 17, 33, 128, 4), "core"),
+                  ((2, 13, 21, 128, 4), "core")]
+P_DROP = 0.2
 
 
-def attention_case(n, lq, lk, h, heads, form, fused):
+def prefix_mask(l, lens):
+    return (torch.arange(l)[None, :] < torch.tensor(lens)[:, None]).float()
+
+
+def two_thirds(l):
+    return (2 * l + 2) // 3
+
+
+def attention_case(n, lq, lk, h, heads, form, fused, lens=None, p_drop=0.0, seed=0, supported=True):
     """form: core (q, k, v separate), kv (k, v the column blocks of one (N, Lk, 2H) leaf), qkv (one (N, L, 3H) leaf).
+    lens: (valid keys per sequence, valid queries per sequence or None); None: the seeded masks of ATTENTION_SHAPES.
+    p_drop > 0: dropout on the probabilities with the host model of the kernels' mask (oracle/f64.py drop_keep).
+    supported: what attention_train_supported answers for the shape (False: no fused instantiation for H / heads).
     Rows of masked-out queries depend on float32's absorption of the score into -1e4 (oracle/f64.py header): their upstream
     gradient is zero and their outputs are not compared."""
     q, k, v = act(n, lq, h, seed=1), act(n, lk, h, seed=2), act(n, lk, h, seed=3)
-    km = lens_mask(n, lk, seed=4, lo=3)
-    qm = lens_mask(n, lq, seed=5, lo=3) if lq != lk else None
+    if lens is None:
+        km = lens_mask(n, lk, seed=4, lo=3)
+        qm = lens_mask(n, lq, seed=5, lo=3) if lq != lk else None
+    else:
+        km = prefix_mask(lk, lens[0])
+        qm = None if lens[1] is None else prefix_mask(lq, lens[1])
+    drop = f64.attention_drop(n, heads, lq, lk, p_drop, seed) if p_drop > 0 else None
     gout = act(n, lq, h, seed=6)
     if qm is not None:
         gout = gout * qm[:, :, None].to(BF16)
+    att = lambda q, k, v, stage: f64.train_attention(q, k, v, qm, km, heads, stage, drop)      # noqa: E731
     if form == "core":
         leaves = [q, k, v]
-        fn = lambda q, k, v, stage: f64.train_attention(q, k, v, qm, km, heads, stage)      # noqa: E731
+        fn = att
     elif form == "kv":
         leaves = [q, torch.cat([k, v], -1)]
-        fn = lambda q, kv, stage: f64.train_attention(q, kv[..., :h], kv[..., h:], qm, km, heads, stage)      # noqa: E731
+        fn = lambda q, kv, stage: att(q, kv[..., :h], kv[..., h:], stage)      # noqa: E731
     else:
         leaves = [torch.cat([q, k, v], -1)]
-        fn = lambda t, stage: f64.train_attention(t[..., :h], t[..., h:2 * h], t[..., 2 * h:], qm, km, heads, stage)      # noqa: E731
-    return Case("Attention" + form.capitalize() + "Fn", "%s %dx%dx%dx%d h%d %s" % (form, n, lq, lk, h, heads, "fused" if fused else "chain"),
-                fn, leaves, [True] * len(leaves), [gout], chain=True, q_mask=qm, k_mask=km, heads=heads, fused=fused, form=form)
+        fn = lambda t, stage: att(t[..., :h], t[..., h:2 * h], t[..., 2 * h:], stage)      # noqa: E731
+    name = "%s %dx%dx%dx%d h%d %s%s" % (form, n, lq, lk, h, heads, "fused" if fused else "chain", " p%g" % p_drop if p_drop else "")
+    return Case("Attention" + form.capitalize() + "Fn", name, fn, leaves, [True] * len(leaves), [gout], chain=True, q_mask=qm,
+                k_mask=km, heads=heads, fused=fused, form=form, p_drop=p_drop, seed=seed, drop=drop, supported=supported)
+
+
+def attention_case_at(shape, form, fused, **kw):
+    """a case of the explicit table: N = 2, sequence 0 full, sequence 1 with ceil(2 L / 3) valid keys and -- cross attention
+    (Lq != Lk): a query mask -- the same share of valid queries.  Every case has a masked key, no sequence has none valid."""
+    n, lq, lk, h, heads = shape
+    assert n == 2
+    lens = ((lk, two_thirds(lk)), (lq, two_thirds(lq)) if lq != lk else None)
+    return attention_case(n, lq, lk, h, heads, form, fused, lens=lens, **kw)
 
 
 def attention_cases():
     cross, self_ = ATTENTION_SHAPES
-    return [attention_case(*cross, "core", True), attention_case(*cross, "core", False), attention_case(*cross, "kv", True),
-            attention_case(*self_, "core", True), attention_case(*self_, "core", False), attention_case(*self_, "qkv", True),
-            attention_case(*self_, "qkv", False)]
+    out = [attention_case(*cross, "core", True), attention_case(*cross, "core", False), attention_case(*cross, "kv", True),
+           attention_case(*self_, "core", True), attention_case(*self_, "core", False), attention_case(*self_, "qkv", True),
+           attention_case(*self_, "qkv", False)]
+    for s in ATTENTION_FULL:                  # qkv / kv: ld = 3H / 2H and non-zero column offsets
+        out += [attention_case_at(s, "core", True), attention_case_at(s, "qkv" if s[1] == s[2] else "kv", True)]
+    for s in ATTENTION_HEADS:
+        out += [attention_case_at(s, "core", True)] + ([attention_case_at(s, "qkv", True)] if s[1] == s[2] else [])
+    out += [attention_case_at((2, lq, lk, 128, 4), "core", True) for lq, lk in ATTENTION_EDGES]
+    out += [attention_case_at(s, "core", False, supported=s != ATTENTION_CHAIN_ONLY) for s in ATTENTION_CHAIN]
+    # seeds: both seed words in use (xml_seed_words), a different mask per case
+    out += [attention_case_at(s, form, True, p_drop=P_DROP, seed=(i << 32) + 4242 + i) for i, (s, form) in enumerate(ATTENTION_DROP)]
+    return out
+
+
+def attention_tensors(case, outs, grads):
+    """-> [(name, tensor, compared rows (N, L) bool or None)] of an attention case's output and gradients: masked-out query
+    rows of O are not compared (see attention_case)."""
+    qm = case.cfg["q_mask"]
+    return [("out0", outs[0], None if qm is None else qm > 0)] + [("grad%d" % i, g, None) for i, g in enumerate(grads)]
+
+
+def block_errors(G, W, S, dh, rows=None):
+    """Errors per block = (sequence, 16-row tile, dh-column block) of an (N, L, C) tensor -- what one wave of attention_train.hip
+    computes as one tile of one head -- over the compared rows.  -> dict of (N, tiles, C // dh) tensors: kmax / smax = max|G - W| /
+    max|S - W|, krms / srms, and cnt (compared elements; blocks with cnt == 0 hold no compared row)."""
+    G, W, S = G.detach().cpu().double(), W.double(), S.double()
+    n, l, c = W.shape
+    assert G.shape == W.shape == S.shape and c % dh == 0
+    nt = (l + 15) // 16
+    keep = torch.ones(n, l, dtype=torch.bool) if rows is None else rows
+    keep = torch.nn.functional.pad(keep, (0, nt * 16 - l))
+
+    def blocks(e):
+        e = torch.nn.functional.pad(e, (0, 0, 0, nt * 16 - l)) * keep[:, :, None]
+        return e.view(n, nt, 16, c // dh, dh)
+    eg, es = blocks((G - W).abs()), blocks((S - W).abs())
+    cnt = keep.view(n, nt, 16).sum(2).double()[:, :, None].expand(n, nt, c // dh) * dh
+    div = cnt.clamp_min(1)
+    return dict(kmax=eg.amax((2, 4)), smax=es.amax((2, 4)), krms=(eg.pow(2).sum((2, 4)) / div).sqrt(),
+                srms=(es.pow(2).sum((2, 4)) / div).sqrt(), cnt=cnt)
+
+
+def check_blocks(name, case, G, W, S, dh, c, rows=None, c_rms=None):
+    """Block-wise chain check: in every block max|G - W| <= c max|S - W| and rms(G - W) <= c_rms (c / 2) rms(S - W) (the block's own
+    staged error, not the tensor's), and G == W exactly where S == W exactly.  A fault confined to one tile of small values (the
+    far key tile of a short sequence, one head's column block) hides under the tensor-wide maximum of check_chain.
+    -> worst max ratio, worst rms ratio, number of blocks."""
+    c_rms = c / 2 if c_rms is None else c_rms
+    e = block_errors(G, W, S, dh, rows)
+    used = e["cnt"] > 0
+    exact = used & (e["smax"] == 0)
+    wrong = exact & (e["kmax"] != 0)
+    assert not bool(wrong.any()), "%s %s: %d blocks differ from W where the staged reference is exact; (n, tile, column block) %s" % (
+        name, case, int(wrong.sum()), wrong.nonzero()[:4].tolist())
+    live = used & ~exact
+    one = torch.ones(())
+    rmax = torch.where(live, e["kmax"] / torch.where(live, e["smax"], one), 0 * one)
+    rrms = torch.where(live, e["krms"] / torch.where(live, e["srms"], one), 0 * one)
+    wm, wr = float(rmax.max()), float(rrms.max())
+    im = [int(x) for x in (rmax == rmax.max()).nonzero()[0]]
+    ir = [int(x) for x in (rrms == rrms.max()).nonzero()[0]]
+    print("NUMERICS %s %s bf16 blocks: %d worst max ratio %.3f at (n, tile, column block) %s kernel_err %.3e ref_err %.3e; "
+          "worst rms ratio %.3f at %s" % (name, case, int(used.sum()), wm, im, float(e["kmax"][tuple(im)]),
+                                          float(e["smax"][tuple(im)]), wr, ir))
+    assert wm <= c, "%s %s: block (n, tile, column block) %s: max|G-W| %.3e > %g x the staged reference's %.3e in that block" % (
+        name, case, im, float(e["kmax"][tuple(im)]), c, float(e["smax"][tuple(im)]))
+    assert wr <= c_rms, "%s %s: block (n, tile, column block) %s: rms %.3e > %g x the staged reference's %.3e in that block" % (
+        name, case, ir, float(e["krms"][tuple(ir)]), c_rms, float(e["srms"][tuple(ir)]))
+    return wm, wr, int(used.sum())
 
 
 # ---- ModularPoolFn ----------------------------------------------------------------------------------------------------------
