@@ -299,22 +299,36 @@ def train_pair_sim(q, f2, stage=ident):
     return torch.einsum("bd,bld->bl", staged(q, stage, fwd=False), staged(f2, stage, fwd=False))
 
 
-def train_span_loss(sims, filters, mask, st_ed, merged, ks):
-    """SpanLossFn (f32 in the bf16 model too: PairSimFn's output is f32): no bf16 boundary."""
+def span_logits(sims, filters, mask, merged, ks):
+    """The masked start / end logits (N, L) of the span head.  mask: one (N, L) mask for every stream, or a list / tuple with
+    one mask per stream (the split form masks stream i with mask i; the merged form has one stream and uses the first)."""
     n_sim = len(sims)
-    mask = mask.to(sims[0].dtype)
+    masks = list(mask) if isinstance(mask, (list, tuple)) else [mask] * n_sim
+    masks = [m.to(sims[0].dtype) for m in masks]
     conv = lambda s, w: F.conv1d(s.unsqueeze(1), w, padding=ks // 2).squeeze(1)     # noqa: E731
     if merged:
         s = (sims[0] + sims[1]) / 2
-        lst, led = O.mask_logits(conv(s, filters[0]), mask), O.mask_logits(conv(s, filters[1]), mask)
+        lst, led = O.mask_logits(conv(s, filters[0]), masks[0]), O.mask_logits(conv(s, filters[1]), masks[0])
     else:
-        lst = sum(O.mask_logits(conv(sims[i], filters[i]), mask) for i in range(n_sim)) / n_sim
-        led = sum(O.mask_logits(conv(sims[i], filters[n_sim + i]), mask) for i in range(n_sim)) / n_sim
+        lst = sum(O.mask_logits(conv(sims[i], filters[i]), masks[i]) for i in range(n_sim)) / n_sim
+        led = sum(O.mask_logits(conv(sims[i], filters[n_sim + i]), masks[i]) for i in range(n_sim)) / n_sim
+    return lst, led
+
+
+def train_span_loss(sims, filters, mask, st_ed, merged, ks):
+    """SpanLossFn (f32 in the bf16 model too: PairSimFn's output is f32): no bf16 boundary.  mask: see `span_logits`."""
+    lst, led = span_logits(sims, filters, mask, merged, ks)
     return F.cross_entropy(lst, st_ed[:, 0]) + F.cross_entropy(led, st_ed[:, 1])
 
 
+def rank_order(scores_masked):
+    """(N, N) -> the column order of every row, descending, equal values: lower index first (rank_loss_kernel's documented
+    rule; a stable sort -- without it torch leaves the order of ties undefined)."""
+    return torch.sort(scores_masked, descending=True, dim=1, stable=True)[1]
+
+
 def train_rank_loss(scores, ranks_ctx, ranks_q, margin, lse):
-    """RankLossFn (f32 scores from VideoLevelScoresFn): no bf16 boundary."""
+    """RankLossFn (f32 scores from VideoLevelScoresFn): no bf16 boundary.  Ties: lower index first (`rank_order`)."""
     n = scores.shape[0]
     ar = torch.arange(n)
     pos = scores[ar, ar]
@@ -322,8 +336,10 @@ def train_rank_loss(scores, ranks_ctx, ranks_q, margin, lse):
     masked[ar, ar] = 999
 
     def neg(sc, scm, r):
-        return sc[ar, torch.sort(scm, descending=True, dim=1)[1][ar, r.long()]]
+        return sc[ar, rank_order(scm)[ar, r.long()]]
 
     def rl(p, ng):
-        return torch.log1p(torch.exp(ng - p)).sum() / n if lse else torch.clamp(margin + ng - p, min=0).sum() / n
+        # margin + (neg - pos), the difference first: a fully masked video has pos = neg = -1e10, whose difference is exactly 0,
+        # whereas (margin + neg) - pos loses the margin to absorption (all of it in float32, 1e-6 of it in float64)
+        return torch.log1p(torch.exp(ng - p)).sum() / n if lse else torch.clamp(margin + (ng - p), min=0).sum() / n
     return torch.stack([rl(pos, neg(scores, masked, ranks_ctx)), rl(pos, neg(scores.t(), masked.t(), ranks_q))])

@@ -9,7 +9,9 @@ without a GPU.
 * the staged float64 AUTOGRAD references of the training nodes (oracle/f64.py, tests/train_bf16_cases.py): identity stage ==
   plain float64 autograd bit for bit, staged != exact, one bf16 store stays within half a bf16 ulp of W (<= 2^-8 |W|) plus one f32 rounding;
 * sensitivity: deliberately wrong stand-ins are rejected by the check meant for them while the existing `close(...)`
-  limits of test_gpu_kernels.py accept them on that suite's operands."""
+  limits of test_gpu_kernels.py accept them on that suite's operands;
+* the case tables of the training loss tail and the optimizer (tests/train_tail_cases.py) meet their own conditions, and CPU
+  restatements of six wrong kernels fail the new cases while the cases the suite had before accept them."""
 import math
 
 import pytest
@@ -18,6 +20,7 @@ import torch.nn.functional as F
 
 import numerics_regimes as NR
 import train_bf16_cases as TC
+import train_tail_cases as TT
 from oracle import f64
 from oracle import xml_oracle as O
 from test_gpu_kernels import _att_weights, _ragged_mask, close, rnd
@@ -453,3 +456,229 @@ def test_block_wise_check_sees_a_fault_that_the_tensor_wide_bound_hides():
     off[1, 32, 5] = 2.0 ** -30
     with pytest.raises(AssertionError, match="staged reference is exact"):
         TC.check_blocks("dV masked key", case.name, off, w, s, dh, C_TRAIN_CHAIN)
+
+
+# ---- the training loss tail and the optimizer at every loop edge (tests/train_tail_cases.py, tests/test_gpu_train_tail.py) ------
+TAIL = dict(pair=TT.pair_sim_cases(), span=TT.span_cases(), rank=TT.rank_cases(), scores=TT.scores_cases())
+TOY = dict(pair=[TC.pair_sim_case()], span=TC.span_loss_cases(), rank=TC.rank_loss_cases(), scores=TC.scores_cases())
+
+
+def _masks_of(case):
+    return case.cfg["masks"] if "masks" in case.cfg else [case.cfg["mask"]] * case.cfg["n_sim"]
+
+
+def _keep_out(case):
+    if case.op != "VideoLevelScoresFn":
+        return None
+    keep = torch.ones(case.gouts[0].shape[1], dtype=torch.bool)
+    keep[2] = False                                 # the fully masked video's column
+    return keep
+
+
+def _as_kernel(case, res):
+    """(outs, grads) of a float64 model -> in the dtypes the kernel returns (bf16 gradients for bf16 leaves)."""
+    outs, grads = res
+    return outs, [g if g is None or t.dtype != BF16 else f64.bf16_round(g) for g, t in zip(grads, case.leaves)]
+
+
+def test_tail_case_tables_meet_their_own_conditions():
+    # PairSimFn: the listed shapes, both dtypes, a partial last workgroup of the forward kernel
+    assert {tuple(c.leaves[1].shape) for c in TAIL["pair"]} == set(TT.PAIR_SIM_SHAPES) and len(TAIL["pair"]) == 2 * len(TT.PAIR_SIM_SHAPES)
+    assert any((n * l) % 4 for n, l, _ in TT.PAIR_SIM_SHAPES)
+    # SpanLossFn
+    assert {l for _, l, _ in TT.SPAN_SHAPES} == {1, 3, 63, 64, 65, 100, 127, 128} and {k for _, _, k in TT.SPAN_SHAPES} == {1, 3, 5, 31}
+    assert {n for n, _, _ in TT.SPAN_SHAPES} == {1, 4, 5, 9} and (4, 3, 31) in TT.SPAN_SHAPES and (4, 128, 31) in TT.SPAN_SHAPES
+    two_masks = second_half = clip0 = last_clip = len1 = 0
+    for c in TAIL["span"]:
+        st_ed, masks = c.cfg["st_ed"], c.cfg["masks"]
+        rows = torch.arange(c.cfg["n"])
+        for m in masks:                             # targets on unmasked clips of every stream
+            assert bool((m[rows, st_ed[:, 0]] == 1).all()) and bool((m[rows, st_ed[:, 1]] == 1).all())
+        assert bool((st_ed[:, 0] <= st_ed[:, 1]).all())
+        lens = masks[0].sum(1).long()
+        two_masks += len(masks) == 2 and not torch.equal(masks[0], masks[1])
+        second_half += bool((st_ed[:, 0] >= 64).any()) and bool((st_ed[:, 1] >= 64).any())
+        clip0 += bool((st_ed[:, 0] == 0).any())
+        last_clip += bool((st_ed[:, 1] == lens - 1).any()) and bool((st_ed[:, 0] == lens - 1).any())
+        len1 += bool((lens == 1).any())
+    assert two_masks >= 2 and second_half >= 9 and clip0 == len(TAIL["span"]) and last_clip >= 30 and len1 >= 30
+    # RankLossFn
+    assert {c.cfg["n"] for c in TAIL["rank"] if c.cfg["kind"] is None} == set(TT.RANK_NS)
+    for c in TAIL["rank"]:
+        n, rc, rq = c.cfg["n"], c.cfg["rc"], c.cfg["rq"]
+        for r in (rc, rq):
+            assert int(r.min()) >= 1 and int(r.max()) <= n - 1 and int(r[0]) == 1 and int(r[1]) == n - 1
+        if not c.cfg["lse"]:
+            assert TT.hinge_distance(c) > TT.HINGE_CLEAR, c
+        # the tie rule shows in the tie cases ("higher index first" selects other positions) and in no other
+        flipped = n - 1 - f64.rank_order(TT.rank_masked(c.leaves[0]).flip(1))[torch.arange(n), rc.long()]
+        assert torch.equal(flipped, TT.rank_selected(c.leaves[0], rc, rq)[0]) == (c.cfg["kind"] is None), c
+        if c.cfg["kind"] == "straddle":             # rows 8 .. 11 select columns 253 .. 256 in turn, columns 12 .. 15 those rows
+            cols, rows = TT.rank_selected(c.leaves[0], rc, rq)
+            assert cols[8:12].tolist() == [253, 254, 255, 256] and rows[12:16].tolist() == [253, 254, 255, 256]
+    # VideoLevelScoresFn
+    assert {c.cfg["shape"] for c in TAIL["scores"]} == set(TT.SCORES_SHAPES)
+    for c in TAIL["scores"]:
+        assert TT.scores_gap(c) >= TT.SCORE_GAP, c
+        assert c.cfg["dense"] or int((c.gouts[0] != 0).sum(1).max()) <= 3
+        for v, (p1, p2) in c.cfg["ties"].items():
+            f = c.leaves[c.cfg["n_mod"]]
+            assert p1 < p2 and torch.equal(f[v, p1], f[v, p2]) and float(c.cfg["masks"][0][v, p2]) == 1
+    tiles = {(p1 // 16 == p2 // 16) for _, t in TT.SCORES_TIES for p1, p2 in t.values()}
+    assert tiles == {True, False}
+    # every case: R passes the checks by itself and at most ROW_CAP of the rows of any tensor are excluded
+    for c in sum(TAIL.values(), []):
+        assert all(s <= TT.ROW_CAP for s in TT.excluded_shares(c)), c
+        refs = c.refs()
+        outs, grads = refs["R"]
+        grads = [g if g is None or t.dtype != BF16 else refs["S"][1][i] for i, (g, t) in enumerate(zip(grads, c.leaves))]
+        TT.check_case(c, outs, grads, keep_out=_keep_out(c))
+
+
+# -- wrong kernels, restated on the CPU in float64 (so that nothing but the fault separates them from W) ------------------------
+def _span_lanes_below_64(case):
+    """span_loss_kernel without its h = 1 half: clips >= 64 have no logit, no softmax term, no target match, no DC row."""
+    cfg = case.cfg
+    n_sim, st_ed = cfg["n_sim"], cfg["st_ed"]
+
+    def fn(*t, stage):
+        tot = 0
+        for lg, tg in zip(f64.span_logits(t[:n_sim], t[n_sim:], _masks_of(case), cfg["merged"], cfg["ks"]), (st_ed[:, 0], st_ed[:, 1])):
+            low = lg[:, :64]
+            hit = tg < 64
+            tl = torch.where(hit, low[torch.arange(lg.shape[0]), tg.clamp(max=low.shape[1] - 1)], torch.zeros((), dtype=lg.dtype))
+            tot = tot + (torch.logsumexp(low, 1) - tl).mean()
+        return tot
+    return _as_kernel(case, TT.run_fn(case, fn))
+
+
+def _rank_model(select):
+    """rank_loss_kernel with another selection: select(masked (n, n), ranks) -> (index per row, pair counted per row)."""
+    def model(case):
+        cfg = case.cfg
+        lse, rc, rq = cfg["lse"], cfg["rc"], cfg["rq"]
+
+        def fn(s, stage):
+            n = s.shape[0]
+            ar = torch.arange(n)
+            pos = s[ar, ar]
+            m = TT.rank_masked(s)
+            out = []
+            for sc, mm, r in ((s, m, rc), (s.t(), m.t().contiguous(), rq)):
+                idx, live = select(mm, r.long())
+                x = sc[ar, idx] - pos
+                term = torch.log1p(torch.exp(x)) if lse else torch.clamp(TT.MARGIN + x, min=0)
+                out.append((term * live.to(term.dtype)).sum() / n)
+            return torch.stack(out)
+        return _as_kernel(case, TT.run_fn(case, fn))
+    return model
+
+
+def _sel_stable(m, r):
+    ar = torch.arange(m.shape[0])
+    return f64.rank_order(m)[ar, r], torch.ones(m.shape[0], dtype=torch.bool)
+
+
+def _sel_higher_index_first(m, r):
+    """`k > j` in place of `k < j`: equal values, higher index first."""
+    ar = torch.arange(m.shape[0])
+    return m.shape[0] - 1 - f64.rank_order(m.flip(1))[ar, r], torch.ones(m.shape[0], dtype=torch.bool)
+
+
+def _sel_counting_itself(m, r):
+    """`k <= j` in place of `k < j`: every element counts itself, the kernel selects rank - 1."""
+    ar = torch.arange(m.shape[0])
+    return f64.rank_order(m)[ar, r - 1], torch.ones(m.shape[0], dtype=torch.bool)
+
+
+def _sel_first_pass_only(m, r):
+    """the row loop without its j += 256 stride: a wanted element at j >= 256 is never found."""
+    idx, _ = _sel_stable(m, r)
+    return idx, idx < 256
+
+
+def _pair_sim_first_64_chunks(case):
+    """pair_sim_bwd_vec_kernel without its c0 += 64 loop: hidden columns >= 512 of dq and df2 are never written (zeros here)."""
+    outs, grads = case.run(torch.float64, f64.ident)
+    h = case.leaves[0].shape[-1]
+    if h % 8 == 0 and h <= 2048:
+        grads = [g.clone() for g in grads]
+        for g in grads:
+            g[..., 512:] = 0
+    return _as_kernel(case, (outs, grads))
+
+
+def _argmax_last_on_ties(case):
+    if not case.cfg.get("ties"):
+        return _as_kernel(case, case.run(torch.float64, f64.ident))
+    cfg = case.cfg
+    wrong = TT.scores_case(*cfg["shape"], cfg["n_mod"], cfg["dense"], fused=cfg["fused"], ties=cfg["ties"], last=True)
+    return wrong.run(torch.float64, f64.ident)
+
+
+MUTANTS = [("span: lanes >= 64 dropped", "span", _span_lanes_below_64),
+           ("rank: ties, higher index first", "rank", _rank_model(_sel_higher_index_first)),
+           ("rank: only j < 256", "rank", _rank_model(_sel_first_pass_only)),
+           ("pair_sim_bwd: chunks >= 64 skipped", "pair", _pair_sim_first_64_chunks),
+           ("arg-max: last clip on ties", "scores", _argmax_last_on_ties)]
+
+
+def _rejected(case, res):
+    try:
+        TT.check_case(case, *res, keep_out=_keep_out(case))
+    except AssertionError:
+        return True
+    if case.op == "RankLossFn":                     # the structural check of the GPU test
+        return not torch.equal(res[1][0] != 0, case.refs()["W"][1][0] != 0)
+    return False
+
+
+@pytest.mark.parametrize("name,op,model", MUTANTS, ids=[m[0] for m in MUTANTS])
+def test_wrong_tail_kernels_fail_the_new_cases_and_pass_the_old_ones(name, op, model):
+    """Each restated fault is rejected on at least one new case and accepted on every case the suite had before: the gap was real."""
+    bad = [c.name for c in TAIL[op] if _rejected(c, model(c))]
+    assert bad, "%s: accepted on every new case" % name
+    print("MUTANT %s: rejected on %d of %d new cases, e.g. %s" % (name, len(bad), len(TAIL[op]), bad[:3]))
+    for c in TOY[op]:
+        assert not _rejected(c, model(c)), "%s: the old case %s already rejects it" % (name, c)
+    # what rejects it is what was built for it
+    expect = {"span": lambda c: c.cfg["l"] > 64, "pair": lambda c: 512 < c.leaves[0].shape[-1] <= 2048 and c.leaves[0].shape[-1] % 8 == 0,
+              "scores": lambda c: bool(c.cfg["ties"]),
+              "rank": lambda c: c.cfg["kind"] is not None if "ties" in name else c.cfg["n"] > 256}[op]
+    want = [c.name for c in TAIL[op] if expect(c)]
+    assert set(bad) <= set(want) and (op == "rank" or bad == want), (bad, want)
+
+
+def test_correct_restatements_pass_every_new_case():
+    """the mutants' scaffolding with the right rule is accepted everywhere: the rejections above come from the faults alone."""
+    for c in TAIL["rank"] + TOY["rank"]:
+        assert not _rejected(c, _rank_model(_sel_stable)(c)), c
+    for c in TAIL["span"]:
+        if c.cfg["l"] <= 64:
+            assert not _rejected(c, _span_lanes_below_64(c)), c
+
+
+def test_rank_loss_that_counts_an_element_itself_is_off_by_one_everywhere():
+    """The literal `k <= j` in the tie count makes every element count itself: the kernel then selects rank - 1 for every row,
+    ties or not.  The old n = 17 cases reject that already; it is listed for completeness -- the tie rule proper is the
+    "higher index first" model above, which only the new tie cases reject."""
+    model = _rank_model(_sel_counting_itself)
+    assert all(_rejected(c, model(c)) for c in TAIL["rank"]) and all(_rejected(c, model(c)) for c in TOY["rank"])
+
+
+def test_adam_norm_that_misses_blocks_past_64_fails_the_new_layout_only():
+    for layout, caught in ((TT.adam_layout(9), True), (TT.adam_layout(10), False), (TT.adam_toy_layout(), False)):
+        names, sizes = layout
+        state = TT.adam_state(sizes)
+        want = TT.adam_reference(state)
+        # the scaffolding: the true norms through the injected-norm path give the oracle's own step
+        same = TT.adam_reference(state, sumsq=lambda g, off: TT.adam_sumsq_all(g, off))
+        assert TT.check_adam("true norms", same[:4], want[:4], state["seg_off"], names, tol=1e-12) <= 1e-12
+        wrong = TT.adam_reference(state, sumsq=TT.adam_sumsq_first_64_blocks)
+        if caught:
+            with pytest.raises(AssertionError, match="tensor big"):
+                TT.check_adam("first 64 blocks", wrong[:4], want[:4], state["seg_off"], names)
+        else:                                       # total % 4 != 0: no block partials at all; toy: no tensor has 64 blocks
+            TT.check_adam("first 64 blocks", wrong[:4], want[:4], state["seg_off"], names)
+    big = TT.adam_layout(9)[1][4]
+    assert max(TT.adam_toy_layout()[1]) // 1024 < 64 < big // 1024
