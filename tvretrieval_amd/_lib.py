@@ -292,6 +292,13 @@ SIGNATURES_PARTS_EXACT = {
     "xml_chain_members": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
 }
 
+# the companion header include/xmlhip_ingest_pool.h (tests/test_ingest_pool_capi.py checks): ingest from frame- and word-level
+# stores -- clip pooling in the ingest launch
+SIGNATURES_INGEST_POOL = {
+    "xml_ingest_pool_rows": (c_int, [c_int] + [c_void_p, c_int, c_int64, c_int, c_void_p, c_int] * 2 + [c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p] + [c_int] * 3 + [c_float, c_int, c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -299,7 +306,8 @@ def bind(lib):
     """Attach restype / argtypes of every header symbol to a loaded library; check the ABI version."""
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
             list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()) + \
-            list(SIGNATURES_EXACT_PACKED.items()) + list(SIGNATURES_PARTS_EXACT.items()):
+            list(SIGNATURES_EXACT_PACKED.items()) + list(SIGNATURES_PARTS_EXACT.items()) + \
+            list(SIGNATURES_INGEST_POOL.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

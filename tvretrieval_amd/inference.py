@@ -34,7 +34,8 @@ index_clear_rows) and the searches and updates of one with chains of slots for l
 chain_best_allow, chain_best_rows) and the updates and searches of an exact-rank one (index_put_rows_exact,
 exact_certificate_dev, index_exact_bound; with the packed filter image index_put_rows_packed_exact; with chains of slots
 cand_best_part, chain_spread_allow, chain_members) and the subset views of
-video_subset (index_gather_blocks; HIP only, a search with subset= refuses any other backend) call further entries of
+video_subset (index_gather_blocks; HIP only, a search with subset= refuses any other backend) and a ContextFeeder over
+ingest.PooledStore frame- / word-level stores (ingest_pool_rows; HIP only) call further entries of
 tvretrieval_amd.ops; a backend without them serves every search that does not ask for those.
 """
 import numpy as np

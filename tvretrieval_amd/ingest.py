@@ -12,6 +12,13 @@
                       asynchronously on a side stream (the H2D copy of batch i+1 overlaps the encoder kernels of batch
                       i), and ONE device launch (xml_ingest_rows) truncates, pads, converts, normalises and writes
                       the mask.
+  PooledStore         1-2 FRAME- or WORD-level FeatureStores (what a feature extractor emits) + the source-row range of every
+                      clip; ContextFeeder takes one in place of a clip store: it stages the fine rows, and ONE launch
+                      (xml_ingest_pool_rows) pools them into clips (max / mean), normalises each source, concatenates,
+                      and does the rest of the collate -- the reference's three offline numpy + h5py conversion scripts
+                      (utils/video_feature/convert_feature_frm_to_clip.py, normalize_and_concat.py,
+                      utils/text_feature/convert_sub_feature_word_to_clip.py) and their clip-level copy of the corpus on
+                      disk are not needed.  frame_clip_boundaries / sentence_word_ranges restate their index arithmetic.
   StoreEvalDataset    the reference's eval-dataset contract (set_data_mode / load_gt_vid_name_for_query / items with
                       "meta" + "model_inputs") over FeatureStores, for compute_context_info / compute_query2ctx_info.
 """
@@ -82,6 +89,114 @@ class FeatureStore(object):
 
 
 _TORCH_DT = {"float16": torch.float16, "float32": torch.float32}
+
+
+def frame_clip_boundaries(clip_length=1.5, max_video_length=300, frames_in_second=(3, 13, 23), video_fps=30.):
+    """Clip boundaries in frame-feature rows (get_clip2frm_idx_mapping, utils/video_feature/convert_feature_frm_to_clip.py:
+    40-62): the extractor kept frames `frames_in_second` of every second of a `video_fps` video, so feature row j shows second
+    j // k + frames_in_second[j % k] / video_fps; boundary c is the number of rows before c * clip_length seconds, and clip c is
+    rows [b[c], b[c + 1]).  The defaults give 200 boundaries 0 5 9 14 18 23 27 32 ...: clips of 4 or 5 frames."""
+    sec = np.arange(0, max_video_length)
+    times = (np.asarray(frames_in_second)[None, :] / video_fps + sec[:, None]).reshape(-1)
+    return np.searchsorted(times, np.arange(0, max_video_length, clip_length))
+
+
+def sentence_word_ranges(sub_times, sentence_lengths, n_clips, clip_length=1.5):
+    """Word-row range of every clip of one video (process_single_vid_sub + the range logic of convert_h5,
+    utils/text_feature/convert_sub_feature_word_to_clip.py:19-32,68-86).  sub_times (n_sub, 2): start / end seconds of the
+    subtitle sentences in file order; sentence_lengths (num_sens,): word rows per sentence in the word store (num_sens may be
+    below n_sub).  Sentence s is taken by clips floor(st / clip_length) .. ceil(ed / clip_length) - 1 (float32 arithmetic, as
+    there); sentence numbers are clamped to num_sens - 1; a clip's words run from the start of its first sentence to the end of
+    its last.  -> (n_clips, 2) int64 [lo, hi) relative to the video's first word row; [0, 0] where no sentence touches the
+    clip or the range holds no words."""
+    n_clips = int(n_clips)
+    out = np.zeros((n_clips, 2), dtype=np.int64)
+    t = np.asarray(sub_times, dtype=np.float32).reshape(-1, 2) / clip_length
+    lens = np.asarray(sentence_lengths, dtype=np.int64).reshape(-1)
+    num_sens = len(lens)
+    if n_clips == 0 or len(t) == 0 or num_sens == 0:
+        return out
+    word_start = np.concatenate([[0], np.cumsum(lens)])
+    st = np.floor(t[:, 0]).astype(np.int64)
+    ed = np.ceil(t[:, 1]).astype(np.int64)
+    first = np.full(n_clips, -1, dtype=np.int64)          # lowest and highest sentence that touches each clip
+    last = np.full(n_clips, -1, dtype=np.int64)
+    for s in range(len(t)):
+        a, b = max(int(st[s]), 0), min(int(ed[s]), n_clips)
+        if a < b:
+            first[a:b] = np.where(first[a:b] < 0, s, np.minimum(first[a:b], s))
+            last[a:b] = np.maximum(last[a:b], s)
+    hit = first >= 0
+    lo = word_start[np.minimum(first[hit], num_sens - 1)]
+    hi = word_start[np.minimum(last[hit], num_sens - 1) + 1]
+    lo, hi = np.where(lo == hi, 0, lo), np.where(lo == hi, 0, hi)
+    out[hit, 0], out[hit, 1] = lo, hi
+    return out
+
+
+class PooledStore(object):
+    """Clip rows that are POOLED on the device from finer rows: sources = 1 or 2 tuples (FeatureStore, ranges, normalize), in
+    column order (ResNet, then I3D).  ranges is either
+      a 1-D boundary array b shared by every video (frame_clip_boundaries): clip c of a video of F rows is rows
+        [b[c], min(b[c + 1], F)); the video has the clips before the first empty one, as convert_for_single_h5 breaks there
+        (convert_feature_frm_to_clip.py:29-32) -- at most len(b) - 1;
+      or a mapping name -> (n_clips, 2) [lo, hi) relative to the video's first row (sentence_word_ranges); lo == hi: no rows,
+        the clip's block is zero.
+    normalize: x / (||x|| + 1e-5) on that source's pooled block (normalize_and_concat.py).  pool: "max" or "mean".
+    ContextFeeder(video_store= / sub_store=) takes a PooledStore in place of a FeatureStore; n_rows / dim are in CLIPS and
+    output columns, like a clip store's."""
+
+    def __init__(self, sources, pool="max"):
+        sources = list(sources)
+        if len(sources) not in (1, 2):
+            raise ValueError("PooledStore: 1 or 2 sources expected, got %d" % len(sources))
+        if pool not in ("max", "mean"):
+            raise ValueError("PooledStore: pool must be 'max' or 'mean', got %r" % (pool,))
+        self.pool, self.stores, self.ranges, self.norms = pool, [], [], []
+        for store, ranges, normalize in sources:
+            if not isinstance(ranges, dict):
+                ranges = np.asarray(ranges)
+                if ranges.ndim != 1 or len(ranges) < 2 or not np.issubdtype(ranges.dtype, np.integer) or \
+                        ranges[0] < 0 or (np.diff(ranges) < 0).any():
+                    raise ValueError("PooledStore: a shared boundary array must be 1-D, integer, non-negative and rising, with "
+                                     "at least 2 entries")
+                ranges = ranges.astype(np.int64)
+            self.stores.append(store)
+            self.ranges.append(ranges)
+            self.norms.append(bool(normalize))
+        self.dim = sum(int(s.dim) for s in self.stores)
+        self._cache = {}
+
+    def __contains__(self, name):
+        return all(name in s for s in self.stores)
+
+    def _source_ranges(self, si, name):
+        store, rg = self.stores[si], self.ranges[si]
+        rows = int(store.index[name][1])
+        if isinstance(rg, dict):
+            r = np.asarray(rg[name], dtype=np.int64).reshape(-1, 2)
+            if ((r[:, 0] < 0) | (r[:, 0] > r[:, 1]) | (r[:, 1] > rows)).any():
+                raise ValueError("PooledStore: a range of %r lies outside 0 <= lo <= hi <= %d rows of source %d" % (name, rows, si))
+            return r
+        lo, hi = rg[:-1], np.minimum(rg[1:], rows)
+        empty = hi - lo <= 0
+        n = int(np.argmax(empty)) if empty.any() else len(lo)
+        return np.stack([lo[:n], hi[:n]], axis=1)
+
+    def clip_ranges(self, name):
+        """Per source the (n_clips, 2) int64 [lo, hi) ranges of the video's clips, relative to its first row in that source."""
+        got = self._cache.get(name)
+        if got is None:
+            got = [self._source_ranges(si, name) for si in range(len(self.stores))]
+            if len({len(r) for r in got}) != 1:
+                raise ValueError("PooledStore: the sources disagree on the clip count of %r: %s"
+                                 % (name, " / ".join(str(len(r)) for r in got)))
+            self._cache[name] = got
+        return got
+
+    def n_rows(self, name):
+        """clips of the video"""
+        return len(self.clip_ranges(name)[0])
 
 
 class PartTable(object):
@@ -208,7 +323,9 @@ class ContextFeeder(object):
         """feature_dtype=torch.bfloat16 (bf16 models only): the normalised features are handed over in bf16 -- the encoder's
         input LayerNorm reads half the bytes (the C ABI takes f32 or the compute dtype); the reference's contract is f32.
         parts (PartTable of plan_parts over these videos' clip counts, host): nothing is cut off -- the feeder iterates batches
-        of PARTS, each the rows [offset, offset + len) of its video in the store; rows that two parts share are copied twice."""
+        of PARTS, each the rows [offset, offset + len) of its video in the store; rows that two parts share are copied twice.
+        video_store / sub_store may be a PooledStore (frame- / word-level rows): the fine rows a batch's clips name are staged
+        and copied instead, and xml_ingest_pool_rows pools them into clips in the collate launch; stats then count fine rows."""
         self.feature_dtype = feature_dtype
         self.names, self.vs, self.ss = list(video_names), video_store, sub_store
         self.max_ctx_len, self.bsz = int(max_ctx_len), int(batch_size)
@@ -223,7 +340,10 @@ class ContextFeeder(object):
             for tag, store in (("video", video_store), ("sub", sub_store)):
                 if store is None:
                     continue
-                have = np.array([store.index[n][1] for n in self.names], dtype=np.int64)
+                if isinstance(store, PooledStore):
+                    have = np.array([store.n_rows(n) for n in self.names], dtype=np.int64)
+                else:
+                    have = np.array([store.index[n][1] for n in self.names], dtype=np.int64)
                 if (have != counts).any():
                     i = int(np.nonzero(have != counts)[0][0])
                     raise ValueError("ContextFeeder: the part table was planned for %d clips of %r, the %s store holds %d "
@@ -296,6 +416,97 @@ class ContextFeeder(object):
         self.stats["gather_s"] += time.perf_counter() - t0
         return buf, rows, torch.from_numpy(start), int(lens.max())
 
+    def _gather_pooled(self, pstore, items, slot, tag):
+        """The batch of a PooledStore: per source only the fine rows that the items' clips (a video's first max_ctx_len, or a
+        part's) name -- per item the span from the first to the last of them -- go back to back into the pinned buffer, and seg
+        (R, 2) int64 holds each clip row's range RELATIVE TO THAT BUFFER ([0, 0]: no rows).  -> ([(buffer, rows, seg)] per
+        source, row_start (n + 1) int64 over the clip rows, lmax)"""
+        import time
+        t0 = time.perf_counter()
+        if self.parts is None:
+            clips = [(n, 0, min(pstore.n_rows(n), self.max_ctx_len)) for n in items]
+        else:
+            pt = self.parts
+            clips = [(self.names[pt.part_video[p]], int(pt.part_offset[p]), int(pt.part_len[p])) for p in items]
+        lens = np.array([c[2] for c in clips], dtype=np.int64)
+        start = np.concatenate([[0], np.cumsum(lens)])
+        per_source = []
+        for si, store in enumerate(pstore.stores):
+            seg = np.zeros((int(start[-1]), 2), dtype=np.int64)
+            runs, rows = [], 0
+            for k, (name, c0, ln) in enumerate(clips):
+                r = pstore.clip_ranges(name)[si][c0:c0 + ln]
+                full = r[:, 1] > r[:, 0]
+                if not full.any():
+                    continue
+                lo, hi = int(r[full, 0].min()), int(r[full, 1].max())
+                seg[int(start[k]):int(start[k + 1])] = np.where(full[:, None], r - lo + rows, 0)
+                src = int(store.index[name][0]) + lo
+                if runs and runs[-1][0] + runs[-1][2] == src:          # adjacent in the store: one copy
+                    runs[-1] = (runs[-1][0], runs[-1][1], runs[-1][2] + hi - lo)
+                else:
+                    runs.append((src, rows, hi - lo))
+                rows += hi - lo
+            key = (tag, slot, si)
+            ev = self._slot_done.get(key)
+            if ev is not None:       # the copy that last read this pinned slot must have finished before it is rewritten
+                ev.synchronize()
+            buf = self._stage.get(key)
+            if buf is None or buf.shape[0] < max(rows, 1):
+                buf = torch.empty((max(int(rows * 1.25), 1), store.dim), dtype=_TORCH_DT[store.dtype])
+                if self.device.type == "cuda":
+                    buf = buf.pin_memory()
+                self._stage[key] = buf
+            out = buf.numpy()
+            chunk = max(1, (8 << 20) // (store.dim * out.itemsize))              # ~8 MB pieces
+            jobs = [(s + o, d + o, min(chunk, n - o)) for s, d, n in runs for o in range(0, n, chunk)]
+
+            def copy(j, out=out, store=store):
+                out[j[1]:j[1] + j[2]] = store.data[j[0]:j[0] + j[2]]
+            if len(jobs) > 1 and self.host_threads > 1:
+                if self._pool is None:
+                    from concurrent.futures import ThreadPoolExecutor
+                    self._pool = ThreadPoolExecutor(self.host_threads)
+                list(self._pool.map(copy, jobs))
+            else:
+                for j in jobs:
+                    copy(j)
+            per_source.append((buf, rows, torch.from_numpy(seg)))
+        self.stats["gather_s"] += time.perf_counter() - t0
+        return per_source, torch.from_numpy(start), int(lens.max())
+
+    def _pooled_batch(self, pstore, items, slot, tag, copy_stream):
+        """[features, mask] of one batch of a PooledStore: stage, copy on the side stream, one xml_ingest_pool_rows launch."""
+        per_source, start, lmax = self._gather_pooled(pstore, items, slot, tag)
+        cuda = self.device.type == "cuda"
+        sources = []
+        if cuda:
+            cur = torch.cuda.current_stream(self.device)
+            with torch.cuda.stream(copy_stream):
+                dstart = start.to(self.device, non_blocking=True)
+                moved = [dstart]
+                for si, (host, rows, seg) in enumerate(per_source):
+                    dev = host[:max(rows, 1)].to(self.device, non_blocking=True)      # (no rows: one unread row, never NULL)
+                    dseg = seg.to(self.device, non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(copy_stream)
+                    self._slot_done[(tag, slot, si)] = done
+                    sources.append((dev, dseg, pstore.norms[si]))
+                    moved += [dev, dseg]
+            cur.wait_stream(copy_stream)
+            for t in moved:                      # allocated on the copy stream, consumed on the compute stream
+                t.record_stream(cur)
+        else:
+            dstart = start
+            for si, (host, rows, seg) in enumerate(per_source):
+                sources.append((host[:max(rows, 1)].clone(), seg, pstore.norms[si]))
+        for si, (host, rows, seg) in enumerate(per_source):
+            self.stats["rows"] += rows
+            self.stats["h2d_bytes"] += rows * pstore.stores[si].dim * host.element_size()
+        feat, mask = self.ops.ingest_pool_rows(sources, dstart, len(items), lmax, self.max_ctx_len, pool=pstore.pool,
+                                               normalize=self.norm[tag], eps=1e-5, out_dtype=self.feature_dtype)
+        return [feat, mask]
+
     def __iter__(self):
         cuda = self.device.type == "cuda"
         copy_stream = torch.cuda.Stream(self.device) if cuda else None
@@ -305,6 +516,9 @@ class ContextFeeder(object):
             for tag, store in (("video", self.vs), ("sub", self.ss)):
                 if store is None:
                     out += [None, None]
+                    continue
+                if isinstance(store, PooledStore):
+                    out += self._pooled_batch(store, names, bi & 1, tag, copy_stream)
                     continue
                 host, rows, start, lmax = self._gather(store, names, bi & 1, tag)
                 self.stats["rows"] += rows

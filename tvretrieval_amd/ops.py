@@ -317,6 +317,47 @@ def ingest_rows(src, row_start, n, lmax, max_len, normalize=True, eps=1e-5, out_
     return out, mask
 
 
+# ---- ingest from frame- / word-level stores (include/xmlhip_ingest_pool.h; ingest.PooledStore) ----------------------------------
+POOLS = {"max": 0, "mean": 1}         # XML_POOL_MAX / XML_POOL_MEAN
+
+
+def ingest_pool_rows(sources, row_start, n, lmax, max_len, pool="max", normalize=True, eps=1e-5, out_dtype=torch.float32,
+                     want_filled=False):
+    """Context collate with clip pooling on the device (xml_ingest_pool_rows): sources = 1 or 2 tuples (src, seg, norm) -- src
+    (rows_x, d_x) f16 / f32 rows FINER than clips (frames, words), seg (R, 2) int64 on the device: the half-open source-row range
+    of each of the batch's R = row_start[n] clip rows (an empty or out-of-range range gives a zero block), norm: x / (||x|| + eps)
+    on that source's pooled block.  row_start (n + 1,) int64 clip rows per video, back to back -> (features (n, lmax, sum d_x)
+    out_dtype [max or mean over each range, per-source norm, with normalize the norm of the whole row, zero padding], mask
+    (n, lmax)) and with want_filled also filled (n, lmax): 1 where a source had rows for the clip."""
+    if len(sources) not in (1, 2):
+        raise _lib.XmlHipError("ingest_pool_rows: 1 or 2 sources expected, got %d" % len(sources))
+    if pool not in POOLS:
+        raise _lib.XmlHipError("ingest_pool_rows: pool must be 'max' or 'mean', got %r" % (pool,))
+    _req(row_start, "row_start", torch.int64)
+    n, lmax = int(n), int(lmax)
+    if row_start.numel() != n + 1:
+        raise _lib.XmlHipError("ingest_pool_rows: row_start must hold n + 1 = %d entries" % (n + 1))
+    args, d = [], 0
+    for src, seg, norm in sources:
+        _req(src, "src"); _req(seg, "seg", torch.int64)
+        if src.dtype not in (torch.float32, torch.float16) or src.dim() != 2:
+            raise _lib.XmlHipError("ingest_pool_rows: src: expected (rows, d) float32 or float16")
+        if seg.dim() != 2 or seg.shape[1] != 2:
+            raise _lib.XmlHipError("ingest_pool_rows: seg: expected (R, 2) int64, one source-row range per clip row")
+        args += [_p(src), dt_of(src), int(src.shape[0]), int(src.shape[1]), _p(seg), int(bool(norm))]
+        d += int(src.shape[1])
+    if len(sources) == 1:
+        args += [None, 0, 0, 0, None, 0]
+    dev = sources[0][0].device
+    out = torch.empty((n, lmax, d), dtype=out_dtype, device=dev)
+    mask = torch.empty((n, lmax), dtype=torch.float32, device=dev)
+    filled = torch.empty((n, lmax), dtype=torch.float32, device=dev) if want_filled else None
+    check(_lib.load().xml_ingest_pool_rows(len(sources), *args, _p(row_start), _p(out), dt_of(out_dtype), _p(mask), _p(filled), n,
+                                           lmax, int(max_len), float(eps), int(bool(normalize)), POOLS[pool], _stream()),
+          "xml_ingest_pool_rows")
+    return (out, mask, filled) if want_filled else (out, mask)
+
+
 def gather_feature_rows(src, row_start, ids, lmax, max_len, item_of=None, normalize=True, eps=1e-5, tef=False,
                         out_dtype=torch.float32, out=None, mask_out=None, len_out=None, want_len=True):
     """One stream of a training batch from a device-resident ragged store (xml_gather_feature_rows): src (rows, d) f32 / f16,
