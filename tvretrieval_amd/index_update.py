@@ -764,6 +764,7 @@ class MutableCorpusIndex(CorpusIndex):
         self.chain_head = torch.arange(cap, dtype=torch.int32, device=dev)
         self.chain_next = torch.full((cap,), -1, dtype=torch.int32, device=dev)
         self.chain_offset = torch.zeros((cap,), dtype=torch.int32, device=dev)
+        self.fold = _inference.ChainFold(self)
 
     def _alloc_k6_image(self, m, shape, dtype, dev, plan=None):
         """The zero-filled K6 operand of modality m for (capacity, lpad, H) rows of `dtype`: the packed image of `plan` (a

@@ -28,16 +28,18 @@ and the sharded drivers call:
   moment_topk(st, ed, w, l_ref, min_l, max_l, n_out, summ=, pair_vid=, vid_len=)
   F16S                                                    the dtype sentinel of split-f16 models and rows
 The split-f16 exact mode (split_f16_rows, SplitRows, F16_UNIT_LOG2), explain_moments (span_evidence), the device-side result
-records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and searches on an index of parts (group_best_allow,
-best_part_rows, moments_decode(part_offset=)) and the updates of an index_update.MutableCorpusIndex (index_put_rows,
-index_clear_rows) and the searches and updates of one with chains of slots for long videos (index_set_chains,
-chain_best_allow, chain_best_rows) and the updates and searches of an exact-rank one (index_put_rows_exact,
-exact_certificate_dev, index_exact_bound; with the packed filter image index_put_rows_packed_exact; with chains of slots
-cand_best_part, chain_spread_allow, chain_members) and the subset views of
+records (moments_decode, nms_moments), vcmr_search_host (ingest_rows) and searches on an index whose long videos take several
+rows -- the drivers see index.fold and ask it alone: PartsFold for an index of parts (group_best_allow, best_part_rows),
+ChainFold for chains of slots (chain_best_allow, chain_best_rows; exact-rank: cand_best_part, chain_spread_allow,
+chain_members), both moments_decode(part_offset=) -- and the updates of an index_update.MutableCorpusIndex (index_put_rows,
+index_clear_rows; with chains index_set_chains) and of an exact-rank one (index_put_rows_exact, exact_certificate_dev,
+index_exact_bound; with the packed filter image index_put_rows_packed_exact) and the subset views of
 video_subset (index_gather_blocks; HIP only, a search with subset= refuses any other backend) and a ContextFeeder over
 ingest.PooledStore frame- / word-level stores (ingest_pool_rows; HIP only) call further entries of
 tvretrieval_amd.ops; a backend without them serves every search that does not ask for those.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -79,9 +81,12 @@ class CorpusIndex(object):
         # fetches the clip rows nor writes the (exactly zero) probabilities beyond it, K9 does not read them
         self.vlen = self.vlen_all = None
         self.ragged = False
+        # long videos held as several rows: None (every row is a whole video), a PartsFold or a ChainFold.  The search drivers
+        # ask the fold; the attributes of the two forms below serve ops.chain_*, the update path, subset views and tools.
+        self.fold = None
         # long videos indexed in parts (build_corpus_index(parts=)): the device ingest.PartTable; rows
-        # of the index are then PARTS (n_videos keeps meaning index rows) and n_source_videos the videos they fold back into
-        self.parts = None
+        # of the index are then PARTS (n_videos keeps meaning index rows) and n_source_videos the videos they fold back into.
+        # index.parts is the table the PartsFold holds -- one fact, kept once (the property below)
         self.n_source_videos = self.n_videos
         # an index that takes updates (index_update.MutableCorpusIndex): rows are SLOTS, live the
         # (1, ceil(n_videos / 32)) int32 words of the occupied ones -- every search sees live AND video_allow -- and slot_ids
@@ -92,6 +97,19 @@ class CorpusIndex(object):
         # slot's part in its video.  A video's number -- in top_videos, in a caller's video_allow -- is its HEAD slot.
         self.chain_head = self.chain_next = self.chain_offset = None
         self.part_overlap = self.max_parts = None
+
+    @property
+    def parts(self):
+        """The device PartTable of a parts index, None on every other index."""
+        return self.fold._parts if isinstance(self.fold, PartsFold) else None
+
+    @parts.setter
+    def parts(self, table):
+        """Only cleared: index.parts = None on a (copy of a) parts index leaves an index of plain rows, each a video."""
+        if table is not None:
+            raise AttributeError("index.parts is made by build_corpus_index(parts=); it can only be set to None")
+        if self.parts is not None:
+            self.fold = None
 
     def set_valid_lengths(self):
         """Per-video valid length from the masks (one small device pass + one host read at build time)."""
@@ -364,7 +382,7 @@ def build_corpus_index(model, context_batches, ops=hip_ops, keep_raw=False, vide
         if index.l_ref > parts.max_ctx_len:
             raise ValueError("build_corpus_index: rows of %d clips, but the part table was planned for max_ctx_len = %d"
                              % (index.l_ref, parts.max_ctx_len))
-        index.parts = parts.to(index.device)
+        index.fold = PartsFold(parts.to(index.device))          # (index.parts reads the table from it)
         index.n_source_videos = parts.n_videos
     return index
 
@@ -564,9 +582,9 @@ def pack_video_allow(allowed):
 
 
 def _check_video_allow(video_allow, index, nq):
-    """video_allow of a search over index for nq queries: int32 words on the index's device, 1 or nq rows.  On a parts index
-    the bits number SOURCE videos."""
-    nv = index.n_source_videos if index.parts is not None else index.n_videos
+    """video_allow of a search over index for nq queries: int32 words on the index's device, 1 or nq rows.  On an index with a
+    fold the bits number the fold's videos (a parts index: SOURCE videos)."""
+    nv = index.fold.n_videos if index.fold is not None else index.n_videos
     nw = (nv + 31) // 32
     if not torch.is_tensor(video_allow) or video_allow.dtype != torch.int32 or video_allow.dim() != 2:
         raise ValueError("video_allow must be a 2-D int32 tensor of bit words (pack_video_allow)")
@@ -576,33 +594,106 @@ def _check_video_allow(video_allow, index, nq):
     return video_allow
 
 
-def _parts_meta2vid(index, meta2vid):
-    """K10's table of a parts index, index row -> the caller's id of the source video (PartTable.meta2vid), composed once per
-    ids tensor and kept on the index: the same tensor, unchanged since (same object, same version), is served from there."""
-    if meta2vid is None or not torch.is_tensor(meta2vid):
-        return index.parts.meta2vid(meta2vid)
-    kept = index.__dict__.get("_parts_meta2vid")
-    if kept is None or kept[0] is not meta2vid or kept[1] != meta2vid._version:
-        kept = (meta2vid, meta2vid._version, index.parts.meta2vid(meta2vid))
-        index._parts_meta2vid = kept
-    return kept[2]
+class PartsFold(object):
+    """index.fold of a parts index (build_corpus_index(parts=)): the rows of a long video are the CSR
+    ranges of the device ingest.PartTable.  A fold is what the search drivers know about long videos held as several rows:
+      overlap, n_videos (the bits a caller's video_allow must cover), part_offset (K10's operand: first clip of each row)
+      best_allow(ops, scores, allow)  (rows, Nv) scores -> allow words over index rows: each allowed video's best part
+      best_rows(ops, scores, video)   a video per row -> the index row of its best part
+      video_of(top_i)                 listed index rows -> their videos (out["top_videos"])
+      meta2vid(meta2vid)              a caller's video -> id table -> K10's index row -> id table"""
+
+    def __init__(self, parts):
+        self._parts, self._meta2vid = parts, None
+        self.overlap, self.n_videos, self.part_offset = parts.overlap, parts.n_videos, parts.part_offset
+
+    def best_allow(self, ops, scores, allow):
+        return ops.group_best_allow(scores, self._parts, allow)
+
+    def best_rows(self, ops, scores, video):
+        return ops.best_part_rows(scores, self._parts, video)
+
+    def video_of(self, top_i):
+        return torch.where(top_i >= 0, self._parts.part_video[top_i.clamp_min(0).long()], top_i)
+
+    def meta2vid(self, meta2vid):
+        """PartTable.meta2vid, composed once per ids tensor and kept: the same tensor, unchanged since (same object, same
+        version), is served from here."""
+        if meta2vid is None or not torch.is_tensor(meta2vid):
+            return self._parts.meta2vid(meta2vid)
+        kept = self._meta2vid
+        if kept is None or kept[0] is not meta2vid or kept[1] != meta2vid._version:
+            kept = self._meta2vid = (meta2vid, meta2vid._version, self._parts.meta2vid(meta2vid))
+        return kept[2]
+
+
+class ChainFold(object):
+    """index.fold of an index that takes updates and holds long videos as chains of slots (MutableCorpusIndex.create(...,
+    part_overlap=O)): PartsFold's members over the index's chain tables, which updates rewrite in
+    place -- a video's number is its HEAD slot, meta2vid is per slot already.  The last three members serve the exact-rank
+    chain (section 20g), which folds re-scored candidate lists, not a score matrix; only this fold has them."""
+
+    def __init__(self, index):
+        self._index = index       # (the tables are allocated once: the operands may be bound here)
+        self.overlap, self.n_videos, self.part_offset = index.part_overlap, index.n_videos, index.chain_offset
+
+    def best_allow(self, ops, scores, allow):
+        return ops.chain_best_allow(scores, self._index, allow)
+
+    def best_rows(self, ops, scores, video):
+        return ops.chain_best_rows(scores, self._index, video)
+
+    def video_of(self, top_i):
+        return torch.where(top_i >= 0, self._index.chain_head[top_i.clamp_min(0).long()], top_i)
+
+    def meta2vid(self, meta2vid):
+        return meta2vid
+
+    def slot_allow(self, ops, allow):
+        """The allow words of an exact-rank search: (per-slot words for the selections that propose candidate SLOTS, head-bit
+        words for the fold of a full row).  allow is what stage_video_topk hands on: the live words themselves -- they carry
+        every bit of a chain, nothing is launched -- or a caller's mask ANDed with them, whose bits number videos by their head
+        slot: ops.chain_spread_allow gives every slot its head's bit."""
+        live = self._index.live
+        if allow is None or allow is live:
+            return live, live
+        return ops.chain_spread_allow(allow, self._index) & live, allow
+
+    def fold_candidates(self, ops, scores, ids):
+        """Candidate lists of SLOTS -> the same lists with every video reduced to its best candidate part (the others
+        (-inf, -1))."""
+        return ops.cand_best_part(scores, ids, self._index.chain_head, self._index.chain_offset)
+
+    def members(self, ops, video):
+        return ops.chain_members(self._index, video)
 
 
 def _check_parts_search(index, max_pred_l, external_top=None, pad_tail=False):
-    """What a search on a parts index cannot do, each with its reason (an index with chains of slots: the same)."""
-    overlap = index.parts.overlap if index.parts is not None else index.part_overlap
+    """What a search on an index with a fold cannot do, each with its reason."""
+    fold = index.fold
     if external_top is not None:
         raise ValueError("external_top on a parts index: a caller's lists name index rows and would bypass the fold that lets "
                          "only the best part of a video compete (rank the source videos with the index instead)")
-    if index.exact is not None and index.chain_head is None:     # (with chains the fold runs on the re-scored candidate lists)
+    if index.exact is not None and not hasattr(fold, "fold_candidates"):     # (no fold of re-scored candidate lists)
         raise ValueError("a parts index cannot be an exact-rank index (exact_filter=True): no f32 score matrix exists to "
                          "take the best part of a video from")
-    if int(max_pred_l) > overlap:
+    if int(max_pred_l) > fold.overlap:
         raise ValueError("max_pred_l = %d exceeds the part overlap of %d clips: a moment of that length need not lie inside "
-                         "one part (plan_parts(overlap=) must be >= max_pred_l)" % (max_pred_l, overlap))
+                         "one part (plan_parts(overlap=) must be >= max_pred_l)" % (max_pred_l, fold.overlap))
     if pad_tail:
         raise ValueError("pad_tail=True on a parts index: the reference-shaped tail would have to invent rows in the video "
                          "slots that stay empty once every video is counted once")
+
+
+def _decode_operands(index, meta2vid):
+    """K10's (meta2vid table, keywords) for this index: the slot -> id table of an index that takes updates unless the
+    caller has one; with a fold, the fold's table and the first clip of every row, so that records carry the video's id and
+    whole-video times."""
+    if meta2vid is None and index.live is not None:
+        meta2vid = index.slot_ids
+    if index.fold is None:
+        return meta2vid, {}
+    return index.fold.meta2vid(meta2vid), dict(part_offset=index.fold.part_offset)
 
 
 def _allow_rows(video_allow, rows):
@@ -612,19 +703,52 @@ def _allow_rows(video_allow, rows):
     return video_allow.index_select(0, rows).contiguous()
 
 
-def _exact_chain_allow(index, video_allow, ops):
-    """The allow words of an exact-rank search on an index with chains: (per-slot words for the selections that propose
-    candidate SLOTS, head-bit words for the fold of a full row).  video_allow is what stage_video_topk hands on: the live
-    words themselves -- they carry every bit of a chain, nothing is launched -- or a caller's mask ANDed with them, whose bits
-    number videos by their head slot: ops.chain_spread_allow gives every slot its head's bit."""
-    if video_allow is None or video_allow is index.live:
-        return index.live, index.live
-    return ops.chain_spread_allow(video_allow, index) & index.live, video_allow
+def _exact_allow(index, k, video_allow, ops):
+    """How every exact-rank search begins: the k check, then the allow words.  -> t with t.fold (index.fold: None or the
+    ChainFold), t.allow (the words of every selection over corpus columns; per slot with chains) and t.head_allow (with chains:
+    the head-bit words a full row is folded under)."""
+    ex = index.exact
+    if k > min(ex.n_candidates, index.n_videos):
+        raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
+                         "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
+    t = types.SimpleNamespace(fold=index.fold, allow=video_allow, head_allow=video_allow)
+    if t.fold is not None:
+        t.allow, t.head_allow = t.fold.slot_allow(ops, video_allow)
+    return t
 
 
-def _exact_chain_fold(index, ops, scores, ids):
-    """Candidate lists of SLOTS -> the same lists with every video reduced to its best candidate part (the others (-inf, -1))."""
-    return ops.cand_best_part(scores, ids, index.chain_head, index.chain_offset)
+def _exact_first_tier(t, index, q_filter, q_rescore, eq, k, alpha, ops, subset, split):
+    """What the two exact-rank modes share behind their query preparation (per modality: the FILTER operand, the re-score
+    operand, the rounding-error norms): K6 over the filter image, K8's M candidates, their re-score, the fold of an index with
+    chains, K8 again for the top-k, the certificate, the info dict.  Returns (top_w (Nq, k) -- the raw re-scored values --,
+    top_i, info) and leaves in t what the later tiers read: filt, rows_c, masks, fail, thr, n_fail, outside."""
+    ex, mods = index.exact, index.modalities
+    t.masks = [index.mask[m] for m in mods]
+    t.filt = _k6(index, q_filter, ops, subset=subset)
+    m_c = min(ex.n_candidates, index.n_videos)
+    cand_s, cand_i = ops.topk_rows(t.filt, m_c, alpha=0.0, allow=t.allow)
+    t.rows_c = [ex.feat1n_f32[m] for m in mods]                  # f32 rows / SplitRows (Nv, lpad, H)
+    cand_r = ops.q2c_rescore(q_rescore, t.rows_c, t.masks, cand_i)
+    fold_r, fold_i = t.fold.fold_candidates(ops, cand_r, cand_i) if t.fold is not None else (cand_r, cand_i)
+    top_w, top_i = ops.topk_rows(fold_r, k, alpha=0.0, idx_in=fold_i)
+    t.outside = index.n_videos > m_c
+    t.fail, eps, t.thr, t.n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, q_filter[0].shape[1], alpha,
+                                                      t.outside, split)
+    info = dict(fail=t.fail, eps=eps, q2c_filter=t.filt, cand_indices=cand_i, cand_filter=cand_s, cand_scores=cand_r,
+                n_candidates=m_c, n_full_rows=0)
+    if t.fold is not None:
+        info.update(cand_folded_indices=fold_i, cand_folded_scores=fold_r, q_rescore=q_rescore)
+    return top_w, top_i, info
+
+
+def _exact_full_rows(t, scores, rows, k, alpha, ops):
+    """The last tier of both modes: scores (len(rows), Nv), the f32-grade scores of EVERY video for the query rows `rows` ->
+    their (top_w = exp(alpha s), top_i); on an index with chains the row is folded (the fold of index_parts.hip) under the
+    head-bit words."""
+    row_allow = _allow_rows(t.allow, rows)
+    if t.fold is not None:
+        row_allow = t.fold.best_allow(ops, scores, _allow_rows(t.head_allow, rows))
+    return ops.topk_rows(scores, k, alpha=alpha, allow=row_allow)
 
 
 def stage_exact_topk(index, qvec, k, alpha, ops=hip_ops, defer_check=False, video_allow=None, subset=None):
@@ -652,24 +776,15 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
     video_allow (pack_video_allow's words, 1 or Nq rows): every selection over corpus columns -- the candidate K8, the second
     tier's select_ge_rows, the third tier's full row -- takes the mask; candidate slots a short row leaves empty are id -1,
     which the re-score turns into -inf.  The certificate is unchanged (conservative: a -inf at the candidates' end passes).
-    An index with chains of slots (index.chain_head): the lists are of VIDEOS, each ranked by its best
-    part, top_i the slots of those parts.  Candidates are proposed as slots under per-slot allow words (_exact_chain_allow);
-    every re-scored list is folded (ops.cand_best_part) before its top-k, so T_k is the k-th value over k DISTINCT videos and
-    the certificate holds unchanged; the third tier's full row is folded by ops.chain_best_allow under the head-bit words.
+    An index with chains of slots (index.fold a ChainFold): the lists are of VIDEOS, each ranked by its
+    best part, top_i the slots of those parts.  Candidates are proposed as slots under per-slot allow words (fold.slot_allow);
+    every re-scored list is folded (fold.fold_candidates) before its top-k, so T_k is the k-th value over k DISTINCT videos and
+    the certificate holds unchanged; the third tier's full row is folded by fold.best_allow under the head-bit words.
     info then also holds cand_folded_indices / cand_folded_scores and q_rescore (the query operands of ops.q2c_rescore).
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
-    ex = index.exact
-    mods = index.modalities
-    if k > min(ex.n_candidates, index.n_videos):
-        raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
-                         "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
-    chains = index.chain_head is not None
-    head_allow = video_allow
-    if chains:
-        video_allow, head_allow = _exact_chain_allow(index, video_allow, ops)
-    masks = [index.mask[m] for m in mods]
+    t = _exact_allow(index, k, video_allow, ops)
     q_sr, q_hi, eq = [], [], []
-    for m in mods:
+    for m in index.modalities:
         q = qvec[m].contiguous()
         if q.dtype != torch.float32:
             raise ValueError("exact-rank mode needs f32 query vectors (an f32 / ops.F16S model)")
@@ -680,21 +795,10 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
             sr = ops.split_f16_rows(qn, ops.F16_UNIT_LOG2)
             hi, e = ops.round_bf16_rows_err(qn)
         q_sr.append(sr), q_hi.append(hi), eq.append(e)
-    nq, hidden = q_hi[0].shape
-    filt = _k6(index, q_hi, ops, subset=subset)
-    m_c = min(ex.n_candidates, index.n_videos)
-    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
-    rows_c = [ex.feat1n_f32[m] for m in mods]                    # SplitRows (Nv, lpad, H)
-    cand_r = ops.q2c_rescore(q_sr, rows_c, masks, cand_i)
-    fold_r, fold_i = _exact_chain_fold(index, ops, cand_r, cand_i) if chains else (cand_r, cand_i)
-    top_w, top_i = ops.topk_rows(fold_r, k, alpha=0.0, idx_in=fold_i)
-    outside = index.n_videos > m_c
-    fail, eps, thr_all, n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, hidden, alpha, outside, True)
-    info = dict(fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s, cand_scores=cand_r,
-                n_candidates=m_c, n_fail_dev=n_fail, n_full_rows=0, overflow_dev=None)
-    if chains:
-        info.update(cand_folded_indices=fold_i, cand_folded_scores=fold_r, q_rescore=q_sr)
-    if outside:
+    top_w, top_i, info = _exact_first_tier(t, index, q_hi, q_sr, eq, k, alpha, ops, subset, True)
+    ex, nq, fail, n_fail = index.exact, top_w.shape[0], t.fail, t.n_fail
+    info.update(n_fail_dev=n_fail, overflow_dev=None)
+    if t.outside:
         r_cap = min(nq, ex.tier2_rows if ex.tier2_rows is not None else max(32, nq // 64))
         c_cap = min(int(ex.tier2_cap), index.n_videos)
         if c_cap < k:
@@ -702,14 +806,14 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
         order = torch.argsort(fail, descending=True, stable=True)[:r_cap]          # failing queries first; a permutation
         is_fail = fail.index_select(0, order) != 0
         inf_ = torch.full((), float("inf"), device=fail.device)
-        thr = torch.where(is_fail, thr_all.index_select(0, order), inf_).contiguous()      # passing slots select nothing
-        cand2, cnt2 = ops.select_ge_rows(filt.index_select(0, order).contiguous(), thr, c_cap,
-                                         allow=_allow_rows(video_allow, order))
+        thr = torch.where(is_fail, t.thr.index_select(0, order), inf_).contiguous()        # passing slots select nothing
+        cand2, cnt2 = ops.select_ge_rows(t.filt.index_select(0, order).contiguous(), thr, c_cap,
+                                         allow=_allow_rows(t.allow, order))
         q_sub = [sr[order] for sr in q_sr]
         q_sub = [ops.SplitRows(sr.data.contiguous(), sr.inv.contiguous()) for sr in q_sub]
-        full = ops.q2c_rescore(q_sub, rows_c, masks, cand2)
-        if chains:
-            full, cand2 = _exact_chain_fold(index, ops, full, cand2)
+        full = ops.q2c_rescore(q_sub, t.rows_c, t.masks, cand2)
+        if t.fold is not None:
+            full, cand2 = t.fold.fold_candidates(ops, full, cand2)
         # slots of PASSING queries selected nothing: their rows are c_cap times -inf, and the top-k of an all-tied row with
         # payloads takes K8's one-block-minimum-per-element path (0.46 ms for 156 such rows -- more than the second tier's
         # re-score).  Their results are discarded below; a ramp of distinct values keeps them on the fast path.
@@ -732,11 +836,8 @@ def stage_exact_topk_f16s(index, qvec, k, alpha, ops=hip_ops, defer_check=False,
                     rows = bad[b0:b0 + 16]
                     qs = [ops.SplitRows(sr.data.index_select(0, rows).contiguous(), sr.inv.index_select(0, rows).contiguous())
                           for sr in q_sr]
-                    allv = ops.q2c_rescore(qs, rows_c, masks, every.repeat(rows.numel(), 1).contiguous())
-                    row_allow = _allow_rows(video_allow, rows)
-                    if chains:       # the fold of index_parts.hip on a full f32-grade row, under the head-bit words
-                        row_allow = ops.chain_best_allow(allv, index, _allow_rows(head_allow, rows))
-                    fw, fi = ops.topk_rows(allv, k, alpha=alpha, allow=row_allow)
+                    allv = ops.q2c_rescore(qs, t.rows_c, t.masks, every.repeat(rows.numel(), 1).contiguous())
+                    fw, fi = _exact_full_rows(t, allv, rows, k, alpha, ops)
                     top_w.index_copy_(0, rows, fw)
                     top_i.index_copy_(0, rows, fi)
                 info["n_full_rows"] = int(bad.numel())
@@ -756,65 +857,40 @@ def stage_exact_topk_f32(index, qvec, k, alpha, ops=hip_ops, video_allow=None, s
          too close together for that (> EXACT_TIER2_CAP such videos), a full f32 K6 row (the f32 path itself).
     video_allow: as in stage_exact_topk_f16s -- the candidate K8, both select_ge_rows calls and the fallback's full row.
     An index with chains of slots: as in stage_exact_topk_f16s -- every re-scored list is folded before its top-k, the
-    fallback's full f32 row by ops.chain_best_allow.
+    fallback's full f32 row by fold.best_allow.
     Returns (top_w = exp(alpha s) (Nq, k) f32, top_i (Nq, k) int32, info dict)."""
-    ex = index.exact
-    mods = index.modalities
-    if k > min(ex.n_candidates, index.n_videos):
-        raise ValueError("exact-rank mode: top-%d videos asked of %d candidates per query (ExactFilter.n_candidates; K8 "
-                         "proposes at most 256) -- lower max_vcmr_video or raise n_candidates" % (k, ex.n_candidates))
-    chains = index.chain_head is not None
-    head_allow = video_allow
-    if chains:
-        video_allow, head_allow = _exact_chain_allow(index, video_allow, ops)
-    masks = [index.mask[m] for m in mods]
-    qn = [ops.l2norm_rows(qvec[m].contiguous()) for m in mods]
+    t = _exact_allow(index, k, video_allow, ops)
+    qn = [ops.l2norm_rows(qvec[m].contiguous()) for m in index.modalities]
     if qn[0].dtype != torch.float32:
         raise ValueError("exact-rank mode needs f32 query vectors (an f32 model)")
     qb, eq = [], []
     for q in qn:
         b, e = ops.round_bf16_rows_err(q)
         qb.append(b), eq.append(e)
-    filt = _k6(index, qb, ops, subset=subset)
-    m_c = min(ex.n_candidates, index.n_videos)
-    cand_s, cand_i = ops.topk_rows(filt, m_c, alpha=0.0, allow=video_allow)
-    f32rows = [ex.feat1n_f32[m] for m in mods]
-    cand_r = ops.q2c_rescore(qn, f32rows, masks, cand_i)
-    fold_r, fold_i = _exact_chain_fold(index, ops, cand_r, cand_i) if chains else (cand_r, cand_i)
-    top_w, top_i = ops.topk_rows(fold_r, k, alpha=0.0, idx_in=fold_i)
-    fail, eps, thr_all, n_fail = _exact_certificate(ex, mods, ops, cand_s, top_w, eq, qn[0].shape[1], alpha,
-                                                    index.n_videos > m_c, False)
-    nf = int(n_fail.item())        # (host sync: the launch shapes below depend on it)
-    n_full = 0
+    top_w, top_i, info = _exact_first_tier(t, index, qb, qn, eq, k, alpha, ops, subset, False)
+    nf = int(t.n_fail.item())        # (host sync: the launch shapes below depend on it)
+    info["n_fail"] = nf
     if nf:
-        rows = torch.nonzero(fail, as_tuple=False).reshape(-1)
+        rows = torch.nonzero(t.fail, as_tuple=False).reshape(-1)
         qsub = [q.index_select(0, rows).contiguous() for q in qn]
         # Second tier: T_k (the k-th re-scored value) is a LOWER bound of the final k-th score, so only videos whose filter
         # score reaches T_k - eps can still enter: usually a few dozen more than M.  Re-score exactly those.
-        thr = thr_all.index_select(0, rows).contiguous()
-        frows = filt.index_select(0, rows).contiguous()
-        cap = int(ops.select_ge_rows(frows, thr, allow=_allow_rows(video_allow, rows)).max())
-        if video_allow is not None:
+        thr = t.thr.index_select(0, rows).contiguous()
+        frows = t.filt.index_select(0, rows).contiguous()
+        cap = int(ops.select_ge_rows(frows, thr, allow=_allow_rows(t.allow, rows)).max())
+        if t.allow is not None:
             cap = max(cap, k)          # (rows with fewer than k allowed videos: the list is filled up with id -1 = -inf)
         if cap <= EXACT_TIER2_CAP:
-            cand2, _ = ops.select_ge_rows(frows, thr, cap, allow=_allow_rows(video_allow, rows))
-            full = ops.q2c_rescore(qsub, f32rows, masks, cand2)                       # (-inf where a row has fewer candidates)
-            if chains:
-                full, cand2 = _exact_chain_fold(index, ops, full, cand2)
+            cand2, _ = ops.select_ge_rows(frows, thr, cap, allow=_allow_rows(t.allow, rows))
+            full = ops.q2c_rescore(qsub, t.rows_c, t.masks, cand2)                    # (-inf where a row has fewer candidates)
+            if t.fold is not None:
+                full, cand2 = t.fold.fold_candidates(ops, full, cand2)
             fw, fi = ops.topk_rows(full, k, alpha=alpha, idx_in=cand2)
         else:   # scores so close together that the filter cannot separate them: the f32 K6 row itself
-            n_full = nf
-            full = ops.q2c_scores_fused(qsub, f32rows, masks)
-            row_allow = _allow_rows(video_allow, rows)
-            if chains:           # the fold of index_parts.hip on the full f32 row, under the head-bit words
-                row_allow = ops.chain_best_allow(full, index, _allow_rows(head_allow, rows))
-            fw, fi = ops.topk_rows(full, k, alpha=alpha, allow=row_allow)
+            info["n_full_rows"] = nf
+            fw, fi = _exact_full_rows(t, ops.q2c_scores_fused(qsub, t.rows_c, t.masks), rows, k, alpha, ops)
         top_w.index_copy_(0, rows, fw)
         top_i.index_copy_(0, rows, fi)
-    info = dict(n_fail=nf, n_full_rows=n_full, fail=fail, eps=eps, q2c_filter=filt, cand_indices=cand_i, cand_filter=cand_s,
-                cand_scores=cand_r, n_candidates=m_c)
-    if chains:
-        info.update(cand_folded_indices=fold_i, cand_folded_scores=fold_r, q_rescore=qn)
     return top_w, top_i, info
 
 
@@ -954,39 +1030,25 @@ def stage_video_topk(model, index, qvec, max_vcmr_video=100, q2c_alpha=20.0, ops
         video_allow = _subset_allow(subset, video_allow)
     if index.live is not None and external_top is None:
         video_allow = index.live if video_allow is None else video_allow[:, :index.live.shape[1]] & index.live
-    if index.chain_head is not None and index.exact is not None:
-        # chains on an exact-rank index: no f32 matrix to fold -- the exact-rank chain folds its candidate lists itself
+    if index.fold is not None:
         _check_parts_search(index, 0, external_top)
-        k = min(max_vcmr_video, index.n_videos)
-        top_w, top_i, exact = stage_exact_topk(index, qvec, k, q2c_alpha, ops, bool(defer_exact_check), video_allow)
-        return None, top_w, top_i, exact
-    if index.chain_head is not None:
-        _check_parts_search(index, 0, external_top)
-        q2c = stage_q2c(index, qvec, ops)
-        best = ops.chain_best_allow(q2c, index, video_allow)
-        top_w, top_i = ops.topk_rows(q2c, min(max_vcmr_video, index.n_videos), alpha=q2c_alpha, allow=best)
-        return q2c, top_w, top_i, None
-    if index.parts is not None:
-        # long videos in parts: K6 scores every part, the fold keeps each video's best part (and the caller's mask, which
-        # numbers source videos), K8 ranks those -- the restricted search over the index rows, one row per video
-        _check_parts_search(index, 0, external_top)
-        q2c = stage_q2c(index, qvec, ops)
-        best = ops.group_best_allow(q2c, index.parts, video_allow)
-        top_w, top_i = ops.topk_rows(q2c, min(max_vcmr_video, index.n_videos), alpha=q2c_alpha, allow=best)
-        return q2c, top_w, top_i, None
-    if external_top is None and index.exact is not None:
+    k = min(max_vcmr_video, index.n_videos)
+    if external_top is not None:    # external video-retrieval results replace K6/K8 (xml/inference.py:349-355):
+        q2c = None                  # (meta idx int32, exp(alpha*s))
+        top_i, top_w = external_top
+    elif index.exact is not None:
         q2c = None          # (the f32 (Nq, Nv) matrix is never formed; exact["q2c_filter"] is the bf16 pass's)
         # defer_exact_check (split-f16 exact mode): no host read-back inside the pass; out["exact"]["overflow_dev"] (device
-        # bool, None when every video is a candidate) says whether the on-device second tier's capacity was exceeded
-        top_w, top_i, exact = stage_exact_topk(index, qvec, min(max_vcmr_video, index.n_videos), q2c_alpha, ops,
-                                               bool(defer_exact_check), video_allow, subset)
-    elif external_top is None:
+        # bool, None when every video is a candidate) says whether the on-device second tier's capacity was exceeded.
+        # With a fold (chains) there is no f32 matrix to fold: the exact-rank chain folds its candidate lists itself
+        top_w, top_i, exact = stage_exact_topk(index, qvec, k, q2c_alpha, ops, bool(defer_exact_check), video_allow, subset)
+    else:
         q2c = stage_q2c(index, qvec, ops, subset)
-        k = min(max_vcmr_video, index.n_videos)
+        if index.fold is not None:
+            # long videos in several rows: K6 scored every row, the fold keeps each video's best part (and the caller's mask,
+            # which numbers videos as the fold does), K8 ranks those -- the restricted search over the rows, one per video
+            video_allow = index.fold.best_allow(ops, q2c, video_allow)
         top_w, top_i = ops.topk_rows(q2c, k, alpha=q2c_alpha, allow=video_allow)
-    else:   # external video-retrieval results replace K6/K8 (xml/inference.py:349-355): (meta idx int32, exp(alpha*s))
-        q2c = None
-        top_i, top_w = external_top
     return q2c, top_w, top_i, exact
 
 
@@ -1058,21 +1120,13 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     if video_allow is not None and pad_tail:
         raise ValueError("video_allow and pad_tail=True exclude each other: the reference-shaped tail would have to invent "
                          "rows in the empty video slots of a restricted list")
-    parts = index.parts
-    pkw = {}
-    if index.live is not None:
-        if pad_tail:
-            raise ValueError("pad_tail=True on an index that takes updates: the reference-shaped tail would have to invent rows "
-                             "in the video slots that stay empty when fewer than K videos are live")
-        if meta2vid is None:
-            meta2vid = index.slot_ids
-    chains = index.chain_head is not None
-    if chains:      # (meta2vid: slot -> id, the same for every slot of a chain -- slot_ids unless the caller has a table)
+    fold = index.fold
+    if index.live is not None and pad_tail:
+        raise ValueError("pad_tail=True on an index that takes updates: the reference-shaped tail would have to invent rows "
+                         "in the video slots that stay empty when fewer than K videos are live")
+    if fold is not None:
         _check_parts_search(index, max_pred_l, external_top, pad_tail)
-        pkw = dict(part_offset=index.chain_offset)
-    if parts is not None:
-        _check_parts_search(index, max_pred_l, external_top, pad_tail)
-        meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=parts.part_offset)
+    meta2vid, pkw = _decode_operands(index, meta2vid)
     qvec = stage_query_vectors(model, query_feat, query_mask, n_valid_tokens)
     forked = fork_query_linears(model, index, qvec, ops) if not K7_SUMMARIES else None
     q2c, top_w, top_i, exact = stage_video_topk(model, index, qvec, max_vcmr_video, q2c_alpha, ops, external_top,
@@ -1085,10 +1139,8 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
     out = dict(q2c=q2c, top_scores=top_w, top_indices=top_i, flat_scores=fs, flat_indices=fi)
     if exact is not None:
         out["exact"] = exact
-    if parts is not None:       # (index plumbing: the source video of every listed row, -1 in the empty slots)
-        out["top_videos"] = torch.where(top_i >= 0, parts.part_video[top_i.clamp_min(0).long()], top_i)
-    if chains:                  # (the head slot of every listed slot, -1 in the empty slots)
-        out["top_videos"] = torch.where(top_i >= 0, index.chain_head[top_i.clamp_min(0).long()], top_i)
+    if fold is not None:        # (the source video / the head slot of every listed row, -1 in the empty slots)
+        out["top_videos"] = fold.video_of(top_i)
     if nms_thd is not None:
         rec, cnt = ops.moments_decode(fs, flat=fi, top_idx=top_i, meta2vid=meta2vid, l_ref=index.l_ref,
                                       clip_length=clip_length, seconds=True, **pkw)
@@ -1096,20 +1148,17 @@ def vcmr_search(model, index, query_feat, query_mask, max_vcmr_video=100, max_be
         out.update(records=rec, record_count=cnt, nms_records=nrec, nms_index=nidx, nms_count=ncnt)
     if svmr_video is not None:
         pv = svmr_video.to(torch.int32).reshape(-1).contiguous()
-        if parts is not None:       # a SOURCE video per query: its best part for that query stands for it (-1: unknown id)
-            pv = ops.best_part_rows(q2c, parts, pv)
-            out["svmr_rows"] = pv
-        if chains and index.exact is not None:
+        if fold is not None and index.exact is not None:
             # no q2c matrix: the slots of each video, re-scored with the query operands the exact-rank chain made, folded to
             # the best part.  The fold leaves one slot per row (the head for a chain of nothing but -inf, where a top-1 by
             # value would find an empty list): the largest id is that slot, -1 for a slot outside the index.
-            members = ops.chain_members(index, pv)
+            members = fold.members(ops, pv)
             sc = ops.q2c_rescore(exact["q_rescore"], [index.exact.feat1n_f32[m] for m in index.modalities],
                                  [index.mask[m] for m in index.modalities], members)
-            pv = _exact_chain_fold(index, ops, sc, members)[1].amax(1).to(torch.int32)
-            out["svmr_rows"] = pv
-        elif chains:                # any slot of a video: the slot of its best part for that query (-1: outside the index)
-            pv = ops.chain_best_rows(q2c, index, pv)
+            pv = fold.fold_candidates(ops, sc, members)[1].amax(1).to(torch.int32)
+        elif fold is not None:      # a video per query (a SOURCE video; any slot of a chain): the index row of its best part
+            pv = fold.best_rows(ops, q2c, pv)      # for that query stands for it (-1: unknown id / outside the index)
+        if fold is not None:
             out["svmr_rows"] = pv
         pv = pv.reshape(-1, 1)
         st1, ed1 = stage_span_probs(model, index, qvec, pv, ops, q_lin=q_lin)
@@ -1324,7 +1373,7 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
     dev = next(model.parameters()).device
     ragged = row_start is not None
     nq = (row_start.numel() - 1) if ragged else query_feat.shape[0]
-    if index.parts is not None or index.chain_head is not None:
+    if index.fold is not None:
         _check_parts_search(index, max_pred_l, None, pad_tail)
     if index.live is not None and pad_tail:
         raise ValueError("pad_tail=True on an index that takes updates (see vcmr_search)")
@@ -1359,13 +1408,9 @@ def vcmr_search_host(model, index, query_feat, query_mask=None, row_start=None, 
         buffers.last_done.synchronize()                  # (the pass before the previous one: normally long finished)
     main = torch.cuda.current_stream(dev)
     side = buffers.copy_stream
-    pkw = {}
-    if index.parts is not None:      # records name source videos, in whole-video time (see vcmr_search)
-        meta2vid, pkw = _parts_meta2vid(index, meta2vid), dict(part_offset=index.parts.part_offset)
-    elif meta2vid is None:       # (an index that takes updates: the records carry the caller's ids of the slots)
-        meta2vid = index.slot_ids if index.slot_ids is not None else torch.arange(index.n_videos, dtype=torch.int32, device=dev)
-    if index.chain_head is not None:     # chains of slots: whole-video times (every slot of a chain carries the video's id)
-        pkw = dict(part_offset=index.chain_offset)
+    meta2vid, pkw = _decode_operands(index, meta2vid)       # (with a fold: the video's id, whole-video times; see vcmr_search)
+    if meta2vid is None:
+        meta2vid = torch.arange(index.n_videos, dtype=torch.int32, device=dev)
     copied, freed = [None, None], buffers.freed
     ev_h2d = []
 
@@ -1489,7 +1534,7 @@ class GraphedVcmrSearch(object):
             raise ValueError("GraphedVcmrSearch: video_allow_rows must be None, 1 or nq = %d, got %r" % (nq, video_allow_rows))
         if "video_allow" in search_kwargs:
             raise ValueError("GraphedVcmrSearch: pass video_allow_rows= here and the mask itself to every call")
-        if getattr(index, "parts", None) is not None or getattr(index, "chain_head", None) is not None:
+        if index.fold is not None:
             raise ValueError("GraphedVcmrSearch: a parts index (build_corpus_index(parts=)) is not captured yet -- the fold and "
                              "K10 with offsets need no host round trip, but the captured pass has not been verified; use "
                              "vcmr_search or vcmr_search_host")
