@@ -999,8 +999,20 @@ typedef enum {
   XML_DC_Q2C_PERSIST_MIN_K_BYTES,
   XML_DC_L2N_MAXJ, XML_DC_L2N_LANES,                          /* 16-byte chunks per lane, lanes per row             */
   XML_DC_ATTN_MAX_L, XML_DC_ATTN_SMALL_MAX_L, XML_DC_ATTN_SMALL_UNITS,
-  XML_DC_ATTN_N_HEAD_SIZES, XML_DC_ATTN_HEAD_SIZE0            /* head size i is XML_DC_ATTN_HEAD_SIZE0 + i          */
+  XML_DC_ATTN_N_HEAD_SIZES, XML_DC_ATTN_HEAD_SIZE0,           /* head size i is XML_DC_ATTN_HEAD_SIZE0 + i          */
+  /* K7 / span evidence / re-score (numbered from 100: the head sizes above are open-ended) */
+  XML_DC_CONVSE_TM = 100, XML_DC_RESCORE_TM_BIG,              /* pairs per chunk                                    */
+  XML_DC_CONVSE_SMALL_P, XML_DC_CONVSE_SMALL_NV,              /* the one-workgroup inversion takes at most these    */
+  XML_DC_CONVSE_SUB_MAX, XML_DC_CONVSE_SUB_MIN_PAIRS_PER_VIDEO, /* sub-counters per video; from P >= this * nv      */
+  XML_DC_CONVSE_STEP_BYTES, XML_DC_CONVSE_MAX_KSIZE, XML_DC_CONVSE_FAST_KSIZE, XML_DC_CONVSE_END
 } xml_dispatch_constant;
+/* the re-rank kernels of convse.hip: which entry is asked about, and what */
+typedef enum { XML_CONVSE_K7 = 0, XML_CONVSE_EVIDENCE = 1, XML_CONVSE_RESCORE = 2 } xml_convse_entry;
+typedef enum { XML_CONVSE_REFUSED = 0, XML_CONVSE_STAGED = 1, XML_CONVSE_DMA = 2 } xml_convse_mainloop;
+typedef enum { XML_CONVSE_INV_SMALL = 0, XML_CONVSE_INV_GLOBAL = 1, XML_CONVSE_INV_SUB = 2 } xml_convse_inversion;
+typedef enum { XML_CONVSE_EPI_FAST = 0, XML_CONVSE_EPI_GENERAL = 1, XML_CONVSE_EPI_ROWMAX = 2 } xml_convse_epilogue;
+typedef enum { XML_CONVSE_ASK_MAINLOOP = 0, XML_CONVSE_ASK_EPILOGUE = 1 } xml_convse_shape_question;
+typedef enum { XML_CONVSE_ASK_INVERSION = 0, XML_CONVSE_ASK_CHUNK_PAIRS = 1, XML_CONVSE_ASK_MAX_CHUNKS = 2 } xml_convse_pairs_question;
 int64_t xml_dispatch_const(int which);                                       /* xml_dispatch_constant -> value  */
 int xml_dispatch_gemm(int64_t M, int N, int K, int dt);                      /* xml_gemm_kernel; dt f32 / bf16 / f16s */
 int xml_dispatch_gemm_rules(int64_t M, int N, int K, int dt);                /* xml_gemm_rules flags            */
@@ -1012,6 +1024,16 @@ int xml_dispatch_q2c_fused(int n_mod, int lpad, int hidden, int dt, int launch);
 int xml_dispatch_q2c_walk(int what, int a, int b);
 int xml_dispatch_attention(int lq, int lk, int hidden, int n_heads, int dt); /* xml_attn_kernel of the attention core */
 int xml_dispatch_l2norm(int d, int dt);                                      /* xml_l2norm_kernel of xml_l2norm_rows */
+/* xml_convse_rerank* (XML_CONVSE_K7), xml_span_evidence (_EVIDENCE), xml_q2c_rescore (_RESCORE; l_ref, ksize, summ ignored);
+ * dt f32 / bf16 / f16s.  nq = query rows of the operand (they bound the DMA loop's 32-bit row offsets).
+ *   XML_CONVSE_ASK_MAINLOOP -> xml_convse_mainloop; XML_CONVSE_REFUSED: the entry returns XML_ERR_UNSUPPORTED for the shape
+ *   XML_CONVSE_ASK_EPILOGUE -> xml_convse_epilogue (summ != 0: candidate summaries asked for, xml_convse_rerank_ex), or
+ *                              XML_CONVSE_EPI_ROWMAX for the re-score; -1 on a refused shape */
+int xml_dispatch_convse_shape(int entry, int what, int64_t nq, int lpad, int l_ref, int hidden, int ksize, int summ, int dt);
+/* n_pairs = nq * kpairs (span evidence: its explicit pairs) on nv videos:
+ *   XML_CONVSE_ASK_INVERSION -> xml_convse_inversion;  _CHUNK_PAIRS -> pairs per workgroup chunk;
+ *   _MAX_CHUNKS -> workgroups of the launch, n_pairs / chunk_pairs + min(n_pairs, nv) */
+int64_t xml_dispatch_convse_pairs(int entry, int what, int64_t n_pairs, int nv, int dt);
 
 #ifdef __cplusplus
 }

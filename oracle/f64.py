@@ -315,6 +315,53 @@ def span_logits(sims, filters, mask, merged, ks):
     return lst, led
 
 
+def convse(q, f, masks, pair_q, pair_vid, conv_w, l_ref, merged, ks, softmax=False, dtype=torch.float64):
+    """K7 / span evidence on explicit pairs, in `dtype` (float64: the exact value W; float32: the reference's own arithmetic R).
+    q[m] (Nq, H), f[m] (Nv, Lpad, H): the STORED operand values; masks[m] (Nv, Lpad) -- one mask per stream, the merged form
+    uses the first; pair_q, pair_vid (P,): pair p = query row pair_q[p] x video pair_vid[p], a video outside [0, Nv) = a
+    skipped pair (zero rows); conv_w flat [st filters..., ed filters...], one pair of filters per unmerged stream.
+    Similarities by einsum on the listed pairs only; taps zero-padded at l_ref (clips >= l_ref do not exist), mask_logits
+    behind the filter, the mean over unmerged streams, optionally the softmax over the first l_ref clips.
+    -> dict of (P, Lpad) rows, entries l >= l_ref zero: st, ed, sims (list, unmasked), sim (their mean)."""
+    n_mod, n_conv = len(q), 1 if merged else len(q)
+    nv, lpad = f[0].shape[0], f[0].shape[1]
+    pq, pv = O._t(pair_q).long(), O._t(pair_vid).long()
+    ok = (pv >= 0) & (pv < nv)
+    pqc, pvc = pq.clamp(min=0), pv.clamp(0, nv - 1)
+    sims = [torch.einsum("pd,pld->pl", O._t(q[m]).to(dtype)[pqc], O._t(f[m]).to(dtype)[pvc, :l_ref]) for m in range(n_mod)]
+    cw = O._t(conv_w).to(dtype)
+    filters = [cw[i * ks:(i + 1) * ks].view(1, 1, ks) for i in range(2 * n_conv)]
+    mk = [O._t(masks[0 if merged else m]).to(dtype)[pvc, :l_ref] for m in range(n_conv)]
+    st, ed = span_logits(sims, filters, mk, merged, ks)
+    if softmax:
+        st, ed = torch.softmax(st, -1), torch.softmax(ed, -1)
+
+    def rows(x):
+        out = x.new_zeros(x.shape[0], lpad)
+        out[:, :l_ref] = x
+        out[~ok] = 0
+        return out
+    return dict(st=rows(st), ed=rows(ed), sims=[rows(s) for s in sims], sim=rows(sum(sims) / n_mod))
+
+
+def q2c_rescore(qn, cn, masks, pair_vid, dtype=torch.float64):
+    """xml_q2c_rescore: out[q, j] = sum_m max_l mask_logits(qn_m[q] . cn_m[v, l]) / n_mod for v = pair_vid[q, j]; -inf for a
+    video outside [0, Nv).  Stored operand values, `dtype` arithmetic."""
+    pv = O._t(pair_vid).long()
+    nq, kp = pv.shape
+    nv = cn[0].shape[0]
+    ok = (pv >= 0) & (pv < nv)
+    pvc = pv.clamp(0, nv - 1).reshape(-1)
+    pq = torch.arange(nq).repeat_interleave(kp)
+    tot = 0
+    for m in range(len(qn)):
+        s = torch.einsum("pd,pld->pl", O._t(qn[m]).to(dtype)[pq], O._t(cn[m]).to(dtype)[pvc])
+        tot = tot + O.mask_logits(s, O._t(masks[m]).to(dtype)[pvc]).max(1)[0]
+    out = (tot / len(qn)).view(nq, kp)
+    out[~ok] = float("-inf")
+    return out
+
+
 def train_span_loss(sims, filters, mask, st_ed, merged, ks):
     """SpanLossFn (f32 in the bf16 model too: PairSimFn's output is f32): no bf16 boundary.  mask: see `span_logits`."""
     lst, led = span_logits(sims, filters, mask, merged, ks)

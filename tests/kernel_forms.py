@@ -152,6 +152,72 @@ def tile_rows_l2norm_ok(hidden, es):
     return bool(LIB.xml_q2c_tile_rows_l2norm_ok(hidden, dt_of(es)))
 
 
+# ---- K7 / span evidence / exact-rank re-score (convse.hip) ----------------------------------------------------------------
+# operand types here: torch-free names "f32", "bf16", "f16s" (the split-f16 form has 4-byte elements like f32)
+CONVSE_DT = {"f32": _lib.XML_F32, "bf16": _lib.XML_BF16, "f16s": _lib.XML_F16S}
+CONVSE_ENTRIES = {"k7": E["XML_CONVSE_K7"], "evidence": E["XML_CONVSE_EVIDENCE"], "rescore": E["XML_CONVSE_RESCORE"]}
+CONVSE_LOOPS = {E["XML_CONVSE_REFUSED"]: "refused", E["XML_CONVSE_STAGED"]: "staged", E["XML_CONVSE_DMA"]: "dma"}
+CONVSE_INVERSIONS = {E["XML_CONVSE_INV_SMALL"]: "one-workgroup", E["XML_CONVSE_INV_GLOBAL"]: "global", E["XML_CONVSE_INV_SUB"]: "sub"}
+CONVSE_EPILOGUES = {E["XML_CONVSE_EPI_FAST"]: "fast", E["XML_CONVSE_EPI_GENERAL"]: "general", E["XML_CONVSE_EPI_ROWMAX"]: "rowmax"}
+CONVSE_TM, RESCORE_TM_BIG = const("CONVSE_TM"), const("RESCORE_TM_BIG")
+CONVSE_SMALL_P, CONVSE_SMALL_NV = const("CONVSE_SMALL_P"), const("CONVSE_SMALL_NV")
+CONVSE_SUB_MIN_PAIRS_PER_VIDEO, CONVSE_STEP_BYTES = const("CONVSE_SUB_MIN_PAIRS_PER_VIDEO"), const("CONVSE_STEP_BYTES")
+
+
+def convse_mainloop(entry, nq, lpad, l_ref, hidden, ksize, dt):
+    """"dma" (LDS-DMA ring), "staged" (register-staged loop, zero-filled K tail) or "refused" (XML_ERR_UNSUPPORTED)."""
+    return CONVSE_LOOPS[ask("xml_dispatch_convse_shape", CONVSE_ENTRIES[entry], E["XML_CONVSE_ASK_MAINLOOP"], nq, lpad, l_ref,
+                            hidden, ksize, 0, CONVSE_DT[dt])]
+
+
+def convse_steps(hidden, dt):
+    """K steps of either mainloop, and the bytes of K in the last one (a whole step: CONVSE_STEP_BYTES)."""
+    kb = hidden * (2 if dt == "bf16" else 4)
+    return cdiv(kb, CONVSE_STEP_BYTES), kb - (cdiv(kb, CONVSE_STEP_BYTES) - 1) * CONVSE_STEP_BYTES
+
+
+def convse_epilogue(entry, ksize, summ=False, dt="f32"):
+    """K7 / span evidence: "fast" (5 taps, no summaries) or "general"; the re-score: "rowmax"."""
+    return CONVSE_EPILOGUES[ask("xml_dispatch_convse_shape", CONVSE_ENTRIES[entry], E["XML_CONVSE_ASK_EPILOGUE"], 1, 16, 16, 32,
+                                ksize, int(summ), CONVSE_DT[dt])]
+
+
+def convse_inversion(entry, n_pairs, nv, dt="f32"):
+    """how the pair list is inverted: "one-workgroup", "global" counters or 16 "sub"-counters per video."""
+    return CONVSE_INVERSIONS[ask("xml_dispatch_convse_pairs", CONVSE_ENTRIES[entry], E["XML_CONVSE_ASK_INVERSION"], n_pairs, nv,
+                                 CONVSE_DT[dt])]
+
+
+def convse_chunk_pairs(entry, n_pairs, nv, dt="f32"):
+    return ask("xml_dispatch_convse_pairs", CONVSE_ENTRIES[entry], E["XML_CONVSE_ASK_CHUNK_PAIRS"], n_pairs, nv, CONVSE_DT[dt])
+
+
+def convse_max_chunks(entry, n_pairs, nv, dt="f32"):
+    """workgroups of the launch: n_pairs / chunk_pairs + min(n_pairs, nv)."""
+    return ask("xml_dispatch_convse_pairs", CONVSE_ENTRIES[entry], E["XML_CONVSE_ASK_MAX_CHUNKS"], n_pairs, nv, CONVSE_DT[dt])
+
+
+def convse_form(nq, n_pairs, nv, lpad, l_ref, hidden, ksize, dt, summ=False, entry="k7"):
+    """"<mainloop><steps>[+tail<bytes>]-<epilogue>-<inversion>" of one K7 / span-evidence launch, or "refused"."""
+    loop = convse_mainloop(entry, nq, lpad, l_ref, hidden, ksize, dt)
+    if loop == "refused":
+        return loop
+    steps, last = convse_steps(hidden, dt)
+    tail = "" if last == CONVSE_STEP_BYTES else "+tail%d" % last
+    return "%s%d%s-%s-%s" % (loop, steps, tail, convse_epilogue(entry, ksize, summ, dt), convse_inversion(entry, n_pairs, nv, dt))
+
+
+def rescore_form(nq, n_pairs, nv, lpad, hidden, dt):
+    """"<mainloop><steps>[+tail<bytes>]-chunk<pairs>-<inversion>" of one xml_q2c_rescore launch, or "refused"."""
+    loop = convse_mainloop("rescore", nq, lpad, lpad, hidden, 5, dt)
+    if loop == "refused":
+        return loop
+    steps, last = convse_steps(hidden, dt)
+    tail = "" if last == CONVSE_STEP_BYTES else "+tail%d" % last
+    return "%s%d%s-chunk%d-%s" % (loop, steps, tail, convse_chunk_pairs("rescore", n_pairs, nv, dt),
+                                  convse_inversion("rescore", n_pairs, nv, dt))
+
+
 # ---- attention -----------------------------------------------------------------------------------------------------------
 ATTN_KERNELS = {E["XML_ATTN_SMALL"]: "small", E["XML_ATTN_LARGE"]: "large",
                 E["XML_ATTN_REFUSED_HEADS"]: "refused: hidden % n_heads",

@@ -2007,6 +2007,8 @@ for _s in ("xml_rccl_available", "xml_rccl_unique_id", "xml_rccl_comm_init", "xm
 for _s in ("xml_dispatch_const", "xml_dispatch_gemm", "xml_dispatch_gemm_rules", "xml_dispatch_gemm_kloop", "xml_dispatch_q2c",
            "xml_dispatch_q2c_fused", "xml_dispatch_q2c_walk", "xml_dispatch_attention", "xml_dispatch_l2norm"):
     EXEMPT[_s] = "dispatch introspection: integers in, an enum out, no memory; tests/test_reduction_width_plan.py"
+for _s in ("xml_dispatch_convse_shape", "xml_dispatch_convse_pairs"):
+    EXEMPT[_s] = "dispatch introspection: integers in, an enum out, no memory; tests/test_convse_cases_reference.py"
 
 
 # =====================================================================================================================

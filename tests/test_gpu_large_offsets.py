@@ -1142,7 +1142,7 @@ LARGE_EXEMPT.update({s: NO_DEVICE for s in (
     "xml_rccl_topk_by_owner_workspace_bytes", "xml_merge_shard_topk_workspace_bytes", "xml_nms_vcmr_host", "xml_nms_svmr_host",
     "xml_nms_vcmr_batched_host", "xml_nms_svmr_batched_host", "xml_dispatch_const", "xml_dispatch_gemm",
     "xml_dispatch_gemm_rules", "xml_dispatch_gemm_kloop", "xml_dispatch_q2c", "xml_dispatch_q2c_fused", "xml_dispatch_q2c_walk",
-    "xml_dispatch_attention", "xml_dispatch_l2norm")})
+    "xml_dispatch_attention", "xml_dispatch_l2norm", "xml_dispatch_convse_shape", "xml_dispatch_convse_pairs")})
 # the encoders, the query side and everything behind K8 see a batch of videos or queries (and the model's weights), never the
 # resident corpus: their row counts are those of tests/test_gpu_fullsize.py at most
 LARGE_EXEMPT.update({s: BATCH_ONLY for s in (

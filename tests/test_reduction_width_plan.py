@@ -212,3 +212,31 @@ def test_pinned_thresholds():
     assert not DM.q2c_tiled_ok(128, 64, 4) and DM.q2c_tiled_ok(128, 96, 4) and not DM.q2c_tiled_ok(112, 96, 4)
     assert DM.attn_form(32, 32, 64, 1, 2) == "small" and DM.attn_form(33, 32, 64, 1, 2) == DM.attn_form(32, 33, 64, 1, 2) == "large"
     assert DM.attn_form(128, 128, 64, 1, 2) == "large" and DM.attn_form(129, 128, 64, 1, 2) == "refused: longer than 128"
+    # K7 / span evidence / re-score (convse.hip)
+    assert (DM.CONVSE_TM, DM.RESCORE_TM_BIG, DM.CONVSE_SMALL_P, DM.CONVSE_SMALL_NV) == (64, 128, 32768, 4096)
+    assert (DM.CONVSE_SUB_MIN_PAIRS_PER_VIDEO, DM.CONVSE_STEP_BYTES, c("CONVSE_SUB_MAX")) == (128, 128, 16)
+    assert (c("CONVSE_MAX_KSIZE"), c("CONVSE_FAST_KSIZE")) == (15, 5)
+    for entry in ("k7", "evidence"):
+        assert [DM.convse_inversion(entry, p, nv) for p, nv in ((32768, 4096), (32769, 4096), (32768, 4097))] == \
+            ["one-workgroup", "global", "global"]
+        assert [DM.convse_inversion(entry, p, 257) for p in (128 * 257 - 1, 128 * 257)] == ["global", "sub"]
+        assert [DM.convse_epilogue(entry, ks) for ks in (1, 3, 5, 7, 15)] == ["general", "general", "fast", "general", "general"]
+        assert DM.convse_chunk_pairs(entry, 10 ** 6, 2, "f16s") == 64
+    assert DM.convse_epilogue("k7", 5, summ=True) == "general" and DM.convse_epilogue("evidence", 5, summ=True) == "fast"
+    assert [DM.convse_inversion("rescore", p, 2) for p in (1, 255, 256)] == ["global", "global", "sub"]
+    assert [DM.convse_chunk_pairs("rescore", p, 2, dt) for dt in ("f32", "bf16", "f16s") for p in (128, 129)] == [64, 64, 64, 64, 64, 128]
+    assert DM.convse_max_chunks("k7", 129, 13) == 2 + 13 and DM.convse_max_chunks("k7", 5, 13) == 5
+    assert DM.convse_max_chunks("rescore", 129, 2, "f16s") == 1 + 2 and DM.convse_max_chunks("rescore", 128, 2, "f16s") == 2 + 2
+    # the DMA mainloop: whole 128-byte rows, and both 32-bit row-offset conditions (query rows; a video's lpad clip rows)
+    loop = lambda nq, lpad, h, dt, e="k7": DM.convse_mainloop(e, nq, lpad, lpad, h, 5, dt)       # noqa: E731
+    assert [loop(4, 16, h, "f32") for h in (8, 24, 32, 40, 64)] == ["staged", "staged", "dma", "staged", "dma"]
+    assert [loop(4, 16, h, "bf16") for h in (32, 64, 72, 96, 128)] == ["staged", "dma", "staged", "staged", "dma"]
+    assert [loop(4, 16, h, "f16s") for h in (32, 96)] == ["dma", "dma"] and loop(4, 16, 48, "f16s") == "refused"
+    for e in ("k7", "evidence", "rescore"):
+        assert loop(2 ** 32 // 128 - 1, 16, 32, "f32", e) == "dma" and loop(2 ** 32 // 128, 16, 32, "f32", e) == "staged"
+        assert loop(2 ** 32 // 128, 16, 32, "f16s", e) == "refused"
+        assert loop(4, 128, 2 ** 23 - 32, "f32", e) == "dma" and loop(4, 128, 2 ** 23, "f32", e) == "staged"
+        assert loop(4, 24, 32, "f32", e) == loop(4, 144, 32, "f32", e) == loop(4, 16, 12, "f32", e) == "refused"
+    assert [DM.convse_mainloop("k7", 4, 16, l_ref, 32, ks, "f32") for l_ref, ks in ((17, 5), (0, 5), (16, 4), (16, 17), (16, 15))] == \
+        ["refused"] * 4 + ["dma"]
+    assert DM.convse_mainloop("rescore", 4, 16, 99, 32, 4, "f32") == "dma"          # (no filter, no l_ref)

@@ -240,6 +240,8 @@ SIGNATURES = {
     "xml_dispatch_q2c_walk": (c_int, [c_int, c_int, c_int]),
     "xml_dispatch_attention": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "xml_dispatch_l2norm": (c_int, [c_int, c_int]),
+    "xml_dispatch_convse_shape": (c_int, [c_int, c_int, c_int64, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "xml_dispatch_convse_pairs": (c_int64, [c_int, c_int, c_int64, c_int, c_int]),
 }
 
 # the companion header include/xmlhip_index.h (tests/test_index_packed_capi.py checks): the packed form of the updatable index

@@ -25,6 +25,11 @@ extern "C" int64_t xml_dispatch_const(int which) {
       d::ATTN_N_HEAD_SIZES};
   static_assert(sizeof(v) / sizeof(v[0]) == XML_DC_ATTN_HEAD_SIZE0, "one value per xml_dispatch_constant");
   if (which >= 0 && which < XML_DC_ATTN_HEAD_SIZE0) return v[which];
+  static const int64_t k7[] = {     // XML_DC_CONVSE_TM ...
+      d::CONVSE_TM, d::RESCORE_TM_BIG, d::CONVSE_SMALL_P, d::CONVSE_SMALL_NV, d::CONVSE_SUB_MAX,
+      d::CONVSE_SUB_MIN_PAIRS_PER_VIDEO, d::CONVSE_STEP_BYTES, d::CONVSE_MAX_KSIZE, d::CONVSE_FAST_KSIZE};
+  static_assert(sizeof(k7) / sizeof(k7[0]) == XML_DC_CONVSE_END - XML_DC_CONVSE_TM, "one value per XML_DC_CONVSE_* constant");
+  if (which >= XML_DC_CONVSE_TM && which < XML_DC_CONVSE_END) return k7[which - XML_DC_CONVSE_TM];
   const int i = which - XML_DC_ATTN_HEAD_SIZE0;
   return i >= 0 && i < d::ATTN_N_HEAD_SIZES ? d::ATTN_HEAD_SIZES[i] : -1;
 }
@@ -64,6 +69,30 @@ extern "C" int xml_dispatch_q2c_walk(int what, int a, int b) {
 extern "C" int xml_dispatch_attention(int lq, int lk, int hidden, int n_heads, int dt) {
   const bool ok = lq > 0 && lk > 0 && hidden > 0 && (dt == XML_F32 || dt == XML_BF16);
   return ok ? dispatch::attn_kernel(lq, lk, hidden, n_heads, dt) : -1;
+}
+static bool convse_entry_ok(int entry, int dt) {
+  return entry >= XML_CONVSE_K7 && entry <= XML_CONVSE_RESCORE && dispatch::convse_dt_ok(dt);
+}
+extern "C" int xml_dispatch_convse_shape(int entry, int what, int64_t nq, int lpad, int l_ref, int hidden, int ksize, int summ,
+                                         int dt) {
+  if (!convse_entry_ok(entry, dt) || nq <= 0 || lpad <= 0 || hidden <= 0) return -1;
+  const bool rescore = entry == XML_CONVSE_RESCORE;
+  const bool shape_ok = rescore ? dispatch::rescore_shape_ok(lpad, hidden, dt) : dispatch::convse_shape_ok(lpad, l_ref, hidden, ksize, dt);
+  const int loop = shape_ok ? dispatch::convse_mainloop(nq, lpad, hidden, dt) : XML_CONVSE_REFUSED;
+  if (what == XML_CONVSE_ASK_MAINLOOP) return loop;
+  if (what != XML_CONVSE_ASK_EPILOGUE || loop == XML_CONVSE_REFUSED) return -1;
+  if (rescore) return XML_CONVSE_EPI_ROWMAX;
+  // (span evidence forms no summaries)
+  return dispatch::convse_fast_epilogue(ksize, entry == XML_CONVSE_K7 && summ != 0) ? XML_CONVSE_EPI_FAST : XML_CONVSE_EPI_GENERAL;
+}
+extern "C" int64_t xml_dispatch_convse_pairs(int entry, int what, int64_t n_pairs, int nv, int dt) {
+  if (!convse_entry_ok(entry, dt) || n_pairs <= 0 || nv <= 0) return -1;
+  const bool rescore = entry == XML_CONVSE_RESCORE;
+  const int tm = rescore ? dispatch::rescore_chunk_pairs(n_pairs, nv, dt) : dispatch::CONVSE_TM;
+  if (what == XML_CONVSE_ASK_INVERSION) return dispatch::convse_inversion(n_pairs, nv, rescore);
+  if (what == XML_CONVSE_ASK_CHUNK_PAIRS) return tm;
+  if (what == XML_CONVSE_ASK_MAX_CHUNKS) return dispatch::convse_max_chunks(n_pairs, nv, tm);
+  return -1;
 }
 extern "C" int xml_dispatch_l2norm(int d, int dt) {
   return d <= 0 || (dt != XML_F32 && dt != XML_BF16) ? -1 : dispatch::l2n_vec_ok(d, dt) ? XML_L2N_VEC16 : XML_L2N_SCALAR;

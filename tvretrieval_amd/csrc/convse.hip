@@ -13,16 +13,13 @@
 #include "band.h"
 #include "gemm.h"
 
-static constexpr int TM = 64;            // pairs per workgroup chunk (a video has ~46 pairs at C3: one chunk each)
+// Which mainloop, inversion path, chunk size and epilogue a shape gets: dispatch.h (xml_dispatch_convse_* answer from it).
+static constexpr int TM = dispatch::CONVSE_TM;      // pairs per workgroup chunk
 static constexpr int LP = 128 + 8;       // row of the LDS similarity patch (floats): [4 halo | 128 clips | 4 halo]
 static constexpr int LH = 4;             // the clips start at float LH of a row (the fast epilogue reads 2 before / 5 past)
 
-// Popular videos: with few videos and many pairs (TVR val: 2 179 videos, 1.09 M pairs = 500 per counter) the counting
-// atomics serialise on their addresses -- 138 us of a 1.1 ms K7.  Every video then gets CONVSE_SUB_MAX sub-counters, a pair
-// uses sub-counter (pair id % sub): 16 x fewer collisions per address; the scan runs over the sub-buckets in (video, sub)
-// order, so a video's bucket is still one contiguous range.
-static constexpr int CONVSE_SUB_MAX = 16;
-static inline int convse_sub(int64_t P, int nv) { return P >= 128 * (int64_t)nv ? CONVSE_SUB_MAX : 1; }
+using dispatch::CONVSE_SUB_MAX;      // sub-counters per popular video (dispatch::convse_sub)
+using dispatch::convse_sub;
 
 struct ConvseWs {
   int32_t* counts;     // [nv * sub]   pairs per (video, sub-counter)
@@ -46,7 +43,7 @@ static size_t convse_ws_layout(const xml_convse_desc* d, ConvseWs* w, char* base
   char* chunk_off = take((nv + 1) * 4);
   char* bucket = take(P * 4);
   char* pos = take(P * 4);
-  char* chunk_vid = take((P / TM + (P < nv ? P : nv) + 1) * 4);
+  char* chunk_vid = take(((size_t)dispatch::convse_max_chunks((int64_t)P, (int)nv, TM) + 1) * 4);      // (64-pair chunks: the most)
   if (w) {
     w->chunk_vid = (int32_t*)chunk_vid;
     w->counts = (int32_t*)counts; w->pos = (int32_t*)pos; w->offsets = (int32_t*)offsets;
@@ -137,7 +134,7 @@ __global__ void convse_fill_kernel(const int32_t* __restrict__ pair_vid, const i
 // Small pair lists (the reference's 50-query batches: 5 000 pairs): the five launches above -- zero, count, zero skipped
 // rows, scan, fill -- cost 24 us of launch floor in a 350 us batch.  ONE workgroup does all of it: counters and bucket
 // starts in LDS, ranks kept in the `pos` scratch by the thread that took them.
-static constexpr int CONVSE_SMALL_NV = 4096, CONVSE_SMALL_P = 32768;
+using dispatch::CONVSE_SMALL_NV;     // (dispatch::convse_small_inversion)
 __global__ __launch_bounds__(1024) void convse_invert_small_kernel(const int32_t* __restrict__ pair_vid,
                                                                    int32_t* __restrict__ offsets, int32_t* __restrict__ chunk_off,
                                                                    int32_t* __restrict__ chunk_vid, int32_t* __restrict__ pos,
@@ -437,7 +434,7 @@ __global__ __launch_bounds__(256, IsSplit16<T>::value ? 2 : 3) void convse_kerne
       mk_r[si][h] = (si < n_sim && l < a.l_ref) ? a.mask[a.merged ? 0 : si][(int64_t)v * a.lpad + l] : 0.f;
     }
   __syncthreads();
-  if (a.ksize == 5 && !a.summ) {
+  if (XML_CONVSE_FAST_EPILOGUE(a.ksize, a.summ)) {      // dispatch::convse_fast_epilogue
     // ---- fast epilogue (5 taps, no candidate summaries): HALF a wave per pair row, a lane owns 4 CONSECUTIVE clips ------
     // The row loop below costs a wave ~30 dependent LDS reads, four 64-lane reductions and four 256-byte stores per pair row
     // and was 0.6 of K7's 1.1 ms at the as-trained shape (tools/bench_k7.py, ablation 2).  Here a lane reads its 4 clips +
@@ -722,13 +719,12 @@ extern "C" int xml_convse_rerank_ex(const xml_convse_desc* d, const void* q_lin0
   if (d->n_mod < 1 || d->n_mod > 2 || (d->n_mod == 2 && (!q_lin1 || !feat2_1))) return XML_ERR_BAD_ARG;
   if (d->n_mod == 2 && !d->merged && !mask1) return XML_ERR_BAD_ARG;
   if (d->merged && d->n_mod != 2) return XML_ERR_BAD_ARG;
-  if (d->lpad % 16 || d->lpad > 128 || d->l_ref > d->lpad || d->l_ref <= 0 || d->hidden % 8) return XML_ERR_UNSUPPORTED;
-  if (!(d->ksize & 1) || d->ksize > 15 || d->ksize < 1) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::convse_shape_ok(d->lpad, d->l_ref, d->hidden, d->ksize, XML_F32)) return XML_ERR_UNSUPPORTED;
   if (summ_out && (min_l < 0 || max_l <= min_l)) return XML_ERR_BAD_ARG;
   if (!(d->softmax & 1)) return XML_ERR_BAD_ARG;      // summaries are of PROBABILITIES; unwritten entries are exact zeros of a softmax
   if (d->dt == XML_F16S) {
     if (!q_inv0 || !c_inv0 || (d->n_mod == 2 && (!q_inv1 || !c_inv1))) return XML_ERR_BAD_ARG;
-    if (d->hidden % 32) return XML_ERR_UNSUPPORTED;
+    if (!dispatch::rescore_shape_ok(d->lpad, d->hidden, XML_F16S)) return XML_ERR_UNSUPPORTED;
   } else if (d->dt != XML_F32 && d->dt != XML_BF16) {
     return XML_ERR_BAD_ARG;
   }
@@ -748,8 +744,7 @@ extern "C" int xml_convse_rerank(const xml_convse_desc* d, const void* q_lin0, c
   if (d->n_mod < 1 || d->n_mod > 2 || (d->n_mod == 2 && (!q_lin1 || !feat2_1))) return XML_ERR_BAD_ARG;
   if (d->n_mod == 2 && !d->merged && !mask1) return XML_ERR_BAD_ARG;
   if (d->merged && d->n_mod != 2) return XML_ERR_BAD_ARG;
-  if (d->lpad % 16 || d->lpad > 128 || d->l_ref > d->lpad || d->l_ref <= 0 || d->hidden % 8) return XML_ERR_UNSUPPORTED;
-  if (!(d->ksize & 1) || d->ksize > 15 || d->ksize < 1) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::convse_shape_ok(d->lpad, d->l_ref, d->hidden, d->ksize, XML_F32)) return XML_ERR_UNSUPPORTED;
   if (d->dt != XML_F32 && d->dt != XML_BF16) return XML_ERR_BAD_ARG;
   return convse_rerank_impl(d, q_lin0, q_lin1, feat2_0, feat2_1, mask0, mask1, pair_vid, conv_w, st_out, ed_out, ws, ws_bytes,
                             nullptr, nullptr, nullptr, nullptr, stream);
@@ -767,8 +762,7 @@ extern "C" int xml_convse_rerank_f16s(const xml_convse_desc* d, const void* q_li
   if (d->n_mod < 1 || d->n_mod > 2 || (d->n_mod == 2 && (!q_lin1 || !feat2_1 || !q_inv1 || !c_inv1))) return XML_ERR_BAD_ARG;
   if (d->n_mod == 2 && !d->merged && !mask1) return XML_ERR_BAD_ARG;
   if (d->merged && d->n_mod != 2) return XML_ERR_BAD_ARG;
-  if (d->lpad % 16 || d->lpad > 128 || d->l_ref > d->lpad || d->l_ref <= 0 || d->hidden % 32) return XML_ERR_UNSUPPORTED;
-  if (!(d->ksize & 1) || d->ksize > 15 || d->ksize < 1) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::convse_shape_ok(d->lpad, d->l_ref, d->hidden, d->ksize, XML_F16S)) return XML_ERR_UNSUPPORTED;
   if (d->dt != XML_F16S) return XML_ERR_BAD_ARG;
   return convse_rerank_impl(d, q_lin0, q_lin1, feat2_0, feat2_1, mask0, mask1, pair_vid, conv_w, st_out, ed_out, ws, ws_bytes,
                             q_inv0, q_inv1, c_inv0, c_inv1, stream);
@@ -789,7 +783,7 @@ static int convse_rerank_impl(const xml_convse_desc* d, const void* q_lin0, cons
   convse_ws_layout(&dl, &w, (char*)ws);
   const int64_t P = (int64_t)dl.nq * dl.kpairs;
   int sub = 1;
-  if (P <= CONVSE_SMALL_P && d->nv <= CONVSE_SMALL_NV) {
+  if (dispatch::convse_small_inversion(P, d->nv)) {
     hipLaunchKernelGGL(convse_invert_small_kernel, dim3(1), dim3(1024), 0, st, pair_vid, w.offsets, w.chunk_off, w.chunk_vid,
                        w.pos, w.bucket, st_out, ed_out, (int)P, d->nv, TM, d->lpad / 4, (d->softmax & 2) ? 0 : 1);
     XML_CHECK_LAUNCH();
@@ -831,11 +825,10 @@ static int convse_rerank_impl(const xml_convse_desc* d, const void* q_lin0, cons
   a.q_inv[0] = q_inv0; a.q_inv[1] = q_inv1 ? q_inv1 : q_inv0;
   a.c_inv[0] = c_inv0; a.c_inv[1] = c_inv1 ? c_inv1 : c_inv0;
   {
-    const int64_t kb = (int64_t)d->hidden * (int64_t)dt_size(d->dt);
-    a.dma = (kb % 128 == 0 && (int64_t)d->nq * kb < (1ll << 32) && (int64_t)d->lpad * kb < (1ll << 32)) ? 1 : 0;
+    a.dma = dispatch::convse_dma(d->nq, d->lpad, d->hidden, d->dt) ? 1 : 0;
     if (g_q2c_ablation == 40) a.dma = 0;             // (debug build: A/B against the register-staged mainloop)
   }
-  const int64_t max_chunks = P / TM + (P < d->nv ? P : d->nv);
+  const int64_t max_chunks = dispatch::convse_max_chunks(P, d->nv, TM);
   const int n_sim = d->merged ? 1 : d->n_mod;
   const size_t patch = (size_t)TM * LP * 4;
   if (d->dt == XML_F16S) {
@@ -916,12 +909,11 @@ extern "C" int xml_span_evidence(const xml_convse_desc* d, const void* q_lin0, c
   if (d->n_mod < 1 || d->n_mod > 2 || (d->n_mod == 2 && (!q_lin1 || !feat2_1 || !sim1_out))) return XML_ERR_BAD_ARG;
   if (d->n_mod == 2 && !d->merged && !mask1) return XML_ERR_BAD_ARG;
   if (d->merged && d->n_mod != 2) return XML_ERR_BAD_ARG;
-  if (d->lpad % 16 || d->lpad > 128 || d->l_ref > d->lpad || d->l_ref <= 0 || d->hidden % 8) return XML_ERR_UNSUPPORTED;
-  if (!(d->ksize & 1) || d->ksize > 15 || d->ksize < 1) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::convse_shape_ok(d->lpad, d->l_ref, d->hidden, d->ksize, XML_F32)) return XML_ERR_UNSUPPORTED;
   const bool split = d->dt == XML_F16S;
   if (split) {
     if (!q_inv0 || !c_inv0 || (d->n_mod == 2 && (!q_inv1 || !c_inv1))) return XML_ERR_BAD_ARG;
-    if (d->hidden % 32) return XML_ERR_UNSUPPORTED;
+    if (!dispatch::rescore_shape_ok(d->lpad, d->hidden, XML_F16S)) return XML_ERR_UNSUPPORTED;
   } else if (d->dt != XML_F32 && d->dt != XML_BF16) {
     return XML_ERR_BAD_ARG;
   }
@@ -962,9 +954,11 @@ extern "C" int xml_q2c_rescore(int n_mod, const void* qn0, const void* qn1, cons
   if (!qn0 || !cn0 || !mask0 || !pair_vid || !out || !ws) return XML_ERR_BAD_ARG;
   if (n_mod < 1 || n_mod > 2 || (n_mod == 2 && (!qn1 || !cn1 || !mask1))) return XML_ERR_BAD_ARG;
   if (nq <= 0 || nv <= 0 || kpairs <= 0 || hidden <= 0) return XML_ERR_BAD_ARG;
-  if (lpad % 16 || lpad > 128 || lpad <= 0 || hidden % 8) return XML_ERR_UNSUPPORTED;
-  if (dt != XML_F32 && dt != XML_BF16 && dt != XML_F16S) return XML_ERR_BAD_ARG;
-  if (dt == XML_F16S && hidden % 32) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::rescore_shape_ok(lpad, hidden, XML_F32)) return XML_ERR_UNSUPPORTED;
+  if (!dispatch::convse_dt_ok(dt)) return XML_ERR_BAD_ARG;
+  if (!dispatch::rescore_shape_ok(lpad, hidden, dt)) return XML_ERR_UNSUPPORTED;
+  // (split rows past the DMA loop's 32-bit row offsets: refused at either chunk size, before anything is launched)
+  if (dispatch::convse_mainloop(nq, lpad, hidden, dt) == XML_CONVSE_REFUSED) return XML_ERR_UNSUPPORTED;
   if (ws_bytes < xml_q2c_rescore_workspace_bytes(nq, nv, kpairs)) return XML_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   xml_convse_desc d{};
@@ -984,9 +978,10 @@ extern "C" int xml_q2c_rescore(int n_mod, const void* qn0, const void* qn1, cons
   XML_CHECK_LAUNCH();
   // rows per chunk: 128 when the average video is listed by more than 64 pairs (then most videos would need two 64-row
   // chunks, each fetching the tile again)
-  const bool big = dt == XML_F16S && P > 64 * (int64_t)nv;
+  const int tm = dispatch::rescore_chunk_pairs(P, nv, dt);
+  const bool big = tm == dispatch::RESCORE_TM_BIG;
   hipLaunchKernelGGL(convse_scan_kernel, dim3(1), dim3(1024), 0, st, w.counts, w.offsets, w.chunk_off, w.chunk_vid, nv,
-                     big ? 128 : TM, sub);
+                     tm, sub);
   XML_CHECK_LAUNCH();
   hipLaunchKernelGGL(convse_fill_kernel, dim3(cdiv(P, 256)), dim3(256), 0, st, pair_vid, w.offsets, w.pos, w.bucket, P, sub);
   XML_CHECK_LAUNCH();
@@ -998,19 +993,18 @@ extern "C" int xml_q2c_rescore(int n_mod, const void* qn0, const void* qn1, cons
   a.offsets = w.offsets; a.chunk_off = w.chunk_off; a.bucket = w.bucket; a.chunk_vid = w.chunk_vid;
   a.nv = nv; a.kpairs = kpairs; a.lpad = lpad; a.hidden = hidden; a.n_mod = n_mod;
   {
-    const int64_t kb = (int64_t)hidden * (int64_t)dt_size(dt);
-    a.dma = (kb % 128 == 0 && (int64_t)nq * kb < (1ll << 32) && (int64_t)lpad * kb < (1ll << 32)) ? 1 : 0;
+    a.dma = dispatch::convse_dma(nq, lpad, hidden, dt) ? 1 : 0;
     if (g_q2c_ablation == 40) a.dma = 0;
   }
-  const int64_t max_chunks = P / TM + (P < nv ? P : nv);
+  const int64_t max_chunks = dispatch::convse_max_chunks(P, nv, tm);
   if (dt == XML_F16S && big) {
     if (!a.dma) return XML_ERR_UNSUPPORTED;
-    using Cfg = GemmCfg<f16s_t, 128, 128, 1, 4>;
+    using Cfg = GemmCfg<f16s_t, dispatch::RESCORE_TM_BIG, 128, 1, 4>;
     constexpr int lds = GemmDma<Cfg, RS_STAGES>::LDS_BYTES;
-    if (!xml_lds_attr_once<rescore_kernel<f16s_t, 128>>(lds)) return XML_ERR_LAUNCH;
-    const int64_t chunks128 = P / 128 + (P < nv ? P : nv);
-    hipLaunchKernelGGL((rescore_kernel<f16s_t, 128>), dim3((unsigned)chunks128), dim3(256), lds, st, a);
+    if (!xml_lds_attr_once<rescore_kernel<f16s_t, dispatch::RESCORE_TM_BIG>>(lds)) return XML_ERR_LAUNCH;
+    hipLaunchKernelGGL((rescore_kernel<f16s_t, dispatch::RESCORE_TM_BIG>), dim3((unsigned)max_chunks), dim3(256), lds, st, a);
   } else if (dt == XML_F16S) {
+    if (!a.dma) return XML_ERR_UNSUPPORTED;          // (as the 128-row form and K7: dispatch::convse_mainloop)
     using Cfg = GemmCfg<f16s_t, TM, 128, 1, 4>;
     constexpr int lds = GemmDma<Cfg, RS_STAGES>::LDS_BYTES;
     if (!xml_lds_attr_once<rescore_kernel<f16s_t>>(lds)) return XML_ERR_LAUNCH;

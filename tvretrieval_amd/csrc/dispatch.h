@@ -127,6 +127,59 @@ constexpr int q2c_ring_slots(bool tiled, int mask_mode) {
   return tiled && (mask_mode == 1 || mask_mode == 2) ? RING_SLOTS_NOMASK : RING_SLOTS;
 }
 
+// ---- K7 / span evidence / exact-rank re-score (convse.hip: xml_convse_rerank*, xml_span_evidence, xml_q2c_rescore) -----
+constexpr int CONVSE_TM = 64;                 // pairs per workgroup chunk (a video has ~46 pairs at C3: one chunk each)
+constexpr int RESCORE_TM_BIG = 128;           // the split-f16 re-score when the average video is listed by more than CONVSE_TM pairs
+// Popular videos: with few videos and many pairs (TVR val: 2 179 videos, 1.09 M pairs = 500 per counter) the counting
+// atomics serialise on their addresses -- 138 us of a 1.1 ms K7.  Every video then gets CONVSE_SUB_MAX sub-counters, a pair
+// uses sub-counter (pair id % sub): 16 x fewer collisions per address; the scan runs over the sub-buckets in (video, sub)
+// order, so a video's bucket is still one contiguous range.
+constexpr int CONVSE_SUB_MAX = 16;
+constexpr int CONVSE_SUB_MIN_PAIRS_PER_VIDEO = 128;
+// Small pair lists (the reference's 50-query batches: 5 000 pairs): ONE workgroup inverts the list, counters in LDS
+constexpr int CONVSE_SMALL_NV = 4096, CONVSE_SMALL_P = 32768;
+constexpr int CONVSE_MAX_KSIZE = 15, CONVSE_FAST_KSIZE = 5, CONVSE_MAX_LPAD = 128;
+constexpr int CONVSE_STEP_BYTES = GEMM_SMALL_STEP_BYTES;      // the mainloops' K step (GemmCfg::ROWB)
+
+constexpr bool convse_dt_ok(int dt) { return dt == XML_F32 || dt == XML_BF16 || dt == XML_F16S; }
+// shapes the entries take (everything else: XML_ERR_UNSUPPORTED); the re-score has no filter and no l_ref
+constexpr bool rescore_shape_ok(int lpad, int hidden, int dt) {
+  return lpad > 0 && lpad % 16 == 0 && lpad <= CONVSE_MAX_LPAD && hidden % 8 == 0 && (dt != XML_F16S || hidden % 32 == 0);
+}
+constexpr bool convse_shape_ok(int lpad, int l_ref, int hidden, int ksize, int dt) {
+  return rescore_shape_ok(lpad, hidden, dt) && l_ref > 0 && l_ref <= lpad && (ksize & 1) && ksize >= 1 && ksize <= CONVSE_MAX_KSIZE;
+}
+// the LDS-DMA mainloop (gemm.h): rows are whole 128-byte K steps and every row offset -- of the nq query rows, of a video's
+// lpad clip rows -- fits the 32 bits it is addressed with; otherwise the register-staged loop with its zero-filled K tail
+constexpr bool convse_dma(int64_t nq, int lpad, int hidden, int dt) {
+  const int64_t kb = (int64_t)hidden * (int64_t)dt_size(dt);
+  return kb % CONVSE_STEP_BYTES == 0 && nq * kb < (1ll << 32) && (int64_t)lpad * kb < (1ll << 32);
+}
+// split rows are whole 128-byte steps by construction (hidden % 32 == 0): without the DMA loop (offsets past 32 bits) refused
+constexpr xml_convse_mainloop convse_mainloop(int64_t nq, int lpad, int hidden, int dt) {
+  return convse_dma(nq, lpad, hidden, dt) ? XML_CONVSE_DMA : dt == XML_F16S ? XML_CONVSE_REFUSED : XML_CONVSE_STAGED;
+}
+constexpr int convse_sub(int64_t P, int nv) { return P >= CONVSE_SUB_MIN_PAIRS_PER_VIDEO * (int64_t)nv ? CONVSE_SUB_MAX : 1; }
+constexpr bool convse_small_inversion(int64_t P, int nv) { return P <= CONVSE_SMALL_P && nv <= CONVSE_SMALL_NV; }
+// K7 / span evidence; the re-score always counts in global memory (it has no rows to zero-fill in the same pass)
+constexpr xml_convse_inversion convse_inversion(int64_t P, int nv, bool rescore) {
+  if (!rescore && convse_small_inversion(P, nv)) return XML_CONVSE_INV_SMALL;
+  return convse_sub(P, nv) > 1 ? XML_CONVSE_INV_SUB : XML_CONVSE_INV_GLOBAL;
+}
+// rows per chunk of the re-score: 128 when the average video is listed by more than 64 pairs (then most videos would need
+// two 64-row chunks, each fetching the tile again)
+constexpr int rescore_chunk_pairs(int64_t P, int nv, int dt) {
+  return dt == XML_F16S && P > CONVSE_TM * (int64_t)nv ? RESCORE_TM_BIG : CONVSE_TM;
+}
+// chunks a launch must provide for: every video ends in at most one partly filled chunk
+constexpr int64_t convse_max_chunks(int64_t P, int nv, int tm) { return P / tm + (P < nv ? P : nv); }
+// K7's epilogue: half a wave per pair row and four clips per lane for the as-trained 5 taps, else the general row loop
+// (which also forms the candidate summaries)
+// (a macro: convse_kernel branches on it with the summaries' pointer as `summ`, evaluated only behind the ksize test -- as a
+// function call, whose arguments are evaluated first, the kernel came out with another register allocation)
+#define XML_CONVSE_FAST_EPILOGUE(ksize, summ) ((ksize) == dispatch::CONVSE_FAST_KSIZE && !(summ))
+constexpr bool convse_fast_epilogue(int ksize, bool summ) { return XML_CONVSE_FAST_EPILOGUE(ksize, summ); }
+
 // ---- L2 normalisation: the 16-byte kernel, half a wave (32 lanes) per row, up to L2N_MAXJ chunks per lane ------------
 constexpr int L2N_MAXJ = 8, L2N_LANES = 32;       // rows of up to 32 * 8 chunks = 4096 bytes
 constexpr bool l2n_vec_ok(int d, int dt) {
