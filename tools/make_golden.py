@@ -533,6 +533,46 @@ def gen_train_collate_case(ns, name, seed):
     print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
 
 
+def gen_eval_collate_tef_case(ns, name, seed, n, dims, max_l, bsz):
+    """Corpus-side collate of the *_tef context modes: what the reference's StartEndEvalDataset._get_item_context
+    (xml/start_end_dataset.py:297-343: truncate, l2_normalize_np_array, the temporal endpoint feature of 328-342 appended to
+    every used stream) and start_end_collate (346-359) hand to the model.  The dataset object is made with __new__ (its
+    __init__ opens h5 files) and the two handlers are plain dicts of arrays.  The world of gen_ingest_case: n videos, some
+    longer than max_l, one of a single clip, an all-zero clip.  Stored: the raw arrays + lengths and, per mode, each batch's
+    padded video_feat / sub_feat (d + 2 columns) and masks."""
+    from baselines.crossmodal_moment_localization import start_end_dataset as sed
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(3, max_l + 20, n)
+    lens[1] = 1
+    vids = ["vid_%d" % i for i in range(n)]
+    out = dict(lens=lens.astype(np.int64), max_l=np.int64(max_l), bsz=np.int64(bsz), dims=np.array(dims, dtype=np.int64))
+    raw = {}
+    for tag, dim in zip(("video", "sub"), dims):
+        rows = [(rng.standard_normal((int(l), dim)) * rng.uniform(0.05, 3.0)).astype(np.float32) for l in lens]
+        rows[2][0] = 0.0                                        # an all-zero clip: x / (0 + eps) stays 0
+        raw[tag] = dict(zip(vids, rows))
+        out["raw/" + tag] = np.concatenate(rows, 0)
+    modes = ("video_sub_tef", "video_tef", "sub_tef")
+    out["modes"] = np.array(json.dumps(modes))
+    for mode in modes:
+        ds = sed.StartEndEvalDataset.__new__(sed.StartEndEvalDataset)
+        ds.ctx_mode, ds.max_ctx_len, ds.clip_length = mode, max_l, 1.5
+        ds.use_video, ds.use_sub, ds.use_tef = "video" in mode, "sub" in mode, "tef" in mode
+        ds.video_data = [dict(vid_name=v, duration=float(l) * 1.5) for v, l in zip(vids, lens)]
+        ds.vid_feat_h5, ds.sub_bert_h5 = raw["video"], raw["sub"]
+        ds.normalize_vfeat = ds.normalize_tfeat = True
+        for b in range(0, n, bsz):
+            _, batched = sed.start_end_collate([ds._get_item_context(i) for i in range(b, min(b + bsz, n))])
+            for tag in ("video", "sub"):
+                if tag in mode:
+                    feat, mask = batched[tag + "_feat"]
+                    out["%s/batch%d/%s_feat" % (mode, b // bsz, tag)] = feat.numpy()
+                    out["%s/batch%d/%s_mask" % (mode, b // bsz, tag)] = mask.numpy()
+    path = os.path.join(OUT_DIR, name + ".npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 def gen_visualization_case(ns, name, cfg, seed, n, len_lo, len_hi, lq_lo, lq_hi):
     """XML.get_visualization_data (xml/model_xml.py:253-289) on a batch of n (query, video) examples: the modular
     attention weights and the per-clip evidence behind the span logits.  The reference returns a list of per-example dicts
@@ -601,7 +641,7 @@ def main():
     if only:      # regenerate a subset: python tools/make_golden.py train_step
         g = globals()
         for fn in ("gen_model_case", "gen_pipeline_case", "gen_external_vr_case", "gen_eval_case", "gen_train_case",
-                   "gen_ingest_case", "gen_train_collate_case", "gen_visualization_case"):
+                   "gen_ingest_case", "gen_train_collate_case", "gen_eval_collate_tef_case", "gen_visualization_case"):
             orig = g[fn]
             g[fn] = (lambda o: lambda ns, name, *a, **k: o(ns, name, *a, **k) if only in name else None)(orig)
     ap = argparse.ArgumentParser()
@@ -644,6 +684,7 @@ def main():
                              hard_pool_size=3), 32, bsz=7, len_lo=5, len_hi=19)
     gen_ingest_case(ns, "ingest_collate", 51, n=11, dims=(48, 32), max_l=40, bsz=4)
     gen_train_collate_case(ns, "train_collate", 52)
+    gen_eval_collate_tef_case(ns, "eval_collate_tef", 51, n=11, dims=(48, 32), max_l=40, bsz=4)
     # staged: two steps without the span loss, then three with it (t_total 10, warmup 0.1: the late tensors see multiplier
     # 0 at THEIR step 0 while the early ones are already decaying)
     gen_train_case(ns, "train_step_staged_video_sub_h128",

@@ -301,6 +301,14 @@ SIGNATURES_INGEST_POOL = {
                                      c_void_p, c_void_p] + [c_int] * 3 + [c_float, c_int, c_int, c_void_p]),
 }
 
+# the companion header include/xmlhip_ingest_tef.h (tests/test_ingest_tef_capi.py checks): the two ingest launches with the
+# temporal endpoint columns of the *_tef context modes
+SIGNATURES_INGEST_TEF = {
+    "xml_ingest_rows_tef": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                    c_int, c_float, c_int, c_void_p]),
+    "xml_ingest_pool_rows_tef": (c_int, SIGNATURES_INGEST_POOL["xml_ingest_pool_rows"][1][:-1] + [c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 
 
@@ -309,7 +317,7 @@ def bind(lib):
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
             list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()) + \
             list(SIGNATURES_EXACT_PACKED.items()) + list(SIGNATURES_PARTS_EXACT.items()) + \
-            list(SIGNATURES_INGEST_POOL.items()):
+            list(SIGNATURES_INGEST_POOL.items()) + list(SIGNATURES_INGEST_TEF.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

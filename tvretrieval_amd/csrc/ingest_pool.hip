@@ -16,8 +16,9 @@
 // reads (source rows named by the batch) * d * 2 B, writes n * lmax * (d_a + d_b) * 4 B (f32) or * 2 B (bf16).
 #include <hip/hip_fp16.h>
 
-#include "../../include/xmlhip_ingest_pool.h"
+#include "../../include/xmlhip_ingest_tef.h"
 #include "common.h"
+#include "ingest_tef.h"
 
 namespace {
 
@@ -53,13 +54,17 @@ __device__ __forceinline__ void pool_range(const int64_t* __restrict__ seg, int6
 }
 
 // NCH: chunks of 512 columns the row may span (d_a + d_b <= NCH * 512).  VEC: d_a % 8 == 0, d_b % 8 == 0 and all of src_a,
-// src_b, dst 16-byte aligned -- a lane's 8 columns belong to one source and move as 16-byte pieces.
-template <typename D, int NCH, bool VEC>
+// src_b, dst 16-byte aligned -- a lane's 8 columns belong to one source and move as 16-byte pieces.  TEF
+// (xmlhip_ingest_tef.h): the row is d_a + d_b + 2 columns wide and ends in the temporal endpoint columns; VEC then asks nothing of
+// dst (its pitch is never a multiple of 16): the loads are the same 16-byte pieces, the stores as wide as dst_align allows.  The
+// feature columns are computed by the same statements either way.
+template <typename D, int NCH, bool VEC, bool TEF>
 __global__ __launch_bounds__(256) void ingest_pool_kernel(
     const char* __restrict__ src_a, int f16_a, int64_t rows_a, int d_a, const int64_t* __restrict__ seg_a, int norm_a,
     const char* __restrict__ src_b, int f16_b, int64_t rows_b, int d_b, const int64_t* __restrict__ seg_b, int norm_b,
     const int64_t* __restrict__ row_start, D* __restrict__ dst, float* __restrict__ mask, float* __restrict__ filled, int n,
-    int lmax, int max_len, float eps, int normalize, int pool_mean) {
+    int lmax, int max_len, float eps, int normalize, int pool_mean, const int32_t* __restrict__ tef_pos,
+    const int32_t* __restrict__ tef_len, int dst_align) {
   const int lane = threadIdx.x & 63;
   const int d = d_a + d_b;
   const int64_t total = (int64_t)n * lmax;
@@ -67,13 +72,15 @@ __global__ __launch_bounds__(256) void ingest_pool_kernel(
     const int i = (int)(r / lmax), l = (int)(r - (int64_t)i * lmax);
     const int64_t first = row_start[i];
     const int len = (int)min((int64_t)max_len, row_start[i + 1] - first);
-    D* out = dst + r * d;
+    D* out = dst + r * (d + (TEF ? 2 : 0));
     if (l >= len) {
       if (lane == 0) {
         if (mask) mask[r] = 0.f;
         if (filled) filled[r] = 0.f;
       }
-      if (VEC) {
+      if (TEF) {
+        tef_zero_row(reinterpret_cast<char*>(out), (int64_t)(d + 2) * (int64_t)sizeof(D), dst_align, lane);
+      } else if (VEC) {
         const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (int c = lane * 8; c < d; c += POOL_CHUNK) st8<D>(out + c, z);
       } else {
@@ -207,7 +214,9 @@ __global__ __launch_bounds__(256) void ingest_pool_kernel(
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       const int c0 = ch * POOL_CHUNK + lane * 8;
-      if (VEC) {
+      if (VEC && TEF) {
+        if (c0 < d) tef_st8<D>(out + c0, acc[ch], dst_align);
+      } else if (VEC) {
         if (c0 < d) st8<D>(out + c0, acc[ch]);
       } else {
 #pragma unroll
@@ -215,25 +224,33 @@ __global__ __launch_bounds__(256) void ingest_pool_kernel(
           if (c0 + j < d) DT<D>::st(out + c0 + j, acc[ch][j]);
       }
     }
+    if (TEF && lane == 0) {
+      int P, L;
+      float t_st, t_ed;
+      tef_place(tef_pos, tef_len, i, len, P, L);
+      tef_values(P + l, L, t_st, t_ed);
+      tef_store<D>(out + d, d, t_st, t_ed, dst_align);
+    }
   }
 }
 
-template <typename D, int NCH, bool VEC>
+template <typename D, int NCH, bool VEC, bool TEF>
 void launch_pool(dim3 grid, hipStream_t st, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a,
                  int norm_a, const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b, int norm_b,
                  const int64_t* row_start, void* dst, float* mask, float* filled, int n, int lmax, int max_len, float eps,
-                 int normalize, int pool) {
-  hipLaunchKernelGGL((ingest_pool_kernel<D, NCH, VEC>), grid, dim3(256), 0, st, (const char*)src_a, (int)(src_dt_a == XML_F16),
+                 int normalize, int pool, const int32_t* tef_pos, const int32_t* tef_len, int dst_align) {
+  hipLaunchKernelGGL((ingest_pool_kernel<D, NCH, VEC, TEF>), grid, dim3(256), 0, st, (const char*)src_a, (int)(src_dt_a == XML_F16),
                      rows_a, d_a, seg_a, norm_a, (const char*)src_b, (int)(src_dt_b == XML_F16), rows_b, d_b, seg_b, norm_b,
-                     row_start, (D*)dst, mask, filled, n, lmax, max_len, eps, normalize, (int)(pool == XML_POOL_MEAN));
+                     row_start, (D*)dst, mask, filled, n, lmax, max_len, eps, normalize, (int)(pool == XML_POOL_MEAN),
+                     tef_pos, tef_len, dst_align);
 }
 
-}  // namespace
+// tef: the entry with the endpoint columns (tef_pos / tef_len may still be NULL)
+int ingest_pool_entry(bool tef, int n_src, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a, int norm_a,
+                      const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b, int norm_b,
+                      const int64_t* row_start, void* dst, int dst_dt, float* mask, float* filled, int n, int lmax, int max_len,
+                      float eps, int normalize, int pool, const int32_t* tef_pos, const int32_t* tef_len, xml_stream_t stream) {
 
-extern "C" int xml_ingest_pool_rows(int n_src, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a,
-                                    int norm_a, const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b,
-                                    int norm_b, const int64_t* row_start, void* dst, int dst_dt, float* mask, float* filled,
-                                    int n, int lmax, int max_len, float eps, int normalize, int pool, xml_stream_t stream) {
   XML_ENTER();
   if (n_src != 1 && n_src != 2) return XML_ERR_BAD_ARG;
   if (!src_a || !seg_a || !row_start || !dst || n <= 0 || lmax <= 0 || max_len <= 0 || d_a <= 0 || rows_a <= 0) return XML_ERR_BAD_ARG;
@@ -246,27 +263,53 @@ extern "C" int xml_ingest_pool_rows(int n_src, const void* src_a, int src_dt_a, 
   }
   if (dst_dt != XML_F32 && dst_dt != XML_BF16) return XML_ERR_BAD_ARG;
   if (pool != XML_POOL_MAX && pool != XML_POOL_MEAN) return XML_ERR_BAD_ARG;
+  if ((tef_pos == nullptr) != (tef_len == nullptr)) return XML_ERR_BAD_ARG;
   if ((int64_t)d_a + d_b > POOL_MAX_D) return XML_ERR_UNSUPPORTED;
   const int d = d_a + d_b;
-  const bool vec = d_a % 8 == 0 && d_b % 8 == 0 &&
-                   ((reinterpret_cast<uintptr_t>(src_a) | reinterpret_cast<uintptr_t>(src_b) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  // with the endpoint columns the destination decides the store width only, never the load width
+  const uintptr_t vec_ptrs = reinterpret_cast<uintptr_t>(src_a) | reinterpret_cast<uintptr_t>(src_b) |
+                             (tef ? (uintptr_t)0 : reinterpret_cast<uintptr_t>(dst));
+  const bool vec = d_a % 8 == 0 && d_b % 8 == 0 && (vec_ptrs & 15) == 0;
+  const int dst_align = tef ? tef_pow2_align(reinterpret_cast<uintptr_t>(dst), ((int64_t)d + 2) * (dst_dt == XML_F32 ? 4 : 2)) : 0;
   // memory-bound: at most 256 CUs x 8 workgroups, the rest by grid stride
   const int64_t rows = (int64_t)n * lmax;
   const dim3 grid((unsigned)min((rows + 3) / 4, (int64_t)2048));
   hipStream_t st = (hipStream_t)stream;
-#define XML_POOL(D, NCH, VEC) \
-  launch_pool<D, NCH, VEC>(grid, st, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b, \
-                           row_start, dst, mask, filled, n, lmax, max_len, eps, normalize, pool)
-#define XML_POOL_W(D, VEC)                 \
+#define XML_POOL(D, NCH, VEC, TEF) \
+  launch_pool<D, NCH, VEC, TEF>(grid, st, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b, \
+                                row_start, dst, mask, filled, n, lmax, max_len, eps, normalize, pool, tef_pos, tef_len, dst_align)
+#define XML_POOL_W(D, VEC, TEF)                 \
   do {                                     \
-    if (d <= 2 * POOL_CHUNK) XML_POOL(D, 2, VEC); \
-    else if (d <= 6 * POOL_CHUNK) XML_POOL(D, 6, VEC); \
-    else XML_POOL(D, 8, VEC);              \
+    if (d <= 2 * POOL_CHUNK) XML_POOL(D, 2, VEC, TEF); \
+    else if (d <= 6 * POOL_CHUNK) XML_POOL(D, 6, VEC, TEF); \
+    else XML_POOL(D, 8, VEC, TEF);              \
   } while (0)
-  if (dst_dt == XML_F32) { if (vec) XML_POOL_W(float, true); else XML_POOL_W(float, false); }
-  else { if (vec) XML_POOL_W(bf16_t, true); else XML_POOL_W(bf16_t, false); }
+#define XML_POOL_V(D, TEF) \
+  do { if (vec) XML_POOL_W(D, true, TEF); else XML_POOL_W(D, false, TEF); } while (0)
+  if (dst_dt == XML_F32) { if (tef) XML_POOL_V(float, true); else XML_POOL_V(float, false); }
+  else { if (tef) XML_POOL_V(bf16_t, true); else XML_POOL_V(bf16_t, false); }
+#undef XML_POOL_V
 #undef XML_POOL_W
 #undef XML_POOL
   XML_CHECK_LAUNCH();
   return XML_OK;
+}
+
+}  // namespace
+
+extern "C" int xml_ingest_pool_rows(int n_src, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a,
+                                    int norm_a, const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b,
+                                    int norm_b, const int64_t* row_start, void* dst, int dst_dt, float* mask, float* filled,
+                                    int n, int lmax, int max_len, float eps, int normalize, int pool, xml_stream_t stream) {
+  return ingest_pool_entry(false, n_src, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b,
+                           row_start, dst, dst_dt, mask, filled, n, lmax, max_len, eps, normalize, pool, nullptr, nullptr, stream);
+}
+
+extern "C" int xml_ingest_pool_rows_tef(int n_src, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a,
+                                        int norm_a, const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b,
+                                        int norm_b, const int64_t* row_start, void* dst, int dst_dt, float* mask, float* filled,
+                                        int n, int lmax, int max_len, float eps, int normalize, int pool, const int32_t* tef_pos,
+                                        const int32_t* tef_len, xml_stream_t stream) {
+  return ingest_pool_entry(true, n_src, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b,
+                           row_start, dst, dst_dt, mask, filled, n, lmax, max_len, eps, normalize, pool, tef_pos, tef_len, stream);
 }

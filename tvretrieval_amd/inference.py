@@ -35,8 +35,8 @@ chain_members), both moments_decode(part_offset=) -- and the updates of an index
 index_clear_rows; with chains index_set_chains) and of an exact-rank one (index_put_rows_exact, exact_certificate_dev,
 index_exact_bound; with the packed filter image index_put_rows_packed_exact) and the subset views of
 video_subset (index_gather_blocks; HIP only, a search with subset= refuses any other backend) and a ContextFeeder over
-ingest.PooledStore frame- / word-level stores (ingest_pool_rows; HIP only) call further entries of
-tvretrieval_amd.ops; a backend without them serves every search that does not ask for those.
+ingest.PooledStore frame- / word-level stores (ingest_pool_rows; HIP only) or with a *_tef ctx_mode (ingest_rows /
+ingest_pool_rows with tef=True; HIP only) call further entries of tvretrieval_amd.ops; a backend without them serves every search that does not ask for those.
 """
 import types
 

@@ -11,7 +11,9 @@
                       pinned staging buffers (two, alternating) in the store's dtype and back to back, are copied
                       asynchronously on a side stream (the H2D copy of batch i+1 overlaps the encoder kernels of batch
                       i), and ONE device launch (xml_ingest_rows) truncates, pads, converts, normalises and writes
-                      the mask.
+                      the mask.  ctx_mode="video_sub_tef" / "video_tef" / "sub_tef": the launch (xml_ingest_rows_tef,
+                      xml_ingest_pool_rows_tef) also appends the reference's two temporal endpoint columns
+                      (start_end_dataset.py:328-342); the parts of a long video get WHOLE-VIDEO time.
   PooledStore         1-2 FRAME- or WORD-level FeatureStores (what a feature extractor emits) + the source-row range of every
                       clip; ContextFeeder takes one in place of a clip store: it stages the fine rows, and ONE launch
                       (xml_ingest_pool_rows) pools them into clips (max / mean), normalises each source, concatenates,
@@ -29,6 +31,7 @@ import numpy as np
 import torch
 
 from . import ops as hip_ops
+from .train_data import CTX_MODES
 
 _DT = {"float16": np.float16, "float32": np.float32}
 
@@ -309,6 +312,23 @@ def plan_parts(n_clips, max_ctx_len, overlap=16):
     return PartTable(pv.astype(np.int32), po.astype(np.int32), pl.astype(np.int32), gs.astype(np.int32), w, o)
 
 
+def _resolve_ctx_mode(who, ctx_mode, video_store, sub_store):
+    """ctx_mode=None: the streams are those whose stores are given, no endpoint columns.  Else one of train_data.CTX_MODES, which
+    must name exactly the streams whose stores are given.  -> whether the mode appends the temporal endpoint columns."""
+    if ctx_mode is None:
+        return False
+    if ctx_mode not in CTX_MODES:
+        raise ValueError("%s: ctx_mode %r: the model has %s (the endpoint columns ride on a video or subtitle stream)"
+                         % (who, ctx_mode, ", ".join(CTX_MODES)))
+    parts = ctx_mode.split("_")
+    for tag, store in (("video", video_store), ("sub", sub_store)):
+        if tag in parts and store is None:
+            raise ValueError("%s: ctx_mode %r needs a %s store" % (who, ctx_mode, tag))
+        if tag not in parts and store is not None:
+            raise ValueError("%s: a %s store is given, ctx_mode %r has no %s stream" % (who, tag, ctx_mode, tag))
+    return "tef" in parts
+
+
 class ContextFeeder(object):
     """Raw clip rows leave the host in the STORE's dtype (f16 on disk: half the PCIe bytes of the reference's f32 batches)
     and back to back -- runs of videos that are adjacent in the store are ONE copy from the memory map into the pinned
@@ -319,16 +339,28 @@ class ContextFeeder(object):
 
     def __init__(self, video_names, video_store=None, sub_store=None, max_ctx_len=100, batch_size=200,
                  normalize_vfeat=True, normalize_tfeat=True, device="cuda:0", ops=hip_ops, feature_dtype=torch.float32,
-                 host_threads=8, parts=None):
+                 host_threads=8, parts=None, ctx_mode=None):
         """feature_dtype=torch.bfloat16 (bf16 models only): the normalised features are handed over in bf16 -- the encoder's
         input LayerNorm reads half the bytes (the C ABI takes f32 or the compute dtype); the reference's contract is f32.
         parts (PartTable of plan_parts over these videos' clip counts, host): nothing is cut off -- the feeder iterates batches
         of PARTS, each the rows [offset, offset + len) of its video in the store; rows that two parts share are copied twice.
         video_store / sub_store may be a PooledStore (frame- / word-level rows): the fine rows a batch's clips name are staged
-        and copied instead, and xml_ingest_pool_rows pools them into clips in the collate launch; stats then count fine rows."""
+        and copied instead, and xml_ingest_pool_rows pools them into clips in the collate launch; stats then count fine rows.
+        ctx_mode (None, or one of train_data.CTX_MODES naming exactly the given stores): with a *_tef mode every feature tensor
+        is two columns wider -- the reference's temporal endpoint feature (start_end_dataset.py:328-342), written by the same
+        launch (xml_ingest_rows_tef / xml_ingest_pool_rows_tef).  The time axis is the truncated video, as there; with parts it
+        is the WHOLE video: a part's columns are the columns the unsplit video has at those clips."""
+        self.use_tef = _resolve_ctx_mode("ContextFeeder", ctx_mode, video_store, sub_store)
+        self.ctx_mode = ctx_mode
         self.feature_dtype = feature_dtype
         self.names, self.vs, self.ss = list(video_names), video_store, sub_store
         self.max_ctx_len, self.bsz = int(max_ctx_len), int(batch_size)
+        if self.use_tef and parts is None and video_store is not None and sub_store is not None:
+            for n in self.names:       # one endpoint feature serves both streams: the reference fails in torch.cat here
+                lv, ls = (min(int(st.n_rows(n)), self.max_ctx_len) for st in (video_store, sub_store))
+                if lv != ls:
+                    raise ValueError("ContextFeeder: video %r has %d video and %d subtitle clips after truncation; ctx_mode %r "
+                                     "appends one temporal endpoint feature to both" % (n, lv, ls, ctx_mode))
         self.parts = parts
         if parts is not None:
             if torch.is_tensor(parts.part_video):
@@ -337,6 +369,7 @@ class ContextFeeder(object):
                 raise ValueError("ContextFeeder: the part table covers %d videos at max_ctx_len %d, the feeder %d at %d"
                                  % (parts.n_videos, parts.max_ctx_len, len(self.names), self.max_ctx_len))
             counts = parts.n_clips()
+            self._part_total = counts
             for tag, store in (("video", video_store), ("sub", sub_store)):
                 if store is None:
                     continue
@@ -359,6 +392,23 @@ class ContextFeeder(object):
 
     def _n_items(self):
         return len(self.names) if self.parts is None else self.parts.n_parts
+
+    def _tef_kw(self, items, moved=None):
+        """Keywords of the ingest op for this batch: none without a *_tef mode (the op is called as ever); tef=True, and with
+        parts each part's place in its video (offset, whole clip count) as two (n,) int32 arrays -- copied like row_start: the
+        caller is inside the copy stream's context and record_stream()s what is appended to `moved`."""
+        if not self.use_tef:
+            return {}
+        if self.parts is None:
+            return dict(tef=True)
+        pt = self.parts
+        rows = np.arange(items.start, items.stop)
+        pos = torch.from_numpy(np.ascontiguousarray(pt.part_offset[rows], dtype=np.int32))
+        tot = torch.from_numpy(np.ascontiguousarray(self._part_total[pt.part_video[rows]], dtype=np.int32))
+        if self.device.type == "cuda":
+            pos, tot = pos.to(self.device, non_blocking=True), tot.to(self.device, non_blocking=True)
+            moved += [pos, tot]
+        return dict(tef=True, tef_pos=pos, tef_len=tot)
 
     def __len__(self):
         return (self._n_items() + self.bsz - 1) // self.bsz
@@ -493,6 +543,7 @@ class ContextFeeder(object):
                     self._slot_done[(tag, slot, si)] = done
                     sources.append((dev, dseg, pstore.norms[si]))
                     moved += [dev, dseg]
+                tef_kw = self._tef_kw(items, moved)
             cur.wait_stream(copy_stream)
             for t in moved:                      # allocated on the copy stream, consumed on the compute stream
                 t.record_stream(cur)
@@ -500,11 +551,12 @@ class ContextFeeder(object):
             dstart = start
             for si, (host, rows, seg) in enumerate(per_source):
                 sources.append((host[:max(rows, 1)].clone(), seg, pstore.norms[si]))
+            tef_kw = self._tef_kw(items)
         for si, (host, rows, seg) in enumerate(per_source):
             self.stats["rows"] += rows
             self.stats["h2d_bytes"] += rows * pstore.stores[si].dim * host.element_size()
         feat, mask = self.ops.ingest_pool_rows(sources, dstart, len(items), lmax, self.max_ctx_len, pool=pstore.pool,
-                                               normalize=self.norm[tag], eps=1e-5, out_dtype=self.feature_dtype)
+                                               normalize=self.norm[tag], eps=1e-5, out_dtype=self.feature_dtype, **tef_kw)
         return [feat, mask]
 
     def __iter__(self):
@@ -529,15 +581,18 @@ class ContextFeeder(object):
                         dstart = start.to(self.device, non_blocking=True)
                         done = torch.cuda.Event()
                         done.record(copy_stream)
+                        moved = [dev, dstart]
+                        tef_kw = self._tef_kw(names, moved)
                     self._slot_done[(tag, bi & 1)] = done
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_stream(copy_stream)
-                    dev.record_stream(cur)          # both were allocated on the copy stream and are consumed on the
-                    dstart.record_stream(cur)       # compute stream: keep the allocator from recycling them early
+                    for t in moved:                 # allocated on the copy stream and consumed on the compute stream: keep
+                        t.record_stream(cur)        # the allocator from recycling them early
                 else:
                     dev, dstart = host[:rows].clone(), start
+                    tef_kw = self._tef_kw(names)
                 feat, mask = self.ops.ingest_rows(dev, dstart, len(names), lmax, self.max_ctx_len, normalize=self.norm[tag],
-                                                  eps=1e-5, out_dtype=self.feature_dtype)
+                                                  eps=1e-5, out_dtype=self.feature_dtype, **tef_kw)
                 out += [feat, mask]
             yield tuple(out)
 
@@ -547,7 +602,11 @@ class StoreEvalDataset(object):
     (+ ts/type for evaluation); video_data: list of dicts with vid_name, duration; video2idx: name -> int."""
 
     def __init__(self, query_data, video_data, video2idx, desc_store, video_store=None, sub_store=None, max_desc_len=30,
-                 max_ctx_len=100, normalize_vfeat=True, normalize_tfeat=True):
+                 max_ctx_len=100, normalize_vfeat=True, normalize_tfeat=True, ctx_mode=None):
+        """ctx_mode (None, or one of train_data.CTX_MODES naming exactly the given stores): with a *_tef mode the context items
+        end in the two temporal endpoint columns, computed as the reference does (start_end_dataset.py:328-342)."""
+        self.use_tef = _resolve_ctx_mode("StoreEvalDataset", ctx_mode, video_store, sub_store)
+        self.ctx_mode = ctx_mode
         self.query_data, self.video_data, self.video2idx = query_data, video_data, video2idx
         self.desc, self.vs, self.ss = desc_store, video_store, sub_store
         self.max_desc_len, self.max_ctx_len = max_desc_len, max_ctx_len
@@ -573,12 +632,24 @@ class StoreEvalDataset(object):
         if self.data_mode == "context":
             v = self.video_data[i]
             mi = {}
+            ctx_l = 0
             if self.vs is not None:
                 f = self.vs[v["vid_name"]][:self.max_ctx_len]
                 mi["video_feat"] = self._norm(f) if self.nv else np.asarray(f, dtype=np.float32)
+                ctx_l = len(f)
             if self.ss is not None:
                 f = self.ss[v["vid_name"]][:self.max_ctx_len]
                 mi["sub_feat"] = self._norm(f) if self.nt else np.asarray(f, dtype=np.float32)
+                ctx_l = len(f)
+            if self.use_tef:           # the reference's lines, on the stream it takes the length from (the subtitles' if any)
+                tef_st = torch.arange(0, ctx_l, 1.0) / ctx_l
+                tef = torch.stack([tef_st, tef_st + 1.0 / ctx_l], dim=1).numpy()
+                for k in list(mi):
+                    if len(mi[k]) != ctx_l:
+                        raise ValueError("StoreEvalDataset: video %r has %d %s rows and %d endpoint rows after truncation; "
+                                         "ctx_mode %r appends one temporal endpoint feature to both streams"
+                                         % (v["vid_name"], len(mi[k]), k, ctx_l, self.ctx_mode))
+                    mi[k] = np.concatenate([mi[k], tef], axis=1)
             return dict(meta=dict(vid_name=v["vid_name"], duration=v.get("duration", 0.0)), model_inputs=mi)
         q = self.query_data[i]
         f = self.desc[str(q["desc_id"])][:self.max_desc_len]

@@ -304,12 +304,38 @@ def l2norm_rows_eps(x, eps=1e-5):
     return y
 
 
-def ingest_rows(src, row_start, n, lmax, max_len, normalize=True, eps=1e-5, out_dtype=torch.float32):
+def _tef_place(what, tef, tef_pos, tef_len, n):
+    """The optional (n,) int32 tef_pos / tef_len of the *_tef ingest entries: both or neither, and only with tef=True."""
+    if (tef_pos is None) != (tef_len is None):
+        raise _lib.XmlHipError("%s: tef_pos and tef_len are given both or neither" % what)
+    if tef_pos is None:
+        return
+    if not tef:
+        raise _lib.XmlHipError("%s: tef_pos / tef_len need tef=True" % what)
+    for t, name in ((tef_pos, "tef_pos"), (tef_len, "tef_len")):
+        _req(t, name, torch.int32)
+        if t.dim() != 1 or t.numel() != n:
+            raise _lib.XmlHipError("%s: %s must hold n = %d entries" % (what, name, n))
+
+
+def ingest_rows(src, row_start, n, lmax, max_len, normalize=True, eps=1e-5, out_dtype=torch.float32, tef=False, tef_pos=None,
+                tef_len=None):
     """Context collate on the device (xml_ingest_rows): src (rows, d) f32 / f16 = the batch's raw clip rows back to back,
-    row_start (n + 1,) int64 -> (features (n, lmax, d) out_dtype [x / (||x|| + eps) per clip, zero padding], mask (n, lmax))."""
+    row_start (n + 1,) int64 -> (features (n, lmax, d) out_dtype [x / (||x|| + eps) per clip, zero padding], mask (n, lmax)).
+    tef=True (xml_ingest_rows_tef): features are (n, lmax, d + 2), the d columns as before plus the temporal endpoint columns
+    (P + l) / L and that + 1 / L of the *_tef context modes; P = tef_pos[i], L = tef_len[i] ((n,) int32, for the parts of a
+    long video) or P = 0, L = the item's truncated length."""
     _req(src, "src"); _req(row_start, "row_start", torch.int64)
     assert src.dtype in (torch.float32, torch.float16) and row_start.numel() == n + 1
     d = src.shape[-1]
+    _tef_place("ingest_rows", tef, tef_pos, tef_len, int(n))
+    if tef:
+        out = torch.empty((n, lmax, d + 2), dtype=out_dtype, device=src.device)
+        mask = torch.empty((n, lmax), dtype=torch.float32, device=src.device)
+        check(_lib.load().xml_ingest_rows_tef(_p(src), dt_of(src), _p(row_start), _p(tef_pos), _p(tef_len), _p(out),
+                                              dt_of(out_dtype), _p(mask), int(n), int(lmax), d, int(max_len), float(eps),
+                                              int(bool(normalize)), _stream()), "xml_ingest_rows_tef")
+        return out, mask
     out = torch.empty((n, lmax, d), dtype=out_dtype, device=src.device)
     mask = torch.empty((n, lmax), dtype=torch.float32, device=src.device)
     check(_lib.load().xml_ingest_rows(_p(src), dt_of(src), _p(row_start), _p(out), dt_of(out_dtype), _p(mask), int(n), int(lmax),
@@ -322,13 +348,15 @@ POOLS = {"max": 0, "mean": 1}         # XML_POOL_MAX / XML_POOL_MEAN
 
 
 def ingest_pool_rows(sources, row_start, n, lmax, max_len, pool="max", normalize=True, eps=1e-5, out_dtype=torch.float32,
-                     want_filled=False):
+                     want_filled=False, tef=False, tef_pos=None, tef_len=None):
     """Context collate with clip pooling on the device (xml_ingest_pool_rows): sources = 1 or 2 tuples (src, seg, norm) -- src
     (rows_x, d_x) f16 / f32 rows FINER than clips (frames, words), seg (R, 2) int64 on the device: the half-open source-row range
     of each of the batch's R = row_start[n] clip rows (an empty or out-of-range range gives a zero block), norm: x / (||x|| + eps)
     on that source's pooled block.  row_start (n + 1,) int64 clip rows per video, back to back -> (features (n, lmax, sum d_x)
     out_dtype [max or mean over each range, per-source norm, with normalize the norm of the whole row, zero padding], mask
-    (n, lmax)) and with want_filled also filled (n, lmax): 1 where a source had rows for the clip."""
+    (n, lmax)) and with want_filled also filled (n, lmax): 1 where a source had rows for the clip.
+    tef=True (xml_ingest_pool_rows_tef): features are (n, lmax, sum d_x + 2), ending in the temporal endpoint columns; tef_pos /
+    tef_len as in ingest_rows."""
     if len(sources) not in (1, 2):
         raise _lib.XmlHipError("ingest_pool_rows: 1 or 2 sources expected, got %d" % len(sources))
     if pool not in POOLS:
@@ -349,9 +377,15 @@ def ingest_pool_rows(sources, row_start, n, lmax, max_len, pool="max", normalize
     if len(sources) == 1:
         args += [None, 0, 0, 0, None, 0]
     dev = sources[0][0].device
-    out = torch.empty((n, lmax, d), dtype=out_dtype, device=dev)
+    _tef_place("ingest_pool_rows", tef, tef_pos, tef_len, n)
+    out = torch.empty((n, lmax, d + (2 if tef else 0)), dtype=out_dtype, device=dev)
     mask = torch.empty((n, lmax), dtype=torch.float32, device=dev)
     filled = torch.empty((n, lmax), dtype=torch.float32, device=dev) if want_filled else None
+    if tef:
+        check(_lib.load().xml_ingest_pool_rows_tef(len(sources), *args, _p(row_start), _p(out), dt_of(out_dtype), _p(mask),
+                                                   _p(filled), n, lmax, int(max_len), float(eps), int(bool(normalize)), POOLS[pool],
+                                                   _p(tef_pos), _p(tef_len), _stream()), "xml_ingest_pool_rows_tef")
+        return (out, mask, filled) if want_filled else (out, mask)
     check(_lib.load().xml_ingest_pool_rows(len(sources), *args, _p(row_start), _p(out), dt_of(out_dtype), _p(mask), _p(filled), n,
                                            lmax, int(max_len), float(eps), int(bool(normalize)), POOLS[pool], _stream()),
           "xml_ingest_pool_rows")
