@@ -309,6 +309,14 @@ SIGNATURES_INGEST_TEF = {
     "xml_ingest_pool_rows_tef": (c_int, SIGNATURES_INGEST_POOL["xml_ingest_pool_rows"][1][:-1] + [c_void_p, c_void_p, c_void_p]),
 }
 
+# the companion header include/xmlhip_train_pool.h (tests/test_train_pool_capi.py checks): training batches from resident frame-
+# and word-level stores -- clip pooling in the batch gather
+SIGNATURES_TRAIN_POOL = {
+    "xml_gather_pool_feature_rows": (c_int, [c_int] + [c_void_p, c_int, c_int64, c_int, c_void_p, c_int] * 2 + [
+        c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int,
+        c_int, c_void_p]),
+}
+
 _lib = None
 
 
@@ -317,7 +325,7 @@ def bind(lib):
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
             list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()) + \
             list(SIGNATURES_EXACT_PACKED.items()) + list(SIGNATURES_PARTS_EXACT.items()) + \
-            list(SIGNATURES_INGEST_POOL.items()) + list(SIGNATURES_INGEST_TEF.items()):
+            list(SIGNATURES_INGEST_POOL.items()) + list(SIGNATURES_INGEST_TEF.items()) + list(SIGNATURES_TRAIN_POOL.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

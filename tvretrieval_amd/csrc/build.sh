@@ -29,7 +29,7 @@ build() {   # $1 = object dir, $2 = extra flags, $3 = output, $4.. = sources
        || [ ../../include/xmlhip_index_exact.h -nt "$o" ] || [ ../../include/xmlhip_index_view.h -nt "$o" ] \
        || [ ../../include/xmlhip_index_exact_packed.h -nt "$o" ] || [ ../../include/xmlhip_index_parts_exact.h -nt "$o" ] \
        || [ ../../include/xmlhip_ingest_pool.h -nt "$o" ] || [ ../../include/xmlhip_ingest_tef.h -nt "$o" ] \
-       || [ ingest_tef.h -nt "$o" ]; then
+       || [ ../../include/xmlhip_train_pool.h -nt "$o" ] || [ ingest_tef.h -nt "$o" ]; then
       $HIPCC $FLAGS $extra -I. -c "$s" -o "$o" &
       pids+=($!)
     fi

@@ -16,7 +16,7 @@
 // reads (source rows named by the batch) * d * 2 B, writes n * lmax * (d_a + d_b) * 4 B (f32) or * 2 B (bf16).
 #include <hip/hip_fp16.h>
 
-#include "../../include/xmlhip_ingest_tef.h"
+#include "../../include/xmlhip_train_pool.h"
 #include "common.h"
 #include "ingest_tef.h"
 
@@ -57,21 +57,40 @@ __device__ __forceinline__ void pool_range(const int64_t* __restrict__ seg, int6
 // src_b, dst 16-byte aligned -- a lane's 8 columns belong to one source and move as 16-byte pieces.  TEF
 // (xmlhip_ingest_tef.h): the row is d_a + d_b + 2 columns wide and ends in the temporal endpoint columns; VEC then asks nothing of
 // dst (its pitch is never a multiple of 16): the loads are the same 16-byte pieces, the stores as wide as dst_align allows.  The
-// feature columns are computed by the same statements either way.
-template <typename D, int NCH, bool VEC, bool TEF>
+// feature columns are computed by the same statements either way.  GATHER (xmlhip_train_pool.h): the training gather over a RESIDENT
+// store -- row_start is the store's clip_start over n_items items and batch position i names its item through ids -> item_of;
+// only how `first` and `len` are found differs (three dependent wave-uniform loads, as in train_batch.hip), the row body is the
+// one below.  Without GATHER the five gather arguments are not read.
+template <typename D, int NCH, bool VEC, bool TEF, bool GATHER>
 __global__ __launch_bounds__(256) void ingest_pool_kernel(
     const char* __restrict__ src_a, int f16_a, int64_t rows_a, int d_a, const int64_t* __restrict__ seg_a, int norm_a,
     const char* __restrict__ src_b, int f16_b, int64_t rows_b, int d_b, const int64_t* __restrict__ seg_b, int norm_b,
     const int64_t* __restrict__ row_start, D* __restrict__ dst, float* __restrict__ mask, float* __restrict__ filled, int n,
     int lmax, int max_len, float eps, int normalize, int pool_mean, const int32_t* __restrict__ tef_pos,
-    const int32_t* __restrict__ tef_len, int dst_align) {
+    const int32_t* __restrict__ tef_len, int dst_align, int64_t n_items, const int32_t* __restrict__ ids,
+    const int32_t* __restrict__ item_of, int64_t n_examples, int32_t* __restrict__ len_out) {
   const int lane = threadIdx.x & 63;
   const int d = d_a + d_b;
   const int64_t total = (int64_t)n * lmax;
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < total; r += (int64_t)gridDim.x * 4) {
     const int i = (int)(r / lmax), l = (int)(r - (int64_t)i * lmax);
-    const int64_t first = row_start[i];
-    const int len = (int)min((int64_t)max_len, row_start[i + 1] - first);
+    int64_t first;
+    int len;
+    if constexpr (GATHER) {
+      // example -> item -> clip rows; anything out of range is an empty example (train_batch.hip)
+      int64_t item = ids[i];
+      if (item_of) item = (item >= 0 && item < n_examples) ? (int64_t)item_of[item] : -1;
+      first = 0;
+      len = 0;
+      if (item >= 0 && item < n_items) {
+        first = row_start[item];
+        len = (int)max((int64_t)0, min(row_start[item + 1] - first, (int64_t)min(max_len, lmax)));
+      }
+      if (lane == 0 && l == 0 && len_out) len_out[i] = len;
+    } else {
+      first = row_start[i];
+      len = (int)min((int64_t)max_len, row_start[i + 1] - first);
+    }
     D* out = dst + r * (d + (TEF ? 2 : 0));
     if (l >= len) {
       if (lane == 0) {
@@ -234,15 +253,57 @@ __global__ __launch_bounds__(256) void ingest_pool_kernel(
   }
 }
 
-template <typename D, int NCH, bool VEC, bool TEF>
+template <typename D, int NCH, bool VEC, bool TEF, bool GATHER>
 void launch_pool(dim3 grid, hipStream_t st, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a,
                  int norm_a, const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b, int norm_b,
                  const int64_t* row_start, void* dst, float* mask, float* filled, int n, int lmax, int max_len, float eps,
-                 int normalize, int pool, const int32_t* tef_pos, const int32_t* tef_len, int dst_align) {
-  hipLaunchKernelGGL((ingest_pool_kernel<D, NCH, VEC, TEF>), grid, dim3(256), 0, st, (const char*)src_a, (int)(src_dt_a == XML_F16),
+                 int normalize, int pool, const int32_t* tef_pos, const int32_t* tef_len, int dst_align, int64_t n_items,
+                 const int32_t* ids, const int32_t* item_of, int64_t n_examples, int32_t* len_out) {
+  hipLaunchKernelGGL((ingest_pool_kernel<D, NCH, VEC, TEF, GATHER>), grid, dim3(256), 0, st, (const char*)src_a, (int)(src_dt_a == XML_F16),
                      rows_a, d_a, seg_a, norm_a, (const char*)src_b, (int)(src_dt_b == XML_F16), rows_b, d_b, seg_b, norm_b,
                      row_start, (D*)dst, mask, filled, n, lmax, max_len, eps, normalize, (int)(pool == XML_POOL_MEAN),
-                     tef_pos, tef_len, dst_align);
+                     tef_pos, tef_len, dst_align, n_items, ids, item_of, n_examples, len_out);
+}
+
+// The launch both entries end in.  gather: row_start is clip_start over n_items items, ids / item_of / n_examples / len_out as in
+// xml_gather_feature_rows; otherwise they are unused.
+int pool_dispatch(bool tef, bool gather, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a, int norm_a,
+                  const void* src_b, int src_dt_b, int64_t rows_b, int d_b, const int64_t* seg_b, int norm_b,
+                  const int64_t* row_start, void* dst, int dst_dt, float* mask, float* filled, int n, int lmax, int max_len, float eps,
+                  int normalize, int pool, const int32_t* tef_pos, const int32_t* tef_len, int64_t n_items, const int32_t* ids,
+                  const int32_t* item_of, int64_t n_examples, int32_t* len_out, xml_stream_t stream) {
+  const int d = d_a + d_b;
+  // with the endpoint columns the destination decides the store width only, never the load width
+  const uintptr_t vec_ptrs = reinterpret_cast<uintptr_t>(src_a) | reinterpret_cast<uintptr_t>(src_b) |
+                             (tef ? (uintptr_t)0 : reinterpret_cast<uintptr_t>(dst));
+  const bool vec = d_a % 8 == 0 && d_b % 8 == 0 && (vec_ptrs & 15) == 0;
+  const int dst_align = tef ? tef_pow2_align(reinterpret_cast<uintptr_t>(dst), ((int64_t)d + 2) * (dst_dt == XML_F32 ? 4 : 2)) : 0;
+  // memory-bound: at most 256 CUs x 8 workgroups, the rest by grid stride
+  const int64_t rows = (int64_t)n * lmax;
+  const dim3 grid((unsigned)min((rows + 3) / 4, (int64_t)2048));
+  hipStream_t st = (hipStream_t)stream;
+#define XML_POOL(D, NCH, VEC, TEF, G) \
+  launch_pool<D, NCH, VEC, TEF, G>(grid, st, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b, \
+                                   row_start, dst, mask, filled, n, lmax, max_len, eps, normalize, pool, tef_pos, tef_len, dst_align, \
+                                   n_items, ids, item_of, n_examples, len_out)
+#define XML_POOL_W(D, VEC, TEF, G)                 \
+  do {                                     \
+    if (d <= 2 * POOL_CHUNK) XML_POOL(D, 2, VEC, TEF, G); \
+    else if (d <= 6 * POOL_CHUNK) XML_POOL(D, 6, VEC, TEF, G); \
+    else XML_POOL(D, 8, VEC, TEF, G);              \
+  } while (0)
+#define XML_POOL_V(D, TEF, G) \
+  do { if (vec) XML_POOL_W(D, true, TEF, G); else XML_POOL_W(D, false, TEF, G); } while (0)
+#define XML_POOL_T(D, G) \
+  do { if (tef) XML_POOL_V(D, true, G); else XML_POOL_V(D, false, G); } while (0)
+  if (dst_dt == XML_F32) { if (gather) XML_POOL_T(float, true); else XML_POOL_T(float, false); }
+  else { if (gather) XML_POOL_T(bf16_t, true); else XML_POOL_T(bf16_t, false); }
+#undef XML_POOL_T
+#undef XML_POOL_V
+#undef XML_POOL_W
+#undef XML_POOL
+  XML_CHECK_LAUNCH();
+  return XML_OK;
 }
 
 // tef: the entry with the endpoint columns (tef_pos / tef_len may still be NULL)
@@ -265,34 +326,9 @@ int ingest_pool_entry(bool tef, int n_src, const void* src_a, int src_dt_a, int6
   if (pool != XML_POOL_MAX && pool != XML_POOL_MEAN) return XML_ERR_BAD_ARG;
   if ((tef_pos == nullptr) != (tef_len == nullptr)) return XML_ERR_BAD_ARG;
   if ((int64_t)d_a + d_b > POOL_MAX_D) return XML_ERR_UNSUPPORTED;
-  const int d = d_a + d_b;
-  // with the endpoint columns the destination decides the store width only, never the load width
-  const uintptr_t vec_ptrs = reinterpret_cast<uintptr_t>(src_a) | reinterpret_cast<uintptr_t>(src_b) |
-                             (tef ? (uintptr_t)0 : reinterpret_cast<uintptr_t>(dst));
-  const bool vec = d_a % 8 == 0 && d_b % 8 == 0 && (vec_ptrs & 15) == 0;
-  const int dst_align = tef ? tef_pow2_align(reinterpret_cast<uintptr_t>(dst), ((int64_t)d + 2) * (dst_dt == XML_F32 ? 4 : 2)) : 0;
-  // memory-bound: at most 256 CUs x 8 workgroups, the rest by grid stride
-  const int64_t rows = (int64_t)n * lmax;
-  const dim3 grid((unsigned)min((rows + 3) / 4, (int64_t)2048));
-  hipStream_t st = (hipStream_t)stream;
-#define XML_POOL(D, NCH, VEC, TEF) \
-  launch_pool<D, NCH, VEC, TEF>(grid, st, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b, \
-                                row_start, dst, mask, filled, n, lmax, max_len, eps, normalize, pool, tef_pos, tef_len, dst_align)
-#define XML_POOL_W(D, VEC, TEF)                 \
-  do {                                     \
-    if (d <= 2 * POOL_CHUNK) XML_POOL(D, 2, VEC, TEF); \
-    else if (d <= 6 * POOL_CHUNK) XML_POOL(D, 6, VEC, TEF); \
-    else XML_POOL(D, 8, VEC, TEF);              \
-  } while (0)
-#define XML_POOL_V(D, TEF) \
-  do { if (vec) XML_POOL_W(D, true, TEF); else XML_POOL_W(D, false, TEF); } while (0)
-  if (dst_dt == XML_F32) { if (tef) XML_POOL_V(float, true); else XML_POOL_V(float, false); }
-  else { if (tef) XML_POOL_V(bf16_t, true); else XML_POOL_V(bf16_t, false); }
-#undef XML_POOL_V
-#undef XML_POOL_W
-#undef XML_POOL
-  XML_CHECK_LAUNCH();
-  return XML_OK;
+  return pool_dispatch(tef, false, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b, row_start,
+                       dst, dst_dt, mask, filled, n, lmax, max_len, eps, normalize, pool, tef_pos, tef_len, 0, nullptr, nullptr, 0,
+                       nullptr, stream);
 }
 
 }  // namespace
@@ -312,4 +348,32 @@ extern "C" int xml_ingest_pool_rows_tef(int n_src, const void* src_a, int src_dt
                                         const int32_t* tef_len, xml_stream_t stream) {
   return ingest_pool_entry(true, n_src, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b,
                            row_start, dst, dst_dt, mask, filled, n, lmax, max_len, eps, normalize, pool, tef_pos, tef_len, stream);
+}
+
+// include/xmlhip_train_pool.h: the same launch over a resident store, the batch named by example ids
+extern "C" int xml_gather_pool_feature_rows(int n_src, const void* src_a, int src_dt_a, int64_t rows_a, int d_a, const int64_t* seg_a,
+                                            int norm_a, const void* src_b, int src_dt_b, int64_t rows_b, int d_b,
+                                            const int64_t* seg_b, int norm_b, const int64_t* clip_start, int64_t n_items,
+                                            const int32_t* ids, int n, const int32_t* item_of, int64_t n_examples, void* dst,
+                                            int dst_dt, float* mask, int32_t* len_out, int lmax, int max_len, float eps,
+                                            int normalize, int pool, int tef, xml_stream_t stream) {
+  XML_ENTER();
+  if (n_src != 1 && n_src != 2) return XML_ERR_BAD_ARG;
+  if (!src_a || !seg_a || !clip_start || !ids || !dst || n <= 0 || lmax <= 0 || max_len <= 0 || d_a <= 0 || rows_a <= 0 || n_items <= 0)
+    return XML_ERR_BAD_ARG;
+  if (item_of && n_examples <= 0) return XML_ERR_BAD_ARG;
+  if (src_dt_a != XML_F32 && src_dt_a != XML_F16) return XML_ERR_BAD_ARG;
+  if (n_src == 2) {
+    if (!src_b || !seg_b || d_b <= 0 || rows_b <= 0) return XML_ERR_BAD_ARG;
+    if (src_dt_b != XML_F32 && src_dt_b != XML_F16) return XML_ERR_BAD_ARG;
+  } else {                            // one source: the _b arguments are ignored
+    src_b = nullptr; seg_b = nullptr; d_b = 0; rows_b = 0; norm_b = 0; src_dt_b = src_dt_a;
+  }
+  if (dst_dt != XML_F32 && dst_dt != XML_BF16) return XML_ERR_BAD_ARG;
+  if (pool != XML_POOL_MAX && pool != XML_POOL_MEAN) return XML_ERR_BAD_ARG;
+  if ((tef != 0 && tef != 1) || (normalize != 0 && normalize != 1) || eps != eps) return XML_ERR_BAD_ARG;
+  if ((int64_t)d_a + d_b > POOL_MAX_D) return XML_ERR_UNSUPPORTED;
+  return pool_dispatch(tef != 0, true, src_a, src_dt_a, rows_a, d_a, seg_a, norm_a, src_b, src_dt_b, rows_b, d_b, seg_b, norm_b,
+                       clip_start, dst, dst_dt, mask, nullptr, n, lmax, max_len, eps, normalize, pool, nullptr, nullptr, n_items, ids,
+                       item_of, n_examples, len_out, stream);
 }

@@ -21,6 +21,8 @@
                       (utils/video_feature/convert_feature_frm_to_clip.py, normalize_and_concat.py,
                       utils/text_feature/convert_sub_feature_word_to_clip.py) and their clip-level copy of the corpus on
                       disk are not needed.  frame_clip_boundaries / sentence_word_ranges restate their index arithmetic.
+                      train_data.DeviceTrainStore takes one too (the fine rows resident, pooled in the batch gather), and
+                      PooledStore[name] pools on the host for StoreTrainDataset / StoreEvalDataset.
   StoreEvalDataset    the reference's eval-dataset contract (set_data_mode / load_gt_vid_name_for_query / items with
                       "meta" + "model_inputs") over FeatureStores, for compute_context_info / compute_query2ctx_info.
 """
@@ -200,6 +202,23 @@ class PooledStore(object):
     def n_rows(self, name):
         """clips of the video"""
         return len(self.clip_ranges(name)[0])
+
+    def __getitem__(self, name):
+        """The video's clip rows, (n_clips, dim) float32, pooled on the HOST: the reference's scripts stage by stage in the numpy
+        expressions of tests/ingest_pool_ref.py -- np.max / np.mean over each range in float32, a zero block for an empty range,
+        x / (||x|| + 1e-5) per normalised source, concatenation.  StoreTrainDataset / StoreEvalDataset take a PooledStore through
+        it (store[name][:max_len], then their own row norm); it is the host statement of the device paths."""
+        f = np.max if self.pool == "max" else np.mean
+        blocks = []
+        for store, rg, norm in zip(self.stores, self.clip_ranges(name), self.norms):
+            src = store[name]
+            block = np.zeros((len(rg), int(store.dim)), dtype=np.float32)
+            for c in range(len(rg)):
+                lo, hi = int(rg[c, 0]), int(rg[c, 1])
+                x = f(src[lo:hi].astype(np.float32), axis=0) if lo < hi else block[c]
+                block[c] = x / (np.sqrt((x * x).sum(dtype=np.float32), dtype=np.float32) + np.float32(1e-5)) if norm else x
+            blocks.append(block)
+        return np.concatenate(blocks, axis=1)
 
 
 class PartTable(object):

@@ -425,6 +425,56 @@ def gather_feature_rows(src, row_start, ids, lmax, max_len, item_of=None, normal
     return out, mask_out, len_out
 
 
+def gather_pool_feature_rows(sources, clip_start, ids, lmax, max_len, item_of=None, pool="max", normalize=True, eps=1e-5,
+                             tef=False, out_dtype=torch.float32, out=None, mask_out=None, len_out=None, want_len=True):
+    """One stream of a training batch from a device-resident FRAME- or WORD-level store (xml_gather_pool_feature_rows; include/
+    xmlhip_train_pool.h): gather_feature_rows with the pooling of ingest_pool_rows in the launch.  sources = 1 or 2 tuples
+    (src, seg, norm) -- src (rows_x, d_x) f16 / f32: the fine rows of the WHOLE store, seg (clip_start[-1], 2) int64: the
+    absolute half-open source-row range of every clip of every item, norm as in ingest_pool_rows.  clip_start (n_items + 1,)
+    int64, ids (n,) int32 example ids, item_of (n_examples,) int32 example -> item or None (ids are item ids) -> (features
+    (n, lmax, sum d_x + 2 * tef) [the rows of ingest_pool_rows on the same ranges, the temporal endpoint columns, zero padding],
+    mask (n, lmax) f32, lengths (n,) int32 or None with want_len=False).  out / mask_out / len_out: existing tensors to write
+    into."""
+    if len(sources) not in (1, 2):
+        raise _lib.XmlHipError("gather_pool_feature_rows: 1 or 2 sources expected, got %d" % len(sources))
+    if pool not in POOLS:
+        raise _lib.XmlHipError("gather_pool_feature_rows: pool must be 'max' or 'mean', got %r" % (pool,))
+    _req(clip_start, "clip_start", torch.int64); _req(ids, "ids", torch.int32)
+    args, d = [], 0
+    for src, seg, norm in sources:
+        _req(src, "src"); _req(seg, "seg", torch.int64)
+        if src.dtype not in (torch.float32, torch.float16) or src.dim() != 2:
+            raise _lib.XmlHipError("gather_pool_feature_rows: src: expected (rows, d) float32 or float16")
+        if seg.dim() != 2 or seg.shape[1] != 2:
+            raise _lib.XmlHipError("gather_pool_feature_rows: seg: expected (R, 2) int64, one source-row range per clip row")
+        args += [_p(src), dt_of(src), int(src.shape[0]), int(src.shape[1]), _p(seg), int(bool(norm))]
+        d += int(src.shape[1])
+    if len(sources) == 1:
+        args += [None, 0, 0, 0, None, 0]
+    dev = sources[0][0].device
+    n, lmax = int(ids.numel()), int(lmax)
+    dd = d + (2 if tef else 0)
+    if item_of is not None:
+        _req(item_of, "item_of", torch.int32)
+    for t, name, shape, dtype in ((out, "out", (n, lmax, dd), None), (mask_out, "mask_out", (n, lmax), torch.float32),
+                                  (len_out, "len_out", (n,), torch.int32)):
+        if t is not None:
+            _req(t, name, dtype)
+            if tuple(t.shape) != shape:
+                raise _lib.XmlHipError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+    if out is None:
+        out = torch.empty((n, lmax, dd), dtype=out_dtype, device=dev)
+    if mask_out is None:
+        mask_out = torch.empty((n, lmax), dtype=torch.float32, device=dev)
+    if len_out is None and want_len:
+        len_out = torch.empty((n,), dtype=torch.int32, device=dev)
+    check(_lib.load().xml_gather_pool_feature_rows(
+        len(sources), *args, _p(clip_start), clip_start.numel() - 1, _p(ids), n, _p(item_of),
+        0 if item_of is None else item_of.numel(), _p(out), dt_of(out), _p(mask_out), _p(len_out), lmax, int(max_len), float(eps),
+        int(bool(normalize)), POOLS[pool], int(bool(tef)), _stream()), "xml_gather_pool_feature_rows")
+    return out, mask_out, len_out
+
+
 def gather_index_rows(table, ids, out=None):
     """out[i, :] = table[ids[i], :] for an (n_rows, w) int64 table and int32 ids, zeros for an id out of range
     (xml_gather_index_rows): the (N, 2) start / end labels -> the batch's st_ed_indices."""

@@ -9,7 +9,10 @@
                       video item, row prefixes, the (N, 2) start / end labels).  `batch(ids)` builds the keyword dict
                       xml_forward_train takes with one xml_gather_feature_rows launch per stream and one xml_gather_index_rows
                       for the labels; `fill(static, ids)` writes the same batch into existing tensors (GraphedTrainStep.static).
-                      Per step the host sends the example ids, nothing else.
+                      Per step the host sends the example ids, nothing else.  The video and / or the subtitle store may
+                      be an ingest.PooledStore (frame- / word-level rows): its fine rows stay resident with the absolute
+                      source-row range of every clip, and that stream's launch is xml_gather_pool_feature_rows -- the clip
+                      pooling, the per-source norms and the collate in the gather.
   train_epoch         the reference's epoch loop on a DeviceTrainStore, eager (train_step) or through a captured
                       GraphedTrainStep (fill + replay, losses read once at the end).
 
@@ -153,8 +156,32 @@ def _store_items(store, what):
     return names, start
 
 
+def _upload_rows(store, total, device, chunk_bytes):
+    """The first `total` rows of a FeatureStore -> a device tensor in the store's dtype."""
+    dim, dt = int(store.dim), _TORCH_DT[store.dtype]
+    rows = torch.empty((total, dim), dtype=dt, device=device)
+    # memory map -> pinned chunks (two, alternating) -> device
+    step = max(1, chunk_bytes // (dim * rows.element_size()))
+    cuda = torch.device(device).type == "cuda"
+    stage = [torch.empty((min(step, total), dim), dtype=dt, pin_memory=cuda) for _ in range(2 if cuda else 1)]
+    done = [None, None]
+    for ci, a in enumerate(range(0, total, step)):
+        b, s = min(a + step, total), ci % len(stage)
+        if done[s] is not None:
+            done[s].synchronize()
+        stage[s].numpy()[:b - a] = store.data[a:b]
+        rows[a:b].copy_(stage[s][:b - a], non_blocking=True)
+        if cuda:
+            done[s] = torch.cuda.Event()
+            done[s].record()
+    if cuda:
+        torch.cuda.current_stream(device).synchronize()
+    return rows
+
+
 class _Resident(object):
     """One FeatureStore on the device: rows in the store's dtype + the row prefix."""
+    pooled = False
 
     def __init__(self, store, what, device, chunk_bytes=64 << 20):
         self.names, start = _store_items(store, what)
@@ -162,25 +189,41 @@ class _Resident(object):
         self.rows_of = np.diff(start)
         self.dim = int(store.dim)
         self.row_start = torch.from_numpy(start).to(device)
-        total = int(start[-1])
-        dt = _TORCH_DT[store.dtype]
-        self.rows = torch.empty((total, self.dim), dtype=dt, device=device)
-        # memory map -> pinned chunks (two, alternating) -> device
-        step = max(1, chunk_bytes // (self.dim * self.rows.element_size()))
-        cuda = torch.device(device).type == "cuda"
-        stage = [torch.empty((min(step, total), self.dim), dtype=dt, pin_memory=cuda) for _ in range(2 if cuda else 1)]
-        done = [None, None]
-        for ci, a in enumerate(range(0, total, step)):
-            b, s = min(a + step, total), ci % len(stage)
-            if done[s] is not None:
-                done[s].synchronize()
-            stage[s].numpy()[:b - a] = store.data[a:b]
-            self.rows[a:b].copy_(stage[s][:b - a], non_blocking=True)
-            if cuda:
-                done[s] = torch.cuda.Event()
-                done[s].record()
-        if cuda:
-            torch.cuda.current_stream(device).synchronize()
+        self.rows = _upload_rows(store, int(start[-1]), device, chunk_bytes)
+        self.nbytes = self.rows.numel() * self.rows.element_size() + self.row_start.numel() * 8
+
+
+class _PooledResident(object):
+    """One ingest.PooledStore on the device: every source's FINE rows in the store's dtype, the items (the names all sources
+    hold, in the first source's row order), clip_start (n_items + 1) over one clip numbering, and per source the (clips, 2)
+    table of ABSOLUTE source-row ranges: PooledStore.clip_ranges(name) plus the item's first row in that source.  Raises
+    ValueError, by name, where the sources disagree on a clip count or a range lies outside its source (clip_ranges)."""
+    pooled = True
+
+    def __init__(self, pstore, what, device, chunk_bytes=64 << 20):
+        first = pstore.stores[0]
+        self.names = [k for k in sorted(first.index, key=lambda k: first.index[k][0]) if k in pstore]
+        if not self.names:
+            raise ValueError("%s store: the sources share no item" % what)
+        self.item = {k: i for i, k in enumerate(self.names)}
+        self.dim, self.pool = int(pstore.dim), pstore.pool
+        ranges = [pstore.clip_ranges(k) for k in self.names]
+        self.rows_of = np.array([len(r[0]) for r in ranges], dtype=np.int64)
+        start = np.concatenate([[0], np.cumsum(self.rows_of)]).astype(np.int64)
+        self.clip_start = torch.from_numpy(start).to(device)
+        self.sources = []
+        self.nbytes = self.clip_start.numel() * 8
+        for si, (store, norm) in enumerate(zip(pstore.stores, pstore.norms)):
+            seg = np.zeros((max(int(start[-1]), 1), 2), dtype=np.int64)
+            for k, r, a in zip(self.names, ranges, start[:-1]):
+                f0, n_rows = int(store.index[k][0]), int(store.index[k][1])
+                if len(r[si]) and (r[si].min() < 0 or r[si].max() > n_rows):
+                    raise ValueError("%s store: a range of %r lies outside the %d rows it has in source %d" % (what, k, n_rows, si))
+                seg[a:a + len(r[si])] = r[si] + f0
+            rows = _upload_rows(store, int(store.data.shape[0]), device, chunk_bytes)
+            seg = torch.from_numpy(seg).to(device)
+            self.sources.append((rows, seg, bool(norm)))
+            self.nbytes += rows.numel() * rows.element_size() + seg.numel() * 8
 
 
 def plan_examples(examples, desc_store, video_store, sub_store, dset_name, max_desc_len, max_ctx_len, clip_length, ctx_mode):
@@ -238,7 +281,8 @@ class DeviceTrainStore(object):
                                 ("sub", self.use_sub, sub_store)):
             if not use:
                 continue
-            r = self.res[tag] = _Resident(store, tag, self.device)
+            pooled = tag != "query" and hasattr(store, "clip_ranges")        # an ingest.PooledStore: frame- / word-level rows
+            r = self.res[tag] = (_PooledResident if pooled else _Resident)(store, tag, self.device)
             key = (lambda e: str(e["desc_id"])) if tag == "query" else (lambda e: e["vid_name"])
             self.item_of[tag] = torch.tensor([r.item[key(e)] for e in self.examples], dtype=torch.int32).to(self.device)
         self.labels = torch.from_numpy(labels).to(self.device)
@@ -279,11 +323,13 @@ class DeviceTrainStore(object):
             r = self.res.get(tag)
             if r is None:
                 continue
-            f, m, _ = self.ops.gather_feature_rows(
-                r.rows, r.row_start, ids_dev, length, max_len, item_of=self.item_of[tag], normalize=self.norm[tag], eps=1e-5,
-                tef=self.use_tef and tag != "query", out_dtype=self.feature_dtype,
-                out=None if out is None else out[tag + "_feat"], mask_out=None if out is None else out[tag + "_mask"],
-                want_len=False)
+            kw = dict(item_of=self.item_of[tag], normalize=self.norm[tag], eps=1e-5, tef=self.use_tef and tag != "query",
+                      out_dtype=self.feature_dtype, out=None if out is None else out[tag + "_feat"],
+                      mask_out=None if out is None else out[tag + "_mask"], want_len=False)
+            if r.pooled:
+                f, m, _ = self.ops.gather_pool_feature_rows(r.sources, r.clip_start, ids_dev, length, max_len, pool=r.pool, **kw)
+            else:
+                f, m, _ = self.ops.gather_feature_rows(r.rows, r.row_start, ids_dev, length, max_len, **kw)
             batch[tag + "_feat"], batch[tag + "_mask"] = f, m
         batch["st_ed_indices"] = self.ops.gather_index_rows(self.labels, ids_dev, out=None if out is None
                                                             else out["st_ed_indices"])
