@@ -317,6 +317,16 @@ SIGNATURES_TRAIN_POOL = {
         c_int, c_void_p]),
 }
 
+# include/xmlhip_train_index.h
+SIGNATURES_TRAIN_INDEX = {
+    "xml_index_gather_video_rows": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int] +
+                                    [c_void_p] * 12 + [c_int, c_int, c_int, c_void_p]),
+    "xml_q2c_scores_arg_bwd_q": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p,
+                                         c_int, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "xml_pair_sim_bwd_q": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+}
+XML_INDEX_ROW_MAJOR, XML_INDEX_BLOCK_IMAGE = 0, 1
+
 _lib = None
 
 
@@ -325,7 +335,8 @@ def bind(lib):
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_INDEX.items()) + list(SIGNATURES_COMPACT.items()) + \
             list(SIGNATURES_PARTS.items()) + list(SIGNATURES_EXACT.items()) + list(SIGNATURES_VIEW.items()) + \
             list(SIGNATURES_EXACT_PACKED.items()) + list(SIGNATURES_PARTS_EXACT.items()) + \
-            list(SIGNATURES_INGEST_POOL.items()) + list(SIGNATURES_INGEST_TEF.items()) + list(SIGNATURES_TRAIN_POOL.items()):
+            list(SIGNATURES_INGEST_POOL.items()) + list(SIGNATURES_INGEST_TEF.items()) + list(SIGNATURES_TRAIN_POOL.items()) + \
+            list(SIGNATURES_TRAIN_INDEX.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -9,7 +9,7 @@ set -euo pipefail
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable"
-SRCS="api.hip linear.hip gemm256.hip gemm256p.hip attention.hip attention_train.hip q2c.hip q2c_ring.hip q2c_persist.hip topk.hip convse.hip moment.hip decode.hip parts.hip nms.hip eval.hip conv1d.hip postproc.hip train.hip gemm_tn.hip index_build.hip index_update.hip index_compact.hip index_view.hip index_parts.hip index_parts_exact.hip index_update_exact.hip ingest.hip ingest_pool.hip train_batch.hip collectives.hip exact.hip split16.hip loss_tail.hip"
+SRCS="api.hip linear.hip gemm256.hip gemm256p.hip attention.hip attention_train.hip q2c.hip q2c_ring.hip q2c_persist.hip topk.hip convse.hip moment.hip decode.hip parts.hip nms.hip eval.hip conv1d.hip postproc.hip train.hip gemm_tn.hip index_build.hip index_update.hip index_compact.hip index_view.hip index_parts.hip index_parts_exact.hip index_update_exact.hip ingest.hip ingest_pool.hip train_batch.hip train_index.hip collectives.hip exact.hip split16.hip loss_tail.hip"
 DBG_DIR=../../tools/microbench/k6_variants
 DBG_SRCS="$DBG_DIR/q2c256.hip $DBG_DIR/q2c_persist4.hip $DBG_DIR/q2c_persist32.hip"
 
@@ -24,12 +24,12 @@ build() {   # $1 = object dir, $2 = extra flags, $3 = output, $4.. = sources
     objs+=("$o")
     if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ common.h -nt "$o" ] || [ gemm.h -nt "$o" ] || [ internal.h -nt "$o" ] \
        || [ debug.h -nt "$o" ] || [ l2norm.h -nt "$o" ] || [ dispatch.h -nt "$o" ] || [ ring256.h -nt "$o" ] || [ split16.h -nt "$o" ] \
-       || [ index_rows.h -nt "$o" ] || [ ../../include/xmlhip.h -nt "$o" ] || [ ../../include/xmlhip_index.h -nt "$o" ] \
+       || [ index_rows.h -nt "$o" ] || [ loss_rows.h -nt "$o" ] || [ ../../include/xmlhip.h -nt "$o" ] || [ ../../include/xmlhip_index.h -nt "$o" ] \
        || [ ../../include/xmlhip_index_compact.h -nt "$o" ] || [ ../../include/xmlhip_index_parts.h -nt "$o" ] \
        || [ ../../include/xmlhip_index_exact.h -nt "$o" ] || [ ../../include/xmlhip_index_view.h -nt "$o" ] \
        || [ ../../include/xmlhip_index_exact_packed.h -nt "$o" ] || [ ../../include/xmlhip_index_parts_exact.h -nt "$o" ] \
        || [ ../../include/xmlhip_ingest_pool.h -nt "$o" ] || [ ../../include/xmlhip_ingest_tef.h -nt "$o" ] \
-       || [ ../../include/xmlhip_train_pool.h -nt "$o" ] || [ ingest_tef.h -nt "$o" ]; then
+       || [ ../../include/xmlhip_train_pool.h -nt "$o" ] || [ ../../include/xmlhip_train_index.h -nt "$o" ] || [ ingest_tef.h -nt "$o" ]; then
       $HIPCC $FLAGS $extra -I. -c "$s" -o "$o" &
       pids+=($!)
     fi

@@ -9,6 +9,7 @@
 // reference: get_video_level_scores xml/model_xml.py:436-453, get_modularized_queries :410-423, forward :241-251.
 #include "gemm.h"
 #include "internal.h"
+#include "loss_rows.h"
 
 namespace {
 
@@ -147,34 +148,6 @@ __global__ __launch_bounds__(256) void q2c_scores_arg_kernel(const T* __restrict
     arg[(int64_t)(q0 + row) * ld_arg + v0 + v] = mc < L ? mc : 0;
   }
 }
-
-// In-order compaction of the non-zero entries of g[0 .. count) (stride `stride`) into s_idx / s_val (capacity cap, checked by
-// the caller: count <= cap).  Returns the number of entries; all threads see it after the trailing barrier.
-__device__ __forceinline__ int collect_active(const float* __restrict__ g, int64_t stride, int count, float scale, int* s_idx,
-                                              float* s_val, int* s_cnt) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < count; i0 += 256) {
-    const int i = i0 + threadIdx.x;
-    const float v = i < count ? g[(int64_t)i * stride] * scale : 0.f;
-    const unsigned long long b = __ballot(v != 0.f);
-    if (lane == 0) s_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int off = base;
-    for (int w = 0; w < wave; ++w) off += s_cnt[w];
-    if (v != 0.f) {
-      const int pos = off + __popcll(b & ((1ull << lane) - 1ull));
-      s_idx[pos] = i;
-      s_val[pos] = v;
-    }
-    base += s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    __syncthreads();
-  }
-  return base;
-}
-
-constexpr int Q2C_BWD_CAP = 1024;      // pairs with a gradient per row / column of dscores (all of them when nq, nv <= 1024)
-constexpr int Q2C_BWD_MAXH = 2048;
 
 // (F.normalize backward of a row, as in l2norm_bwd_kernel: dx = (dy - x (x . dy) / den^2) / den, den = max(|x|, eps); when
 // the norm is clamped it is a constant and only dy / den survives.)

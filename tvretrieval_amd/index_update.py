@@ -342,6 +342,7 @@ class BlockTable(object):
         self._free = [[] for _ in range(17)]                      # length -> sorted first blocks of the maximal free runs
         self._free[16] = [t * 16 for t in range(n_tiles)]
         self.free_blocks = n_tiles * 16
+        self.compactions = 0              # raised by every commit_compact that moved a run: a cached slot -> run table is stale
 
     # ---- queries ----------------------------------------------------------------------------------------------------------
     def run_of(self, slot):
@@ -598,6 +599,7 @@ class BlockTable(object):
                 self._release(slot)
             for slot, (_, (first, nb)) in moves.items():
                 self._take(first, nb, slot)
+            self.compactions += bool(moves)
 
 
 class _TablePlan(object):

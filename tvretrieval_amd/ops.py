@@ -1713,6 +1713,65 @@ def index_gather_blocks(src_block, k6_src, bits_src, n_blocks_src, k6_dst, bits_
           "xml_index_gather_blocks")
 
 
+# ---- training on a resident index (include/xmlhip_train_index.h; tvretrieval_amd/train_index.py) ------------------------------
+def index_gather_video_rows(slots, first_block, vlen, cn_src, f2_src, mask_src, length, n_blocks=0, out=None):
+    """xml_index_gather_video_rows: the context operands of a training batch from the index rows of its videos, the model's 1
+    or 2 modalities in one launch.  slots (n,) int32 device: index row / slot per batch item; first_block (n,) int32 device:
+    the first block of every item's run when cn_src holds TiledRows (n_blocks: the blocks of their image), else None;
+    vlen (Nv,) int32.  cn_src / f2_src / mask_src: per modality the index's K6 operand (a TiledRows, or a row-major
+    (Nv, lpad, H) tensor), feat2 (Nv, lpad, H) and mask (Nv, lpad) f32.  -> per modality (cn (n, length, H), f2 (n, length, H),
+    mask (n, length) f32); rows beyond a video's valid length and items out of range are zero with mask 0.
+    out: the same structure of existing tensors to write into."""
+    n_mod = len(cn_src)
+    if n_mod not in (1, 2) or not (len(f2_src) == len(mask_src) == n_mod):
+        raise _lib.XmlHipError("index_gather_video_rows: 1 or 2 modalities, one K6 operand, feat2 and mask each")
+    image = isinstance(cn_src[0], TiledRows)
+    if any(isinstance(t, TiledRows) != image for t in cn_src):
+        raise _lib.XmlHipError("index_gather_video_rows: the modalities' K6 operands must have one form")
+    _req(slots, "slots", torch.int32); _req(vlen, "vlen", torch.int32)
+    n, length = int(slots.numel()), int(length)
+    nv, lpad, hidden = (int(x) for x in f2_src[0].shape)
+    dt = f2_src[0].dtype
+    if image:
+        _req(first_block, "first_block", torch.int32)
+        if first_block.numel() != n or int(n_blocks) <= 0:
+            raise _lib.XmlHipError("index_gather_video_rows: first_block (n,) int32 and n_blocks >= 1 expected with a block image")
+        es = f2_src[0].element_size()
+        per_tile = 256 * hidden if (hidden * es) % 64 == 0 else 0          # elements of a tile of whole 64-byte slices
+    if vlen.numel() != nv or not 0 < length <= lpad or n <= 0:
+        raise _lib.XmlHipError("index_gather_video_rows: vlen (Nv,), a batch of n >= 1 and 0 < length <= lpad = %d expected" % lpad)
+    outs = []
+    for m in range(n_mod):
+        _req(f2_src[m], "feat2", dt); _req(mask_src[m], "mask", torch.float32)
+        data = cn_src[m].data if image else cn_src[m]
+        _req(data, "cn_src", dt)
+        if tuple(f2_src[m].shape) != (nv, lpad, hidden) or tuple(mask_src[m].shape) != (nv, lpad):
+            raise _lib.XmlHipError("index_gather_video_rows: feat2 (Nv, lpad, H) and mask (Nv, lpad) expected per modality")
+        if image and (not per_tile or data.numel() < (int(n_blocks) + 15) // 16 * per_tile):
+            raise _lib.XmlHipError("index_gather_video_rows: a K6 image of whole 64-byte slices that holds n_blocks = %d blocks "
+                                   "expected" % int(n_blocks))
+        if not image and tuple(data.shape) != (nv, lpad, hidden):
+            raise _lib.XmlHipError("index_gather_video_rows: a row-major K6 operand of shape (Nv, lpad, H) expected")
+        if out is not None:
+            cn, f2, mk = out[m]
+            _req(cn, "cn", dt); _req(f2, "f2", dt); _req(mk, "mask_out", torch.float32)
+            if tuple(cn.shape) != (n, length, hidden) or tuple(f2.shape) != (n, length, hidden) or tuple(mk.shape) != (n, length):
+                raise _lib.XmlHipError("index_gather_video_rows: out: (n, length, H) x 2 and (n, length) expected per modality")
+        else:
+            cn = torch.empty((n, length, hidden), dtype=dt, device=slots.device)
+            f2 = torch.empty((n, length, hidden), dtype=dt, device=slots.device)
+            mk = torch.empty((n, length), dtype=torch.float32, device=slots.device)
+        outs.append((cn, f2, mk, data))
+    b = outs[1] if n_mod == 2 else (None, None, None, None)
+    a = outs[0]
+    check(_lib.load().xml_index_gather_video_rows(
+        n_mod, _lib.XML_INDEX_BLOCK_IMAGE if image else _lib.XML_INDEX_ROW_MAJOR, _p(slots), _p(first_block) if image else None, n,
+        _p(vlen), nv, int(n_blocks) if image else 0, lpad, _p(a[3]), _p(f2_src[0]), _p(mask_src[0]), _p(b[3]),
+        _p(f2_src[1]) if n_mod == 2 else None, _p(mask_src[1]) if n_mod == 2 else None, _p(a[0]), _p(a[1]), _p(a[2]), _p(b[0]),
+        _p(b[1]), _p(b[2]), length, hidden, dt_of(dt), _stream()), "xml_index_gather_video_rows")
+    return [o[:3] for o in outs]
+
+
 # ---- long videos as chains of slots (include/xmlhip_index_parts.h; MutableCorpusIndex(part_overlap=O)) ------------------------
 def _chain_tables(tables, names, what):
     """The (capacity,) int32 chain tables `names` of an index (or of any object that carries them) and its max_parts."""

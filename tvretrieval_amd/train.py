@@ -664,7 +664,11 @@ class GraphedTrainStep(object):
     (set_train_st_ed: re-create the object).
     Returns (loss, loss_dict) as 0-d DEVICE tensors; reading them synchronises."""
 
-    def __init__(self, model, optimizer, batch, grad_clip=-1, warmup_steps=2):
+    def __init__(self, model, optimizer, batch, grad_clip=-1, warmup_steps=2, forward=None):
+        # forward: the function that makes (loss, parts) of model and the static batch -- xml_forward_train, or
+        # train_index.xml_forward_train_index with batch = dict(index=..., **IndexTrainStore.batch(...)): entries of the batch
+        # that are no tensors (the index) are handed on as they are.
+        self.forward = xml_forward_train if forward is None else forward
         # data-parallel runs: with a GradientReducer attached, its bucketed all-reduces (xml_rccl_allreduce_avg_f32 on the
         # reducer's side stream, ordered by events behind the backward kernels of each bucket) are captured as parallel
         # branches of the same graph -- the overlap with backward is part of every replay.  Every rank must construct the
@@ -765,8 +769,7 @@ class GraphedTrainStep(object):
 
     def _body(self, captured=False):
         opt = self.opt
-        loss, parts = xml_forward_train(self.model, neg_ctx_rank=self.neg_ctx, neg_q_rank=self.neg_q, as_tensors=True,
-                                        **self.static)
+        loss, parts = self.forward(self.model, neg_ctx_rank=self.neg_ctx, neg_q_rank=self.neg_q, as_tensors=True, **self.static)
         if opt._reducer is not None:
             opt._reducer.begin()
         opt.flat_g.zero_()
@@ -941,10 +944,10 @@ def allreduce_gradients(optimizer, group=None, bucket_bytes=64 << 20):
         flat.div_(world)
 
 
-def train_step(model, optimizer, batch, grad_clip=-1, group=None):
+def train_step(model, optimizer, batch, grad_clip=-1, group=None, forward=xml_forward_train):
     """One iteration of the reference's loop (xml/train.py:78-95): forward, zero_grad, backward, [global clip],
-    all-reduce (multi-process only), optimizer step.  `batch` = dict of the XML.forward keyword arguments."""
-    loss, loss_dict = xml_forward_train(model, **batch)
+    all-reduce (multi-process only), optimizer step.  `batch` = dict of the keyword arguments of `forward` (XML.forward's)."""
+    loss, loss_dict = forward(model, **batch)
     optimizer.zero_grad()
     loss.backward()
     allreduce_gradients(optimizer, group)

@@ -364,6 +364,34 @@ def q2c_scores_l2norm_bwd_multi(sets, dscores, scale=1.0):
     return outs
 
 
+def q2c_scores_arg_bwd_q(sets, dscores, scale=1.0):
+    """The QUERY gradient of q2c_scores_arg for the model's 1 or 2 modalities in one launch (xml_q2c_scores_arg_bwd_q;
+    include/xmlhip_train_index.h).  sets: list of (query (Nq, H), qn (Nq, H), cn (Nv, L, H) normalised rows, mask (Nv, L) f32,
+    arg (Nq, Nv) int32) -> list of dquery in the activation dtype.  The context rows get no gradient."""
+    _req(dscores, "dscores", F32)
+    n_mod = len(sets)
+    nq, hidden = sets[0][0].shape
+    nv = sets[0][2].shape[0]
+    outs, cols, ls = [], [[] for _ in range(6)], []
+    for query, qn, cn, mask, arg in sets:
+        _req(query, "query", sets[0][0].dtype); _req(qn, "qn", query.dtype); _req(cn, "cn", query.dtype); _req(mask, "mask", F32)
+        _req(arg, "arg", torch.int32)
+        l = cn.shape[1]
+        assert query.shape == (nq, hidden) and qn.shape == (nq, hidden) and cn.shape == (nv, l, hidden)
+        assert mask.shape == (nv, l) and arg.shape == (nq, nv) and arg.stride(0) == nv
+        dq = torch.empty_like(query)
+        outs.append(dq)
+        for c, v in zip(cols, (query, qn, cn, mask, dq, arg)):
+            c.append(v.data_ptr())
+        ls.append(l)
+    assert dscores.shape == (nq, nv) and dscores.stride(1) == 1
+    vp = lambda vals: (ctypes.c_void_p * n_mod)(*vals)      # noqa: E731
+    check(_lib.load().xml_q2c_scores_arg_bwd_q(n_mod, vp(cols[0]), vp(cols[1]), vp(cols[2]), vp(cols[3]), _p(dscores),
+                                               dscores.stride(0), float(scale), vp(cols[4]), nq, nv, (ctypes.c_int * n_mod)(*ls),
+                                               hidden, vp(cols[5]), nv, dt_of(sets[0][0]), _stream()), "xml_q2c_scores_arg_bwd_q")
+    return outs
+
+
 def loss_combine(st_ed, rank2, w_st_ed, w_neg_ctx, w_neg_q):
     """-> (parts (4,) f32 [weighted st_ed, neg_ctx, neg_q, sum], overall 0-d f32); st_ed 0-d / rank2 (2,) f32 or None."""
     ref = st_ed if st_ed is not None else rank2
@@ -401,6 +429,16 @@ def pair_sim_bwd(q, f2, dsim):
     check(_lib.load().xml_pair_sim_bwd(_p(q), _p(f2), _p(dsim), _p(dq), _p(df2), n, l, hidden, dt_of(q), _stream()),
           "xml_pair_sim_bwd")
     return dq, df2
+
+
+def pair_sim_bwd_q(f2, dsim):
+    """dq of pair_sim alone (xml_pair_sim_bwd_q; include/xmlhip_train_index.h): f2 (N, L, H), dsim (N, L) f32 -> (N, H)."""
+    _req(f2, "f2"); _req(dsim, "dsim", F32)
+    n, l, hidden = f2.shape
+    assert dsim.shape == (n, l)
+    dq = torch.empty((n, hidden), dtype=f2.dtype, device=f2.device)
+    check(_lib.load().xml_pair_sim_bwd_q(_p(f2), _p(dsim), _p(dq), n, l, hidden, dt_of(f2), _stream()), "xml_pair_sim_bwd_q")
+    return dq
 
 
 def span_loss(sims, conv_w, masks, st_ed, merged, ks, gout=None):
